@@ -34,11 +34,21 @@ utterance range shard_range(r) with no collective on the data path
 (utterances are independent).  After the timed region every
 rank's hypotheses (labels, fp64 log-prob) are gathered to rank 0 over gloo
 (the host-side gather of north_star), counted against the global batch, and
-checked bit for bit against a 1-GPU decode of the same utterance ids on rank
-0's device.
+(--full) checked bit for bit against a 1-GPU decode of the same utterance ids
+on rank 0's device.
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+results when --dump-outputs DIR is given, and prints the line (metric, value,
+ms_per_step, the schedule, the gather digest).  --full adds everything else
+the line can hold, each measured or checked after (or, for the timeline and
+the clocks, during) the timed steps: the CPU baseline and the oracle parity
+witness, the roofline with the committed profile figures, the live GEMM and
+stand-alone decoder timings, the per-batch timeline, the clocks and the CU
+placement; those fields are null in a plain run's line.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C4]
                     [--global-batch G | --batch B] [--decode-only] [--no-pipeline]
+                    [--full] [--dump-outputs DIR]
 """
 import argparse
 import collections
@@ -168,6 +178,39 @@ def hyp_digest(hyps, logp) -> str:
         m.update(b"|")
         m.update(np.float64(lp).tobytes())
     return m.hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs writes at most this much
+
+
+def dump_outputs(directory, labels, lengths, logp, rank: int = 0, world: int = 1, seed: int = 20261015):
+    """--dump-outputs: what the timed path handed its caller in the last step,
+    as .npy files: labels [utterances, T] (float32; label ids, -1 past each
+    utterance's length, so that no stale host bytes are written), lengths
+    (float32) and logp (float64, the beam scores' own precision).  Outputs
+    beyond DUMP_LIMIT_BYTES are cut to a fixed, seeded sample of utterances
+    (their ids in sample_ids.npy).  Returns the written paths."""
+    labels, lengths = np.asarray(labels), np.asarray(lengths)
+    logp = np.asarray(logp, np.float64)
+    n, width = labels.shape
+    per_utt = 4 * width + 4 + 8 + 4   # labels row, length, logp, sample id
+    ids = None
+    if n * per_utt > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // per_utt)
+        ids = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        labels, lengths, logp = labels[ids], lengths[ids], logp[ids]
+    lab = np.where(np.arange(width)[None, :] < lengths[:, None], labels, -1).astype(np.float32)
+    arrays = {"labels": lab, "lengths": lengths.astype(np.float32), "logp": logp}
+    if ids is not None:
+        arrays["sample_ids"] = ids.astype(np.float32)
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    paths = []
+    for name, a in arrays.items():
+        np.save(d / f"{name}{sfx}.npy", a)
+        paths.append(d / f"{name}{sfx}.npy")
+    return paths
 
 
 # ---------------------------------------------------------------- workload
@@ -556,6 +599,17 @@ def main():
     ap.add_argument("--beam", type=int, default=None)
     ap.add_argument("--waves", type=int, default=0)
     ap.add_argument("--decode-only", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline figure does not need: "
+                         "the CPU baseline and oracle parity, the roofline and profile figures, the live GEMM and "
+                         "stand-alone decoder timings, the per-batch timeline, clock and CU placement of the "
+                         "timed run, and the 1-GPU re-decode of gathered shards (default: none of these; their "
+                         "fields of the line are then null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned to its caller as "
+                         "DIR/labels.npy [utterances, T] (float32, -1 past an utterance's length), "
+                         "DIR/lengths.npy (float32) and DIR/logp.npy (float64); with --gpus N rank r writes "
+                         "<name>_rank<r>.npy for its shard")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-serialized", action="store_true",
                     help="skip the live stand-alone decoder timing after the timed region (profiling runs: "
@@ -1027,7 +1081,7 @@ def finish(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong, elap
         if len(hyps) != GB:
             raise AssertionError(f"gathered {len(hyps)} hypotheses, expected {GB}")
         gather = {"utterances": len(hyps), "digest": hyp_digest(hyps, lps)[:16]}
-        if world > 1 and not args.no_verify:
+        if world > 1 and args.full and not args.no_verify:
             # the same utterance ids decoded shard by shard on this one GPU
             ok = True
             for (f, h, l) in records:
@@ -1047,6 +1101,8 @@ def finish(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong, elap
                 raise AssertionError("gathered hypotheses differ from the 1-GPU decode")
     if world > 1:
         dist.barrier()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, labels, lens, lp, rank, world)
 
     frames = GB * T * args.steps
     value = frames / elapsed
@@ -1056,7 +1112,7 @@ def finish(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong, elap
     # one decode launch covers a pipeline batch (Bl utterances); the parity
     # witness is the last collected batch
     Bl, best_p = parity_src if parity_src else (B, best)
-    if avg_kernel_ms:
+    if avg_kernel_ms and args.full:
         achieved = bpf * Bl * T / (avg_kernel_ms * 1e-3) / 1e9
         ms_, waves_run, _ = dec_config
         variant = decoder_variant(V, waves_run, ms_)
@@ -1102,7 +1158,7 @@ def finish(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong, elap
                            "see roofline.issue for the measured issue/wait fractions"}
 
     mfma = None
-    if rank == 0 and world == 1 and not args.decode_only:
+    if args.full and rank == 0 and world == 1 and not args.decode_only:
         mfma = measure_gemms(asr, d_x, d_wih, d_hid0, d_wout, d_bout, d_emis0, T, B, In, H, V,
                              fused=(d_whh, d_bih, d_bhh) if (sched or {}).get("fused_emission") else None)
         pmc = load_mfma_counters(args.config)
@@ -1126,7 +1182,7 @@ def finish(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong, elap
 
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if isinstance(d_emis_last, tuple):   # (host emissions, how they were obtained)
             emis_host, note = d_emis_last
         else:
@@ -1261,8 +1317,9 @@ def main_native(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong,
         run(1)
     run(args.warmup)
     kernel_ms.clear()
-    timeline = not args.no_timeline
-    clock = ClockSampler(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
+    timeline = args.full and not args.no_timeline
+    clock = (ClockSampler(int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count()))
+             if args.full else None)
     if world > 1:
         dist.barrier()
     gc.collect()
@@ -1270,7 +1327,8 @@ def main_native(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong,
     asr.synchronize()
     if timeline:   # per-batch stage stamps of the timed run (4 timing events per batch), from now
         pl.set_timing(True)
-    clock.start()
+    if clock is not None:
+        clock.start()
     take.wait = 0.0
     c0 = time.process_time()
     t0 = time.perf_counter()
@@ -1278,7 +1336,7 @@ def main_native(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong,
     asr.synchronize()
     elapsed = time.perf_counter() - t0
     host_cpu_ms = 1e3 * (time.process_time() - c0) / args.steps
-    clock_fig = clock.stop()
+    clock_fig = clock.stop() if clock is not None else None
     gc.enable()
     stages = None
     if timeline:
@@ -1288,13 +1346,15 @@ def main_native(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong,
             np.savetxt(os.environ["ASR_BENCH_TIMELINE"], stamps, fmt="%.4f",
                        header="production start, production end, decode start, decode end (ms)")
         pl.set_timing(False)
-    placement = {"streams": [list(r) for r in pl.placement()]}
-    try:   # physical CUs per XCD that each role's CU mask reaches (HW_REG_XCC_ID / HW_ID probe)
-        for role in ("decode", "production"):
-            if any(r[0] == role for r in placement["streams"]):
-                placement[role + "_cus_per_xcd"] = pl.probe_placement(role)
-    except Exception as e:  # pragma: no cover
-        placement["probe_error"] = str(e)
+    placement = None
+    if args.full:
+        placement = {"streams": [list(r) for r in pl.placement()]}
+        try:   # physical CUs per XCD that each role's CU mask reaches (HW_REG_XCC_ID / HW_ID probe)
+            for role in ("decode", "production"):
+                if any(r[0] == role for r in placement["streams"]):
+                    placement[role + "_cus_per_xcd"] = pl.probe_placement(role)
+        except Exception as e:  # pragma: no cover
+            placement["probe_error"] = str(e)
     if hostlog is not None:
         with open(os.environ["ASR_BENCH_HOSTLOG"], "w") as f:
             for what, tt in hostlog:
@@ -1316,10 +1376,10 @@ def main_native(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong,
     Kb = beam + 1
     kcap = -(-(Kb + max(8, Kb // 8)) // 32) * 32
     # buffers for the GEMM timing
-    hid0, em0 = asr.DeviceMatrix(T * B, H), asr.DeviceMatrix(T * B, V)
+    hid0, em0 = (asr.DeviceMatrix(T * B, H), asr.DeviceMatrix(T * B, V)) if args.full else (None, None)
     fused = desc["fused_emission"]
     em_last = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the exact bytes the last collected batch's decode consumed (the
         # parity witness of the measured path), and a check that
         # model_emissions reproduces them (the 1-GPU re-decode relies on it)
@@ -1334,7 +1394,7 @@ def main_native(args, asr, rank, world, first, GB, B, T, In, H, V, beam, strong,
         if not same:
             raise SystemExit("model_emissions does not reproduce the pipeline's emissions")
     ser = None
-    if (rank == 0 and desc["mode"] == asr.PIPELINE_MODES[1] and desc["decode_cus"] < 256
+    if (args.full and rank == 0 and desc["mode"] == asr.PIPELINE_MODES[1] and desc["decode_cus"] < 256
             and not args.no_serialized):
         dc = desc["decode_cus"]
         conc = max(1, (16 if kcap <= 64 else 9) * dc // Bp)   # the decodes the decode CUs hold

@@ -66,13 +66,31 @@ def test_c2_chip_filling_schedule_independent():
     assert co["gather"] == base["gather"]
 
 
+def test_plain_run_dumps_what_it_gathered(tmp_path):
+    """A plain run (no --full) times the steps, leaves every figure that takes
+    work of its own null, and --dump-outputs writes the last step's results:
+    the dumped labels / lengths / log-probs hash to the line's gather digest."""
+    import numpy as np
+    import bench
+    line = _bench("--dump-outputs", str(tmp_path))
+    assert line["steps"] == 6 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 64 * 100 * 6 / (line["ms_per_step"] * 6e-3)) <= 1e-3 * line["value"]
+    for k in ("roofline", "mfma", "cpu_baseline", "parity", "stages", "clock", "cu_placement"):
+        assert line[k] is None, k
+    lab, ln, lp = (np.load(tmp_path / f"{n}.npy") for n in ("labels", "lengths", "logp"))
+    assert lab.dtype == np.float32 and lab.shape == (64, 100) and ln.dtype == np.float32 and lp.dtype == np.float64
+    assert ((lab >= 0) == (np.arange(100)[None, :] < ln[:, None])).all()
+    hyps = [lab[b, :int(ln[b])].astype(np.int32).tolist() for b in range(64)]
+    assert bench.hyp_digest(hyps, lp)[:16] == line["gather"]["digest"]
+
+
 def test_c4_self_launched_ranks_match_one_rank():
     """The driver's multi-GPU form, `bench.py --gpus 2` with no rank
     variables: two rank processes (sharing this box's one GPU: ranks wrap)
     shard C4's 2048 utterances; rank 0 gathers and re-decodes every shard on
     its own device (verified_vs_1gpu), and the digest equals one rank's."""
     one = _bench(config="C4")
-    two = _bench("--gpus", "2", config="C4")
+    two = _bench("--gpus", "2", "--full", config="C4")   # --full: the 1-GPU re-decode of the gathered shards
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert one["gather"]["utterances"] == two["gather"]["utterances"] == 2048
     assert two["gather"]["verified_vs_1gpu"] is True

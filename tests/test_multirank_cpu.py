@@ -109,6 +109,32 @@ def test_merge_records_rejects_gaps():
         bench.merge_records([(0, [[1]], [0.0]), (2, [[2]], [0.0])])
 
 
+def test_dump_outputs_masks_and_samples(tmp_path, monkeypatch):
+    """--dump-outputs: float32 labels with -1 past each length, fp64 log-probs,
+    per-rank names under several ranks, and above the size limit the same
+    seeded sample of utterances every time."""
+    import numpy as np
+    import bench
+    lab = np.arange(40, dtype=np.int32).reshape(8, 5)
+    ln = np.array([0, 1, 2, 3, 4, 5, 5, 2], np.int32)
+    lp = -np.arange(8, dtype=np.float64) / 3
+    paths = bench.dump_outputs(tmp_path / "a", lab, ln, lp)
+    assert sorted(p.name for p in paths) == ["labels.npy", "lengths.npy", "logp.npy"]
+    out = np.load(tmp_path / "a" / "labels.npy")
+    assert out.dtype == np.float32 and out.shape == (8, 5)
+    for b in range(8):
+        assert out[b, :ln[b]].tolist() == lab[b, :ln[b]].tolist() and (out[b, ln[b]:] == -1).all()
+    assert np.load(tmp_path / "a" / "logp.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "logp.npy"), lp)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * (4 * 5 + 16))   # room for 3 utterances
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, lab, ln, lp, rank=1, world=2)
+    ids = np.load(tmp_path / "b" / "sample_ids_rank1.npy").astype(int)
+    assert len(ids) == 3 and len(set(ids)) == 3 and np.array_equal(ids, np.load(tmp_path / "c" / "sample_ids_rank1.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "logp_rank1.npy"), lp[ids])
+    assert np.array_equal(np.load(tmp_path / "b" / "lengths_rank1.npy"), ln[ids].astype(np.float32))
+
+
 def _run_bench(args, env_extra=None, timeout=300):
     """bench.py as the driver starts it (`python bench.py --gpus N ...`), in a
     fresh process without rank variables in its environment."""
