@@ -11,6 +11,8 @@ include/asr_amd.h — it contains no arithmetic of its own:
     RNN_Cell(batch, in, hidden).forward                   RNN_Cell.cu:65
     RNN(batch, in, hidden, time_step, num_layers).forward RNN.cu:9
     DeviceMatrix ~ cuMatrix<float> (toGpu / toCpu)        cuMatrix.h:72-105
+    LSTM(input_size, hidden_size, num_layers, bidirectional).forward
+                                          torch.nn.LSTM; no reference member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -51,6 +53,7 @@ EXPORTS = [
     "asr_stream_create", "asr_stream_destroy", "asr_stream_sync", "asr_device_sync",
     "asr_matmul", "asr_matmul_ta", "asr_matmul_tb", "asr_matadd", "asr_linear_fwd",
     "asr_rnn_cell_fwd", "asr_rnn_fwd", "asr_rnn_recur_fwd", "asr_rnn_persist_stats", "asr_rnn_emit_fwd", "asr_rnn_bidir_workspace_bytes", "asr_rnn_bidir_fwd",
+    "asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -147,6 +150,10 @@ def lib() -> ctypes.CDLL:
         "asr_pipeline_get_drain": [_vp, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_double)],
         "asr_pipeline_get_groups": [_vp, ctypes.POINTER(_i)],
         "asr_rnn_bidir_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+        "asr_lstm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp,
+                         _i, _i, _i, _i, _i, _vp],
+        "asr_lstm_recur_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp,
+                               _i, _i, _i, _i, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -169,6 +176,8 @@ def lib() -> ctypes.CDLL:
         fn.restype = _i
     L.asr_rnn_bidir_workspace_bytes.argtypes = [_i, _i, _i]
     L.asr_rnn_bidir_workspace_bytes.restype = _sz
+    L.asr_lstm_workspace_bytes.argtypes = [_i, _i, _i]
+    L.asr_lstm_workspace_bytes.restype = _sz
     _lib = L
     return L
 
@@ -414,6 +423,143 @@ class RNN:
             rnn_fwd(x, w_ih, w_hh, b_ih, b_hh, self.hiddens[l], self.T, self.B, None, stream)
             x = self.hiddens[l]
         return self.hiddens[-1]
+
+
+# ---------------------------------------------------------------------- LSTM
+def lstm_workspace_bytes(T: int, B: int, H: int) -> int:
+    """asr_lstm_workspace_bytes: 0 for a shape the LSTM kernels do not take."""
+    return int(lib().asr_lstm_workspace_bytes(T, B, H))
+
+
+def device_lengths(lengths: Sequence[int]) -> DeviceBytes:
+    """Utterance lengths as the device int32 [B] array asr_lstm_* read."""
+    ln = np.ascontiguousarray(lengths, dtype=np.int32)
+    d = DeviceBytes(max(ln.nbytes, 4))
+    check(lib().asr_memcpy_h2d(d.ptr, _ptr(ln), ln.nbytes, None), "asr_memcpy_h2d")
+    return d
+
+
+def _lstm_tail(hid: DeviceMatrix, col: int, H: int, hT, cT, lengths, work, need_work: bool, T: int, B: int):
+    """Arguments shared by lstm_fwd / lstm_recur_fwd: the output pointer of the
+    direction that writes columns [col, col + H) of hid's rows, and the rest."""
+    assert hid.rows == T * B and 0 <= col and col + H <= hid.cols, (hid.rows, hid.cols, col, H)
+    need = lstm_workspace_bytes(T, B, H)
+    if need_work and need and (work is None or work.nbytes < need):
+        raise ValueError(f"LSTM workspace of {need} bytes needed (asr_lstm_workspace_bytes)")
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    return hid.ptr + 4 * col, hid.cols, opt(hT), opt(cT), opt(lengths), opt(work)
+
+
+def lstm_fwd(x: DeviceMatrix, W_ih: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh: DeviceMatrix,
+             hid: DeviceMatrix, T: int, B: int, work: DeviceBytes, h0: Optional[DeviceMatrix] = None,
+             c0: Optional[DeviceMatrix] = None, hT: Optional[DeviceMatrix] = None,
+             cT: Optional[DeviceMatrix] = None, lengths: Optional[DeviceBytes] = None, reverse: bool = False,
+             col: int = 0, stream: int = 0) -> DeviceMatrix:
+    """One LSTM layer and direction (asr_lstm_fwd): W_ih [in, 4H], W_hh [H, 4H]
+    (gates i, f, g, o), h_t into columns [col, col + H) of hid [T*B, >= H]
+    (the row stride is hid.cols); lengths from device_lengths()."""
+    inp, H = W_ih.rows, W_hh.rows
+    assert x.rows == T * B and x.cols == inp and W_ih.cols == 4 * H and W_hh.cols == 4 * H
+    out, ldh, pht, pct, pln, pwk = _lstm_tail(hid, col, H, hT, cT, lengths, work, True, T, B)
+    check(lib().asr_lstm_fwd(x.ptr, h0.ptr if h0 else None, c0.ptr if c0 else None, W_ih.ptr, W_hh.ptr,
+                             b_ih.ptr, b_hh.ptr, out, ldh, pht, pct, pln, pwk, T, B, inp, H,
+                             int(bool(reverse)), stream), "asr_lstm_fwd")
+    return hid
+
+
+def lstm_recur_fwd(P: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh: DeviceMatrix,
+                   hid: DeviceMatrix, T: int, B: int, work: Optional[DeviceBytes] = None,
+                   h0: Optional[DeviceMatrix] = None, c0: Optional[DeviceMatrix] = None,
+                   hT: Optional[DeviceMatrix] = None, cT: Optional[DeviceMatrix] = None,
+                   lengths: Optional[DeviceBytes] = None, reverse: bool = False, col: int = 0,
+                   stream: int = 0) -> DeviceMatrix:
+    """The recurrence stage alone (asr_lstm_recur_fwd): P [T*B, 4H] holds x.W_ih
+    (read only); work is needed for H > 128."""
+    H = W_hh.rows
+    assert P.rows == T * B and P.cols == 4 * H and W_hh.cols == 4 * H
+    out, ldh, pht, pct, pln, pwk = _lstm_tail(hid, col, H, hT, cT, lengths, work, H > 128, T, B)
+    check(lib().asr_lstm_recur_fwd(P.ptr, h0.ptr if h0 else None, c0.ptr if c0 else None, W_hh.ptr, b_ih.ptr,
+                                   b_hh.ptr, out, ldh, pht, pct, pln, pwk, T, B, H, int(bool(reverse)),
+                                   stream), "asr_lstm_recur_fwd")
+    return hid
+
+
+class _DeviceView:
+    """Rows [r0, r0 + rows) of a DeviceMatrix, without owning them."""
+
+    def __init__(self, m: DeviceMatrix, r0: int, rows: int):
+        self.ptr, self.rows, self.cols, self._keep = m.ptr + 4 * r0 * m.cols, rows, m.cols, m
+
+
+class LSTM:
+    """torch.nn.LSTM(input_size, hidden_size, num_layers, bidirectional=...) for
+    inference on asr_lstm_fwd: device weights and one workspace, no arithmetic
+    here.  params[layer][direction] = (W_ih [in, 4H], W_hh [H, 4H], b_ih [4H],
+    b_hh [4H]) in this library's [in][out] layout (zeros if None); from_torch
+    takes them from a torch module.  No proj_size, no dropout."""
+
+    def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, bidirectional: bool = False,
+                 params: Optional[Sequence[Sequence[Tuple[np.ndarray, ...]]]] = None):
+        self.inp, self.H, self.L, self.D = input_size, hidden_size, num_layers, 2 if bidirectional else 1
+        H = hidden_size
+        self.layers = []
+        for l in range(num_layers):
+            i = input_size if l == 0 else self.D * H
+            shapes = ((i, 4 * H), (H, 4 * H), (4 * H, 1), (4 * H, 1))
+            dirs = []
+            for d in range(self.D):
+                p = [np.zeros(s, np.float32) for s in shapes] if params is None else params[l][d]
+                dirs.append(tuple(DeviceMatrix.from_numpy(np.asarray(a, np.float32).reshape(s))
+                                  for a, s in zip(p, shapes)))
+            self.layers.append(dirs)
+        self._work: Optional[DeviceBytes] = None
+        self._shape = None
+        self.outputs: List[DeviceMatrix] = []
+        self.h_n: Optional[DeviceMatrix] = None   # [L*D*B, H] as torch's h_n [L*D, B, H]
+        self.c_n: Optional[DeviceMatrix] = None
+
+    @classmethod
+    def from_torch(cls, module) -> "LSTM":
+        """The weight_*_l{k}[_reverse] tensors of a torch.nn.LSTM, transposed to
+        [in][out], and its biases."""
+        if getattr(module, "proj_size", 0) or not module.bias:
+            raise ValueError("LSTM.from_torch: proj_size and bias=False are not supported")
+        params = []
+        for l in range(module.num_layers):
+            dirs = []
+            for sfx in ("", "_reverse")[:2 if module.bidirectional else 1]:
+                get = lambda n: getattr(module, f"{n}_l{l}{sfx}").detach().cpu().float().numpy()   # noqa: E731
+                dirs.append((np.ascontiguousarray(get("weight_ih").T), np.ascontiguousarray(get("weight_hh").T),
+                             get("bias_ih"), get("bias_hh")))
+            params.append(dirs)
+        return cls(module.input_size, module.hidden_size, module.num_layers, module.bidirectional, params)
+
+    def forward(self, x: DeviceMatrix, T: int, B: int, lengths: Optional[Sequence[int]] = None,
+                stream: Optional[int] = None) -> DeviceMatrix:
+        """x time-major [T*B, input_size]; returns the last layer's [T*B, H or 2H]
+        (zeros past each utterance's length); h_n / c_n hold the final states.
+        The two directions of a layer write the two halves of one buffer."""
+        H, D, st = self.H, self.D, stream or 0
+        if self._shape != (T, B):
+            need = lstm_workspace_bytes(T, B, H)
+            if not need:
+                raise AsrError(ASR_ERR_UNSUPPORTED, "asr_lstm_workspace_bytes")
+            if self._work is None or self._work.nbytes < need:
+                self._work = DeviceBytes(need)
+            self.outputs = [DeviceMatrix(T * B, D * H) for _ in range(self.L)]
+            self.h_n, self.c_n = DeviceMatrix(self.L * D * B, H), DeviceMatrix(self.L * D * B, H)
+            self._shape = (T, B)
+        ln = None if lengths is None else device_lengths(lengths)
+        for l, dirs in enumerate(self.layers):
+            for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(dirs):
+                k = (l * D + d) * B
+                lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, self.outputs[l], T, B, self._work,
+                         hT=_DeviceView(self.h_n, k, B), cT=_DeviceView(self.c_n, k, B), lengths=ln,
+                         reverse=d == 1, col=d * H, stream=st)
+            x = self.outputs[l]
+        if ln is not None:   # the kernels read it: keep it until they are done
+            check(lib().asr_stream_sync(ctypes.c_void_p(st or None)), "asr_stream_sync")
+        return self.outputs[-1]
 
 
 # ----------------------------------------------------------------------- CTC

@@ -210,6 +210,52 @@ int asr_rnn_bidir_fwd(const float* d_x, const float* d_h0, const float* const d_
                       const float* const d_b_hh[2], float* d_out, void* d_work, int T, int B,
                       int in, int H, asr_stream_t s);
 
+/* One LSTM layer and direction over a whole sequence — torch.nn.LSTM
+ * semantics (gate order i, f, g, o).  The reference has no LSTM (its only
+ * recurrent cell is the tanh RNN_Cell), so these entry points replace no
+ * reference member; they are what DeepSpeech-style CTC acoustic models need.
+ * x time-major [T*B, in]; W_ih [in, 4H], W_hh [H, 4H] in this library's
+ * [in][out] layout, gate q of hidden unit j at column q*H + j; b_ih, b_hh [4H].
+ *   z = (x_t.W_ih + h_{t-1}.W_hh) + (b_ih + b_hh)
+ *   i, f, o = sigmoid(z_i, z_f, z_o), g = tanh(z_g)
+ *   c_t = f*c_{t-1} + i*g,  h_t = o*tanh(c_t)
+ * d_h0, d_c0 [B,H] (NULL = zeros).  d_hiddens receives h_t at row t*B + b with
+ * row stride ldh >= H floats: ldh = 2H lets a forward and a reverse call fill
+ * the two halves of one [T*B, 2H] buffer (columns outside [0, H) of a row are
+ * not touched).  reverse != 0 runs the frames T-1 .. 0.  d_lengths (device
+ * int32 [B], NULL = all T): for frames t >= d_lengths[b] utterance b's h and c
+ * are carried unchanged and its output row is zeros, i.e. pack_padded_sequence
+ * / pad_packed_sequence; in reverse the utterance starts from h0 / c0 at its
+ * own last frame.  d_hT, d_cT [B,H] (NULL = not wanted) receive the state
+ * after each utterance's last valid frame (in reverse: after frame 0).
+ * d_work: asr_lstm_workspace_bytes(T,B,H) bytes, 16-B aligned (the input
+ * projection for all T, one GEMM that follows asr_set_dense_arith like
+ * asr_linear_fwd, then the cell state); the size is 0 for an invalid shape.
+ * The recurrence contracts on fp32 MFMA.  16 <= H <= 128: one launch with
+ * W_hh resident in registers, 16 utterances per workgroup; 128 < H <= 2048:
+ * one launch per frame (capturable in a graph; needs ldh % 4 == 0 and 16-B
+ * aligned d_hiddens / d_h0).  The kernel depends on H only, so an utterance's
+ * bits do not depend on its batch.
+ * ASR_ERR_ARG: a NULL required pointer, a non-positive size, ldh < H;
+ * ASR_ERR_UNSUPPORTED: H % 16 != 0, H > 2048, B*4H*4 bytes beyond one buffer
+ * resource (0x7ff00000).  No projection (proj_size), dropout or GRU. */
+size_t asr_lstm_workspace_bytes(int T, int B, int H);
+int asr_lstm_fwd(const float* d_x, const float* d_h0, const float* d_c0, const float* d_W_ih,
+                 const float* d_W_hh, const float* d_b_ih, const float* d_b_hh, float* d_hiddens,
+                 long ldh, float* d_hT, float* d_cT, const int32_t* d_lengths, void* d_work, int T,
+                 int B, int in, int H, int reverse, asr_stream_t s);
+
+/* The recurrence stage of asr_lstm_fwd alone (as asr_rnn_recur_fwd is to
+ * asr_rnn_fwd), for callers that run the input projection themselves, e.g.
+ * on another stream: d_P [T*B, 4H] holds x.W_ih (asr_linear_fwd(x, W_ih, NULL,
+ * P, T*B, in, 4H, ASR_EPI_NONE)) and is read only.  asr_lstm_fwd is exactly
+ * that GEMM into d_work followed by this call, bit for bit.  d_work (same
+ * size) holds the cell state at its end and is needed for H > 128 only. */
+int asr_lstm_recur_fwd(const float* d_P, const float* d_h0, const float* d_c0, const float* d_W_hh,
+                       const float* d_b_ih, const float* d_b_hh, float* d_hiddens, long ldh,
+                       float* d_hT, float* d_cT, const int32_t* d_lengths, void* d_work, int T,
+                       int B, int H, int reverse, asr_stream_t s);
+
 /* ---- CTC prefix beam search: replaces CTCBeamSearch (CTCBeamSearch.h:107-150,
  *      CTCBeamSearch.cu:220-312) with the semantics of the CPU decoder
  *      CTCBeamSearch.cpp:50-187 (fixes F1-F3, fp64 log domain). ---- */

@@ -1,0 +1,72 @@
+"""CPU checks of the LSTM entry points (asr_lstm_workspace_bytes, asr_lstm_fwd,
+asr_lstm_recur_fwd): exported, sized and argument-checked before any HIP call
+(no GPU here; the fake device pointers are never dereferenced on the host)."""
+import re
+import subprocess
+
+import pytest
+
+from conftest import asr
+
+NAMES = ["asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd"]
+FAKE = 0x10000   # a non-NULL, 16-byte aligned "device pointer"
+
+
+def test_symbols_in_mirror_and_library():
+    for n in NAMES:
+        assert n in asr.EXPORTS, n
+        assert hasattr(asr.lib(), n), n
+    out = subprocess.run(["nm", "-D", "--defined-only", str(asr.LIB_PATH)], capture_output=True,
+                         text=True, check=True).stdout
+    exported = set(re.findall(r" T (asr_[a-z0-9_]+)$", out, flags=re.M))
+    assert set(NAMES) <= exported
+
+
+@pytest.mark.parametrize("T,B,H", [(1, 1, 16), (7, 5, 16), (12, 50, 128), (5, 3, 144), (3, 16, 1024),
+                                   (200, 1024, 2048)])
+def test_workspace_bytes(T, B, H):
+    n = asr.lib().asr_lstm_workspace_bytes(T, B, H)
+    assert n >= (T * B * 4 * H + B * H) * 4
+    assert n % 16 == 0
+
+
+def test_workspace_bytes_invalid_shape():
+    L = asr.lib()
+    assert L.asr_lstm_workspace_bytes(4, 4, 0) == 0
+    assert L.asr_lstm_workspace_bytes(4, 4, 20) == 0
+    assert L.asr_lstm_workspace_bytes(4, 4, 2064) == 0
+    assert L.asr_lstm_workspace_bytes(0, 4, 16) == 0
+
+
+def fwd(ptr, T, B, inp, H, ldh=None):
+    p = ptr
+    return asr.lib().asr_lstm_fwd(p, p, p, p, p, p, p, p, H if ldh is None else ldh, p, p, p, p,
+                                  T, B, inp, H, 0, None)
+
+
+def recur(ptr, T, B, H, ldh=None):
+    p = ptr
+    return asr.lib().asr_lstm_recur_fwd(p, p, p, p, p, p, p, H if ldh is None else ldh, p, p, p, p,
+                                        T, B, H, 0, None)
+
+
+def test_err_arg():
+    assert fwd(None, 4, 4, 8, 16) == asr.ASR_ERR_ARG
+    assert fwd(FAKE, 0, 4, 8, 16) == asr.ASR_ERR_ARG
+    assert fwd(FAKE, 4, 4, 8, 16, ldh=15) == asr.ASR_ERR_ARG
+    assert fwd(FAKE, 4, 0, 8, 16) == asr.ASR_ERR_ARG
+    assert fwd(FAKE, 4, 4, 0, 16) == asr.ASR_ERR_ARG
+    assert recur(None, 4, 4, 16) == asr.ASR_ERR_ARG
+    assert recur(FAKE, 0, 4, 16) == asr.ASR_ERR_ARG
+    assert recur(FAKE, 4, 4, 256, ldh=255) == asr.ASR_ERR_ARG
+
+
+@pytest.mark.parametrize("H", [20, 2064])
+def test_err_unsupported(H):
+    assert fwd(FAKE, 4, 4, 8, H) == asr.ASR_ERR_UNSUPPORTED
+    assert recur(FAKE, 4, 4, H) == asr.ASR_ERR_UNSUPPORTED
+
+
+def test_err_unsupported_frame_beyond_one_buffer_resource():
+    # B * 4H * 4 bytes of one frame's input projection past one buffer resource
+    assert recur(FAKE, 1, 1 << 17, 2048) == asr.ASR_ERR_UNSUPPORTED
