@@ -13,6 +13,9 @@ include/asr_amd.h — it contains no arithmetic of its own:
     DeviceMatrix ~ cuMatrix<float> (toGpu / toCpu)        cuMatrix.h:72-105
     LSTM(input_size, hidden_size, num_layers, bidirectional).forward
                                           torch.nn.LSTM; no reference member
+    FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
+                                          waveform -> log-mel / MFCC features
+                                          (asr_fbank_*); no reference member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -54,6 +57,8 @@ EXPORTS = [
     "asr_matmul", "asr_matmul_ta", "asr_matmul_tb", "asr_matadd", "asr_linear_fwd",
     "asr_rnn_cell_fwd", "asr_rnn_fwd", "asr_rnn_recur_fwd", "asr_rnn_persist_stats", "asr_rnn_emit_fwd", "asr_rnn_bidir_workspace_bytes", "asr_rnn_bidir_fwd",
     "asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd",
+    "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
+    "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -154,6 +159,12 @@ def lib() -> ctypes.CDLL:
                          _i, _i, _i, _i, _i, _vp],
         "asr_lstm_recur_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp,
                                _i, _i, _i, _i, _vp],
+        "asr_fbank_num_frames": [_vp, _i],
+        "asr_fbank_feature_dim": [_vp],
+        "asr_fbank_host_tables": [_vp, _vp, _vp, _vp],
+        "asr_fbank_create": [_vp, ctypes.POINTER(_vp)],
+        "asr_fbank_destroy": [_vp],
+        "asr_fbank_fwd": [_vp, _vp, ctypes.c_long, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp, _i, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -178,6 +189,8 @@ def lib() -> ctypes.CDLL:
     L.asr_rnn_bidir_workspace_bytes.restype = _sz
     L.asr_lstm_workspace_bytes.argtypes = [_i, _i, _i]
     L.asr_lstm_workspace_bytes.restype = _sz
+    L.asr_fbank_workspace_bytes.argtypes = [_vp, _i, _i]
+    L.asr_fbank_workspace_bytes.restype = _sz
     _lib = L
     return L
 
@@ -560,6 +573,116 @@ class LSTM:
         if ln is not None:   # the kernels read it: keep it until they are done
             check(lib().asr_stream_sync(ctypes.c_void_p(st or None)), "asr_stream_sync")
         return self.outputs[-1]
+
+
+# ----------------------------------------------------------------- front end
+FBANK_WIN_HANN, FBANK_WIN_HAMMING, FBANK_WIN_RECT = 0, 1, 2
+FBANK_WINDOWS = {"hann": FBANK_WIN_HANN, "hamming": FBANK_WIN_HAMMING, "rect": FBANK_WIN_RECT}
+
+
+class FbankConfig(ctypes.Structure):
+    """asr_fbank_config (include/asr_amd.h)."""
+    _fields_ = [("sample_rate", _f), ("win_length", _i), ("hop_length", _i), ("n_fft", _i), ("window", _i),
+                ("preemph", _f), ("n_mels", _i), ("f_min", _f), ("f_max", _f), ("log_floor", _f),
+                ("n_mfcc", _i), ("n_context", _i)]
+
+
+class FeatureFrontend:
+    """Waveform -> log-mel / MFCC features with a +-n_context frame window
+    (asr_fbank_*; the semantics are in include/asr_amd.h), DeepSpeech's input
+    (26 MFCCs, baseline/model.py:23) by default.  window: "hann", "hamming",
+    "rect" or an ASR_FBANK_WIN_* value; f_max None = sample_rate / 2.  No
+    arithmetic here: the tables and the kernels are the library's."""
+
+    def __init__(self, sample_rate: float = 16000.0, win_length: int = 400, hop_length: int = 160,
+                 n_fft: int = 512, window="hann", preemph: float = 0.97, n_mels: int = 40, f_min: float = 0.0,
+                 f_max: Optional[float] = None, log_floor: float = 1e-10, n_mfcc: int = 26, n_context: int = 0):
+        self.h = None
+        self.cfg = FbankConfig(sample_rate, win_length, hop_length, n_fft,
+                               FBANK_WINDOWS[window] if isinstance(window, str) else int(window), preemph, n_mels,
+                               f_min, sample_rate / 2 if f_max is None else f_max, log_floor, n_mfcc, n_context)
+        h = _vp()
+        check(lib().asr_fbank_create(ctypes.byref(self.cfg), ctypes.byref(h)), "asr_fbank_create")
+        self.h = h.value
+        self._work: Optional[DeviceBytes] = None
+        self._keep = None   # the last call's uploaded inputs: alive until its kernels are done
+
+    def num_frames(self, n_samples: int) -> int:
+        return int(lib().asr_fbank_num_frames(ctypes.byref(self.cfg), int(n_samples)))
+
+    @property
+    def feature_dim(self) -> int:
+        return int(lib().asr_fbank_feature_dim(ctypes.byref(self.cfg)))
+
+    def host_tables(self) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """(window [win_length], mel [n_mels, n_fft/2 + 1], dct [n_mfcc, n_mels] or
+        None): the fp32 tables the device uses."""
+        c = self.cfg
+        win = np.zeros(c.win_length, np.float32)
+        mel = np.zeros((c.n_mels, c.n_fft // 2 + 1), np.float32)
+        dct = np.zeros((c.n_mfcc, c.n_mels), np.float32) if c.n_mfcc else None
+        check(lib().asr_fbank_host_tables(ctypes.byref(c), _ptr(win), _ptr(mel), _ptr(dct) if c.n_mfcc else None),
+              "asr_fbank_host_tables")
+        return win, mel, dct
+
+    def workspace_bytes(self, T: int, B: int) -> int:
+        return int(lib().asr_fbank_workspace_bytes(self.h, T, B))
+
+    def forward(self, wave, nsamples=None, stream: Optional[int] = None, B: Optional[int] = None,
+                S: Optional[int] = None, ldw: Optional[int] = None, T: Optional[int] = None):
+        """wave: a numpy [B, S] float32 array, or a device pointer (int) with B, S
+        (and ldw, default S) given; nsamples: None, a sequence of B counts or a
+        DeviceBytes of int32 [B].  Returns (features DeviceMatrix [T*B, F]
+        time-major, frames DeviceBytes int32 [B]); T defaults to num_frames(S)
+        (at least 1).  Asynchronous on stream; inputs uploaded here stay
+        alive in this object until the next call."""
+        st = stream or 0
+        keep = []
+        if isinstance(wave, np.ndarray):
+            wave = np.ascontiguousarray(wave, dtype=np.float32)
+            assert wave.ndim == 2, wave.shape
+            B, S = wave.shape
+            ldw = S
+            dw = DeviceMatrix(B, S)
+            dw.toGpu(wave, st)
+            keep.append(dw)
+            wptr = dw.ptr
+        else:
+            assert B is not None and S is not None, "a device pointer needs B and S"
+            wptr, ldw = int(wave), int(S if ldw is None else ldw)
+        if nsamples is not None and not isinstance(nsamples, DeviceBytes):
+            nsamples = device_lengths(nsamples)
+        keep.append(nsamples)
+        T = max(1, self.num_frames(S)) if T is None else int(T)
+        F = self.feature_dim
+        out = DeviceMatrix(T * B, F)
+        frames = DeviceBytes(4 * B)
+        need = self.workspace_bytes(T, B)
+        if need and (self._work is None or self._work.nbytes < need):
+            self._work = DeviceBytes(need)
+        check(lib().asr_fbank_fwd(self.h, wptr, ldw, nsamples.ptr if nsamples is not None else None, B, S,
+                                  out.ptr, F, frames.ptr, self._work.ptr if need else None, T, st),
+              "asr_fbank_fwd")
+        self._keep = keep
+        return out, frames
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib().asr_fbank_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def device_int32(d: DeviceBytes, n: int, stream: int = 0) -> np.ndarray:
+    """Host copy of a device int32 [n] buffer (e.g. FeatureFrontend's frames)."""
+    out = np.empty(n, np.int32)
+    check(lib().asr_memcpy_d2h(_ptr(out), d.ptr, 4 * n, stream), "asr_memcpy_d2h")
+    return out
 
 
 # ----------------------------------------------------------------------- CTC

@@ -536,6 +536,83 @@ int asr_pipeline_set_timing(asr_pipeline_t* p, int on);
 int asr_pipeline_get_timeline(asr_pipeline_t* p, int cap, int* n, long long* batch, float* t);
 int asr_pipeline_destroy(asr_pipeline_t* p);
 
+/* ---- audio front end: waveform -> log-mel / MFCC features -----------------
+ * No reference member is replaced: the reference has no feature extraction
+ * (baseline/main.py:39 feeds torch.rand in place of the 26 MFCCs with a
+ * +-n_context window that baseline/model.py:23 is sized for).  One handle per
+ * configuration; its tables (window, twiddles, mel weights, DCT) are computed
+ * on the host in double, rounded once to fp32 and uploaded at create.
+ *
+ * Framing: an utterance of n samples has n < win_length ? 0 :
+ * 1 + (n - win_length) / hop_length frames, no centring, no padding; frame t
+ * is samples [t*hop, t*hop + win) of the pre-emphasised signal
+ * (y[i] = x[i] - preemph * x[i-1] over the whole utterance, x[-1] = 0) times
+ * the window, zero-padded at the end to n_fft (unlike torch.stft, which for
+ * win < n_fft centres the window inside n_fft samples).
+ * Power: P[k] = re^2 + im^2, k = 0 .. n_fft/2, no 1/N scaling.
+ * Mel: mel(f) = 2595 log10(1 + f/700); n_mels + 2 points equally spaced in
+ * mel from f_min to f_max, back in Hz; filter m has corners (lo, c, hi) =
+ * points m, m+1, m+2 and weight max(0, min((f_k - lo)/(c - lo),
+ * (hi - f_k)/(hi - c))) at f_k = k * sample_rate / n_fft, no area
+ * normalisation; e[m] = ln(max(sum_k w[m][k] P[k], log_floor)).
+ * n_mfcc > 0: c_k = s_k sum_m e[m] cos(pi k (2m+1) / (2 n_mels)), s_0 =
+ * sqrt(1/n_mels), s_k = sqrt(2/n_mels) (orthonormal DCT-II, no liftering).
+ * Context: output row t is base frames t-C .. t+C, D floats each, zeros for
+ * a frame outside [0, frames_b); rows t >= frames_b are all zeros (the
+ * padding asr_lstm_fwd writes and asr_ctc_decode_ex skips). */
+typedef enum asr_fbank_window {
+    ASR_FBANK_WIN_HANN = 0,     /* symmetric: 0.5 - 0.5 cos(2 pi n / (win - 1)) */
+    ASR_FBANK_WIN_HAMMING = 1,  /* 0.54 - 0.46 cos(2 pi n / (win - 1))          */
+    ASR_FBANK_WIN_RECT = 2
+} asr_fbank_window;
+
+typedef struct asr_fbank_config {
+    float sample_rate;          /* Hz, > 0                                       */
+    int win_length, hop_length; /* samples: 2 <= win <= n_fft, hop >= 1          */
+    int n_fft;                  /* 256, 512, 1024 or 2048                        */
+    int window;                 /* ASR_FBANK_WIN_*                               */
+    float preemph;              /* 0 <= a < 1; 0 = off                           */
+    int n_mels;                 /* 1 .. 128                                      */
+    float f_min, f_max;         /* 0 <= f_min < f_max <= sample_rate / 2         */
+    float log_floor;            /* > 0                                           */
+    int n_mfcc;                 /* 0: log-mel output (D = n_mels); else D = n_mfcc <= n_mels */
+    int n_context;              /* C = 0 .. 16; F = D (2C + 1) <= 4096           */
+} asr_fbank_config;
+
+typedef struct asr_fbank asr_fbank_t;
+
+/* Host only.  Frames of an n_samples utterance (< 0: bad configuration) and
+ * the feature dimension F (0: bad configuration). */
+int asr_fbank_num_frames(const asr_fbank_config* cfg, int n_samples);
+int asr_fbank_feature_dim(const asr_fbank_config* cfg);
+/* Host only, no HIP call: the fp32 tables the device uses (any pointer may be
+ * NULL): h_window[win_length], h_mel[n_mels][n_fft/2 + 1], h_dct[D][n_mels]
+ * (n_mfcc > 0 only). */
+int asr_fbank_host_tables(const asr_fbank_config* cfg, float* h_window, float* h_mel, float* h_dct);
+/* Validates cfg before any HIP call, then uploads the tables (synchronous). */
+int asr_fbank_create(const asr_fbank_config* cfg, asr_fbank_t** out);
+int asr_fbank_destroy(asr_fbank_t* h);
+/* Bytes of d_work for asr_fbank_fwd: the base frames [B][T][D] when
+ * n_context > 0, 0 otherwise (and for a non-positive T or B). */
+size_t asr_fbank_workspace_bytes(const asr_fbank_t* h, int T, int B);
+/* d_wave batch-major [B][ldw], ldw >= S; d_nsamples device int32 [B] with
+ * values <= S (NULL: S for all); d_out time-major [T][B][ldo], ldo >= F,
+ * columns >= F of a row are not touched; T >= asr_fbank_num_frames(cfg, S):
+ * all T rows are written, zeros past an utterance's frames; d_frames device
+ * int32 [B] (may be NULL) receives frames_b and can be passed unchanged as
+ * d_lengths of asr_lstm_fwd.  One launch does a frame's whole chain on chip
+ * (one wave per frame: window, real FFT in LDS, power, sparse mel sums, log,
+ * DCT); with n_context > 0 it writes base frames to d_work and a second
+ * launch gathers the context rows.  Asynchronous on s, no allocation, no
+ * host sync: capturable as a linear chain.  An utterance's bits depend on
+ * the configuration only, never on B, its position in the batch, or T.
+ * ASR_ERR_ARG: a NULL required pointer, a non-positive size, ldw < S,
+ * ldo < F, T too small; ASR_ERR_UNSUPPORTED: a configuration outside the
+ * ranges above (asr_fbank_create), more than 2^25 output rows T*B in one
+ * call.  Both are decided before any HIP call. */
+int asr_fbank_fwd(asr_fbank_t* h, const float* d_wave, long ldw, const int32_t* d_nsamples, int B, int S,
+                  float* d_out, long ldo, int32_t* d_frames, void* d_work, int T, asr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
