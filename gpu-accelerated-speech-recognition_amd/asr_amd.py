@@ -11,6 +11,10 @@ include/asr_amd.h — it contains no arithmetic of its own:
     RNN_Cell(batch, in, hidden).forward                   RNN_Cell.cu:65
     RNN(batch, in, hidden, time_step, num_layers).forward RNN.cu:9
     DeviceMatrix ~ cuMatrix<float> (toGpu / toCpu)        cuMatrix.h:72-105
+    ctc_score(emis, targets) / ctc_align(emis, targets)
+                                          exact CTC log-likelihood and forced
+                                          alignment of given transcripts
+                                          (asr_ctc_align); no reference member
     LSTM(input_size, hidden_size, num_layers, bidirectional).forward
                                           torch.nn.LSTM; no reference member
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
@@ -63,7 +67,8 @@ EXPORTS = [
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
     "asr_ctc_set_timesteps", "asr_ctc_get_beams_ts", "asr_ctc_set_result_stream",
-    "asr_ctc_set_concurrency", "asr_rnn_set_recurrence", "asr_rnn_get_recurrence",
+    "asr_ctc_set_concurrency", "asr_ctc_align_workspace_bytes", "asr_ctc_align",
+    "asr_rnn_set_recurrence", "asr_rnn_get_recurrence",
     "asr_set_dense_arith", "asr_get_dense_arith",
     "asr_pipeline_create", "asr_pipeline_submit", "asr_pipeline_collect", "asr_pipeline_pending",
     "asr_pipeline_describe", "asr_pipeline_get_production", "asr_pipeline_get_streams", "asr_pipeline_get_queue_use",
@@ -180,6 +185,8 @@ def lib() -> ctypes.CDLL:
         "asr_ctc_set_timesteps": [_vp, _i],
         "asr_ctc_set_result_stream": [_vp, _vp],
         "asr_ctc_get_beams_ts": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+        "asr_ctc_align": [_vp, _i, _i, _i, ctypes.c_long, ctypes.c_long, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp,
+                          _i, _i, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -191,6 +198,8 @@ def lib() -> ctypes.CDLL:
     L.asr_lstm_workspace_bytes.restype = _sz
     L.asr_fbank_workspace_bytes.argtypes = [_vp, _i, _i]
     L.asr_fbank_workspace_bytes.restype = _sz
+    L.asr_ctc_align_workspace_bytes.argtypes = [_i, _i, _i]
+    L.asr_ctc_align_workspace_bytes.restype = _sz
     _lib = L
     return L
 
@@ -702,6 +711,7 @@ class CTCDecoder:
             check(lib().asr_ctc_set_waves(self.h, waves), "asr_ctc_set_waves")
         self._emis: Optional[DeviceBytes] = None
         self.T = self.B = 0
+        self._last = None
 
     def config(self) -> Tuple[int, int, int]:
         ms, w, lds = _i(), _i(), _i()
@@ -745,6 +755,7 @@ class CTCDecoder:
                                       _ptr(ln) if ln is not None else None, int(bool(is_log)), stream),
               "asr_ctc_decode_ex")
         self.T, self.B = T, B
+        self._last = (d_emis, fs, us, None if ln is None else ln.copy(), bool(is_log))   # for rescore()
 
     def decode_segment(self, d_emis: int, T: int, t0: int, t1: int, B: int, is_log: bool, stream: int = 0,
                        lengths: Optional[Sequence[int]] = None, frame_stride: Optional[int] = None,
@@ -762,6 +773,7 @@ class CTCDecoder:
                                            _ptr(ln) if ln is not None else None, int(bool(is_log)), stream),
               "asr_ctc_decode_segment")
         self.T, self.B = T, B
+        self._last = None   # rescore() needs the whole utterances behind one pointer
 
     def decode(self, emis: np.ndarray, is_log: bool = False, stream: int = 0,
                lengths: Optional[Sequence[int]] = None, batch_major: bool = False) -> None:
@@ -825,6 +837,31 @@ class CTCDecoder:
         return [[(lab[b, k, :ln[b, k]].tolist(), float(lp[b, k]), ts[b, k, :ln[b, k]].tolist())
                  for k in range(min(nh[b], max_hyps))] for b in range(B)]
 
+    def rescore(self, max_hyps: int, stream: int = 0) -> List[List[Tuple[List[int], float, float]]]:
+        """The final beam re-ranked by exact CTC log-likelihood: per utterance
+        [(labels, exact score, beam score)], exact score descending (equal
+        scores keep their beam order).  A beam score sums only the alignments
+        that survived pruning, a lower bound; the exact one is asr_ctc_align's
+        forward score of every hypothesis against its utterance, one call for
+        the whole batch.  After decode() / decode_device() of whole utterances
+        (the emissions must still be in place)."""
+        if self._last is None:
+            raise AsrError(ASR_ERR_STATE, "CTCDecoder.rescore: no whole-utterance decode yet")
+        d_emis, fs, us, ln, is_log = self._last
+        hyps = self.beams(max_hyps)
+        targets = [lab for u in hyps for lab, _ in u]
+        utt = [b for b, u in enumerate(hyps) for _ in u]
+        if not targets:
+            return [[] for _ in hyps]
+        exact = ctc_score(d_emis, targets, lengths=ln, utt=utt, is_log=is_log, blank=self.blank,
+                          shape=(self.T, self.B, self.V), frame_stride=fs, utt_stride=us, stream=stream)
+        out, k = [], 0
+        for u in hyps:
+            rows = [(lab, float(exact[k + j]), lp) for j, (lab, lp) in enumerate(u)]
+            k += len(u)
+            out.append(sorted(rows, key=lambda r: -r[1]))
+        return out
+
     def last_kernel_ms(self) -> float:
         ms = _f()
         check(lib().asr_ctc_last_kernel_ms(self.h, ctypes.byref(ms)), "asr_ctc_last_kernel_ms")
@@ -840,6 +877,125 @@ class CTCDecoder:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------- CTC alignment and scoring
+def ctc_align_workspace_bytes(T: int, N: int, max_target_len: int) -> int:
+    """Bytes of d_work for asr_ctc_align with a path or spans wanted (0: invalid shape)."""
+    return int(lib().asr_ctc_align_workspace_bytes(T, N, max_target_len))
+
+
+def ctc_align_device(d_emis: int, T: int, B: int, V: int, frame_stride: int, utt_stride: int, d_lengths: int,
+                     is_log: bool, blank: int, d_targets: int, ldt: int, d_target_lengths: int, d_utt: int,
+                     N: int, max_target_len: int, d_score: int = 0, d_vscore: int = 0, d_path: int = 0,
+                     ldp: int = 0, d_spans: int = 0, d_work: int = 0, stream: int = 0) -> None:
+    """asr_ctc_align over raw device pointers (0 = NULL); asynchronous on stream."""
+    check(lib().asr_ctc_align(d_emis, T, B, V, frame_stride, utt_stride, d_lengths or None, int(bool(is_log)),
+                              blank, d_targets, ldt, d_target_lengths, d_utt or None, N, max_target_len,
+                              d_score or None, d_vscore or None, d_path or None, ldp, d_spans or None,
+                              d_work or None, stream or None), "asr_ctc_align")
+
+
+def _upload(a: np.ndarray, stream: int = 0) -> DeviceBytes:
+    a = np.ascontiguousarray(a)
+    d = DeviceBytes(max(a.nbytes, 16))
+    check(lib().asr_memcpy_h2d(d.ptr, _ptr(a), a.nbytes, stream), "asr_memcpy_h2d")
+    return d
+
+
+def _download(d: DeviceBytes, shape, dtype, stream: int = 0) -> np.ndarray:
+    out = np.empty(shape, dtype)
+    check(lib().asr_memcpy_d2h(_ptr(out), d.ptr, out.nbytes, stream), "asr_memcpy_d2h")
+    return out
+
+
+def _ctc_align_call(emis, targets, lengths, utt, is_log, blank, batch_major, shape, frame_stride, utt_stride,
+                    stream, want_score, want_vscore, want_path):
+    """Shared body of ctc_score / ctc_align: upload, one asr_ctc_align, download."""
+    keep = []
+    if isinstance(emis, (int, np.integer)):
+        if shape is None:
+            raise ValueError("a device pointer needs shape=(T, B, V)")
+        T, B, V = (int(x) for x in shape)
+        d_emis = int(emis)
+        fs = (V if batch_major else B * V) if frame_stride is None else int(frame_stride)
+        us = (T * V if batch_major else V) if utt_stride is None else int(utt_stride)
+    else:
+        emis = np.ascontiguousarray(emis, dtype=np.float32)
+        if batch_major:
+            B, T, V = emis.shape
+            fs, us = V, T * V
+        else:
+            T, B, V = emis.shape
+            fs, us = B * V, V
+        keep.append(_upload(emis, stream))
+        d_emis = keep[-1].ptr
+    N = len(targets)
+    mtl = max([len(t) for t in targets] + [0])
+    ldt = max(mtl, 1)
+    tg = np.zeros((N, ldt), np.int32)
+    for n, t in enumerate(targets):
+        tg[n, :len(t)] = np.asarray(t, dtype=np.int32)
+    tl = np.array([len(t) for t in targets], np.int32)
+    d_tg, d_tl = _upload(tg, stream), _upload(tl, stream)
+    d_len = d_utt = None
+    if lengths is not None:
+        ln = np.ascontiguousarray(lengths, dtype=np.int32)
+        assert ln.shape == (B,), (ln.shape, B)
+        d_len = _upload(ln, stream)
+    if utt is not None:
+        ut = np.ascontiguousarray(utt, dtype=np.int32)
+        assert ut.shape == (N,), (ut.shape, N)
+        d_utt = _upload(ut, stream)
+    d_score = DeviceBytes(8 * N) if want_score else None
+    d_vscore = DeviceBytes(8 * N) if want_vscore else None
+    d_path = d_spans = d_work = None
+    if want_path:
+        d_path = DeviceBytes(4 * N * T)
+        d_spans = DeviceBytes(8 * N * ldt)
+        d_work = DeviceBytes(max(ctc_align_workspace_bytes(T, N, mtl), 16))
+    ctc_align_device(d_emis, T, B, V, fs, us, d_len.ptr if d_len else 0, is_log, blank, d_tg.ptr, ldt, d_tl.ptr,
+                     d_utt.ptr if d_utt else 0, N, mtl, d_score.ptr if d_score else 0,
+                     d_vscore.ptr if d_vscore else 0, d_path.ptr if d_path else 0, T,
+                     d_spans.ptr if d_spans else 0, d_work.ptr if d_work else 0, stream)
+    score = _download(d_score, N, np.float64, stream) if want_score else None
+    vscore = _download(d_vscore, N, np.float64, stream) if want_vscore else None
+    paths = spans = None
+    if want_path:
+        pa = _download(d_path, (N, T), np.int32, stream)
+        sp = _download(d_spans, (N, ldt, 2), np.int32, stream)
+        # frames past the utterance's length are -1; so is every frame of an infeasible target
+        paths =[pa[n, :int((pa[n] >= 0).sum())].copy() for n in range(N)]
+        spans = [sp[n, :len(targets[n])].copy() for n in range(N)]
+    return score, vscore, paths, spans
+
+
+def ctc_score(emis, targets: Sequence[Sequence[int]], lengths: Optional[Sequence[int]] = None,
+              utt: Optional[Sequence[int]] = None, is_log: bool = False, blank: int = 0,
+              batch_major: bool = False, shape: Optional[Tuple[int, int, int]] = None,
+              frame_stride: Optional[int] = None, utt_stride: Optional[int] = None, stream: int = 0) -> np.ndarray:
+    """Exact CTC forward log-likelihood log p(target | emissions) of every
+    target, fp64 [N] (-inf: infeasible).  emis: numpy [T][B][V] ([B][T][V] with
+    batch_major), or a device pointer with shape=(T, B, V).  targets: a list of
+    label lists; target n is scored against utterance utt[n] (default n).
+    lengths[b]: frames of utterance b (default T)."""
+    return _ctc_align_call(emis, targets, lengths, utt, is_log, blank, batch_major, shape, frame_stride,
+                           utt_stride, stream, True, False, False)[0]
+
+
+def ctc_align(emis, targets: Sequence[Sequence[int]], lengths: Optional[Sequence[int]] = None,
+              utt: Optional[Sequence[int]] = None, is_log: bool = False, blank: int = 0,
+              batch_major: bool = False, shape: Optional[Tuple[int, int, int]] = None,
+              frame_stride: Optional[int] = None, utt_stride: Optional[int] = None,
+              stream: int = 0) -> Tuple[np.ndarray, List[np.ndarray], List[np.ndarray]]:
+    """Viterbi forced alignment (torchaudio.functional.forced_align semantics):
+    (vscore fp64 [N], paths, spans).  paths[n]: the label emitted at each of the
+    utterance's frames, blank included (empty when the target is infeasible);
+    spans[n]: int32 [L_n, 2], first frame and one past the last frame of each
+    target label ((-1, -1) when infeasible).  Arguments as ctc_score."""
+    _, vscore, paths, spans = _ctc_align_call(emis, targets, lengths, utt, is_log, blank, batch_major, shape,
+                                              frame_stride, utt_stride, stream, False, True, True)
+    return vscore, paths, spans
 
 
 class PipelineConfig(ctypes.Structure):

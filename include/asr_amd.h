@@ -388,6 +388,64 @@ int asr_ctc_set_waves(asr_ctc_t* h, int waves);
 int asr_ctc_set_concurrency(asr_ctc_t* h, int n);
 int asr_ctc_get_config(asr_ctc_t* h, int* max_states, int* waves, int* lds_bytes);
 
+/* ---- CTC forced alignment and exact transcript scoring ---------------------
+ * No reference member is replaced (the reference only searches): the dynamic
+ * programme over the CTC lattice of a GIVEN transcript, in fp64 log domain
+ * with the decoder's lse.  The extended target ext has S = 2L+1 states
+ * (ext[2i] = blank, ext[2i+1] = target[i]); with lp(t, c) the log-probability
+ * of label c at frame t and skip(s) = ext[s] != blank && ext[s] != ext[s-2],
+ *   frame 0:  a[0] = lp(0, blank), a[1] = lp(0, ext[1]), every other state -inf
+ *   forward:  a_t[s] = lse(lse(a[s], a[s-1]), a[s-2] if skip(s)) + lp(t, ext[s])
+ *             score = lse(a[S-1], a[S-2]) after the last frame (a[0] for L = 0):
+ *             log p(target | emissions), the CTC loss negated
+ *   Viterbi:  the same with max for lse (torchaudio.functional.forced_align);
+ *             ties take the smallest jump (stay, then s-1, then s-2), and the
+ *             final state is S-1 unless v[S-2] > v[S-1] strictly.
+ * Emissions as in asr_ctc_decode_ex: element (t, b, v) at d_emis[t*frame_stride
+ * + b*utt_stride + v], probabilities (lp = log((double)p), p = 0 gives -inf) or
+ * log-probabilities if is_log.  d_lengths: device int32 [B] frames per
+ * utterance, clamped to [0, T], NULL = T (the convention of asr_lstm_fwd and
+ * asr_fbank_fwd: d_frames passes straight through).  d_targets [N][ldt] label
+ * ids, ldt >= max_target_len; d_target_lengths [N], clamped to
+ * [0, max_target_len]; d_utt [N]: the utterance target n is scored against,
+ * NULL = utterance n (then N <= B); an n-best list is N = B*K targets with
+ * d_utt[n] = n / K.
+ * Outputs, each may be NULL, at least one given:
+ *   d_score [N]   forward log-likelihood;
+ *   d_vscore [N]  log-probability of the best alignment;
+ *   d_path [N][ldp], ldp >= T: the label emitted at each frame, blank
+ *     included; frames t >= the utterance's length are -1, columns >= T are
+ *     not touched;
+ *   d_spans [N][ldt][2]: first frame and one past the last frame of target
+ *     label i; entries L_n <= i < max_target_len are (-1, -1), entries
+ *     >= max_target_len are not touched.
+ * Infeasible target (fewer frames than L + adjacent repeats, every alignment
+ * of probability 0, a label that is the blank or outside [0, V), d_utt[n]
+ * outside [0, B)): scores -inf, path -1 over the utterance's frames, spans
+ * (-1, -1); never an out-of-range read.  No frames: score 0.0 for L = 0, else
+ * infeasible.
+ * d_work: asr_ctc_align_workspace_bytes(T, N, max_target_len) bytes (a
+ * multiple of 16, 0 for an invalid shape, at most N*T*256 bytes, N*T*64 for
+ * max_target_len <= 127), needed only when a path or spans are wanted: the
+ * Viterbi choices, 2 bits per state and frame.
+ * One launch, one wave per target, the lattice column in registers (lane l
+ * owns 1, 2, 4, 8 or 16 contiguous states by max_target_len); the traceback is
+ * the tail of the same kernel.  Asynchronous on s, no allocation, no host
+ * sync.  A target's results depend only on its own emissions, labels and
+ * frame count: never on N, its position, max_target_len, T, or which outputs
+ * were asked for.
+ * ASR_ERR_ARG: a NULL d_emis / d_targets / d_target_lengths, a non-positive
+ * T, B, V or N, blank outside [0, V), ldt < max_target_len, ldp < T with a
+ * path wanted, no output, NULL d_work with a path or spans wanted, NULL d_utt
+ * with N > B; ASR_ERR_UNSUPPORTED: max_target_len > 511 or < 0, V > 4096.
+ * Both are decided before any HIP call. */
+size_t asr_ctc_align_workspace_bytes(int T, int N, int max_target_len);
+int asr_ctc_align(const float* d_emis, int T, int B, int V, long frame_stride, long utt_stride,
+                  const int32_t* d_lengths, int is_log, int blank, const int32_t* d_targets, long ldt,
+                  const int32_t* d_target_lengths, const int32_t* d_utt, int N, int max_target_len,
+                  double* d_score, double* d_vscore, int32_t* d_path, long ldp, int32_t* d_spans,
+                  void* d_work, asr_stream_t s);
+
 /* ---- throughput pipeline (no reference counterpart: the reference runs one
  *      batch at a time with host syncs between calls, main.cpp:40-72,
  *      RNN.cu:9-30, CTCBeamSearch.cu:262-312) ---------------------------------

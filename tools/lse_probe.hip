@@ -1,4 +1,4 @@
-// Probe: accuracy of the decoder's fp64 lse (csrc/ctc_beam_kernel.inc: lse2 =
+// Probe: accuracy of the decoder's fp64 lse (csrc/ctc_lse.h: lse2 =
 // max + lse_log1p01(lse_exp_neg(-|a - b|))) against a long-double reference
 // and against glibc's double log1p(exp(.)), over random pairs whose gap
 // covers the folds' range (0 .. 40 nats, and a tail to 745).
