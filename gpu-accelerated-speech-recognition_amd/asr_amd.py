@@ -17,6 +17,8 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           (asr_ctc_align); no reference member
     LSTM(input_size, hidden_size, num_layers, bidirectional).forward
                                           torch.nn.LSTM; no reference member
+    GRU(input_size, hidden_size, num_layers, bidirectional).forward
+                                          torch.nn.GRU; no reference member
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
                                           waveform -> log-mel / MFCC features
                                           (asr_fbank_*); no reference member
@@ -61,6 +63,7 @@ EXPORTS = [
     "asr_matmul", "asr_matmul_ta", "asr_matmul_tb", "asr_matadd", "asr_linear_fwd",
     "asr_rnn_cell_fwd", "asr_rnn_fwd", "asr_rnn_recur_fwd", "asr_rnn_persist_stats", "asr_rnn_emit_fwd", "asr_rnn_bidir_workspace_bytes", "asr_rnn_bidir_fwd",
     "asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd",
+    "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
@@ -164,6 +167,9 @@ def lib() -> ctypes.CDLL:
                          _i, _i, _i, _i, _i, _vp],
         "asr_lstm_recur_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp,
                                _i, _i, _i, _i, _vp],
+        "asr_gru_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp,
+                        _i, _i, _i, _i, _i, _vp],
+        "asr_gru_recur_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _i, _vp],
         "asr_fbank_num_frames": [_vp, _i],
         "asr_fbank_feature_dim": [_vp],
         "asr_fbank_host_tables": [_vp, _vp, _vp, _vp],
@@ -196,6 +202,8 @@ def lib() -> ctypes.CDLL:
     L.asr_rnn_bidir_workspace_bytes.restype = _sz
     L.asr_lstm_workspace_bytes.argtypes = [_i, _i, _i]
     L.asr_lstm_workspace_bytes.restype = _sz
+    L.asr_gru_workspace_bytes.argtypes = [_i, _i, _i]
+    L.asr_gru_workspace_bytes.restype = _sz
     L.asr_fbank_workspace_bytes.argtypes = [_vp, _i, _i]
     L.asr_fbank_workspace_bytes.restype = _sz
     L.asr_ctc_align_workspace_bytes.argtypes = [_i, _i, _i]
@@ -578,6 +586,125 @@ class LSTM:
                 lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, self.outputs[l], T, B, self._work,
                          hT=_DeviceView(self.h_n, k, B), cT=_DeviceView(self.c_n, k, B), lengths=ln,
                          reverse=d == 1, col=d * H, stream=st)
+            x = self.outputs[l]
+        if ln is not None:   # the kernels read it: keep it until they are done
+            check(lib().asr_stream_sync(ctypes.c_void_p(st or None)), "asr_stream_sync")
+        return self.outputs[-1]
+
+
+# ----------------------------------------------------------------------- GRU
+def gru_workspace_bytes(T: int, B: int, H: int) -> int:
+    """asr_gru_workspace_bytes: 0 for a shape the GRU kernels do not take."""
+    return int(lib().asr_gru_workspace_bytes(T, B, H))
+
+
+def _gru_tail(hid: DeviceMatrix, col: int, H: int, hT, lengths, T: int, B: int):
+    """Arguments shared by gru_fwd / gru_recur_fwd: the output pointer of the
+    direction that writes columns [col, col + H) of hid's rows, and the rest."""
+    assert hid.rows == T * B and 0 <= col and col + H <= hid.cols, (hid.rows, hid.cols, col, H)
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    return hid.ptr + 4 * col, hid.cols, opt(hT), opt(lengths)
+
+
+def gru_fwd(x: DeviceMatrix, W_ih: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh: DeviceMatrix,
+            hid: DeviceMatrix, T: int, B: int, work: DeviceBytes, h0: Optional[DeviceMatrix] = None,
+            hT: Optional[DeviceMatrix] = None, lengths: Optional[DeviceBytes] = None, reverse: bool = False,
+            col: int = 0, stream: int = 0) -> DeviceMatrix:
+    """One GRU layer and direction (asr_gru_fwd): W_ih [in, 3H], W_hh [H, 3H]
+    (gates r, z, n), h_t into columns [col, col + H) of hid [T*B, >= H] (the
+    row stride is hid.cols); lengths from device_lengths()."""
+    inp, H = W_ih.rows, W_hh.rows
+    assert x.rows == T * B and x.cols == inp and W_ih.cols == 3 * H and W_hh.cols == 3 * H
+    need = gru_workspace_bytes(T, B, H)
+    if need and (work is None or work.nbytes < need):
+        raise ValueError(f"GRU workspace of {need} bytes needed (asr_gru_workspace_bytes)")
+    out, ldh, pht, pln = _gru_tail(hid, col, H, hT, lengths, T, B)
+    check(lib().asr_gru_fwd(x.ptr, h0.ptr if h0 else None, W_ih.ptr, W_hh.ptr, b_ih.ptr, b_hh.ptr, out, ldh, pht,
+                            pln, work.ptr if work is not None else None, T, B, inp, H, int(bool(reverse)), stream),
+          "asr_gru_fwd")
+    return hid
+
+
+def gru_recur_fwd(P: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh: DeviceMatrix, hid: DeviceMatrix,
+                  T: int, B: int, h0: Optional[DeviceMatrix] = None, hT: Optional[DeviceMatrix] = None,
+                  lengths: Optional[DeviceBytes] = None, reverse: bool = False, col: int = 0,
+                  stream: int = 0) -> DeviceMatrix:
+    """The recurrence stage alone (asr_gru_recur_fwd): P [T*B, 3H] holds x.W_ih
+    (read only); no workspace."""
+    H = W_hh.rows
+    assert P.rows == T * B and P.cols == 3 * H and W_hh.cols == 3 * H
+    out, ldh, pht, pln = _gru_tail(hid, col, H, hT, lengths, T, B)
+    check(lib().asr_gru_recur_fwd(P.ptr, h0.ptr if h0 else None, W_hh.ptr, b_ih.ptr, b_hh.ptr, out, ldh, pht, pln,
+                                  T, B, H, int(bool(reverse)), stream), "asr_gru_recur_fwd")
+    return hid
+
+
+class GRU:
+    """torch.nn.GRU(input_size, hidden_size, num_layers, bidirectional=...) for
+    inference on asr_gru_fwd: device weights and one workspace, no arithmetic
+    here.  params[layer][direction] = (W_ih [in, 3H], W_hh [H, 3H], b_ih [3H],
+    b_hh [3H]) in this library's [in][out] layout (zeros if None); from_torch
+    takes them from a torch module.  No dropout."""
+
+    def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, bidirectional: bool = False,
+                 params: Optional[Sequence[Sequence[Tuple[np.ndarray, ...]]]] = None):
+        self.inp, self.H, self.L, self.D = input_size, hidden_size, num_layers, 2 if bidirectional else 1
+        H = hidden_size
+        self.layers = []
+        for l in range(num_layers):
+            i = input_size if l == 0 else self.D * H
+            shapes = ((i, 3 * H), (H, 3 * H), (3 * H, 1), (3 * H, 1))
+            dirs = []
+            for d in range(self.D):
+                p = [np.zeros(s, np.float32) for s in shapes] if params is None else params[l][d]
+                dirs.append(tuple(DeviceMatrix.from_numpy(np.asarray(a, np.float32).reshape(s))
+                                  for a, s in zip(p, shapes)))
+            self.layers.append(dirs)
+        self._work: Optional[DeviceBytes] = None
+        self._shape = None
+        self.outputs: List[DeviceMatrix] = []
+        self.h_n: Optional[DeviceMatrix] = None   # [L*D*B, H] as torch's h_n [L*D, B, H]
+
+    @classmethod
+    def from_torch(cls, module) -> "GRU":
+        """The weight_*_l{k}[_reverse] tensors of a torch.nn.GRU, transposed to
+        [in][out], and its biases."""
+        if not module.bias:
+            raise ValueError("GRU.from_torch: bias=False is not supported")
+        params = []
+        for l in range(module.num_layers):
+            dirs = []
+            for sfx in ("", "_reverse")[:2 if module.bidirectional else 1]:
+                get = lambda n: getattr(module, f"{n}_l{l}{sfx}").detach().cpu().float().numpy()   # noqa: E731
+                dirs.append((np.ascontiguousarray(get("weight_ih").T), np.ascontiguousarray(get("weight_hh").T),
+                             get("bias_ih"), get("bias_hh")))
+            params.append(dirs)
+        return cls(module.input_size, module.hidden_size, module.num_layers, module.bidirectional, params)
+
+    def forward(self, x: DeviceMatrix, T: int, B: int, lengths: Optional[Sequence[int]] = None,
+                h0: Optional[DeviceMatrix] = None, stream: Optional[int] = None) -> DeviceMatrix:
+        """x time-major [T*B, input_size]; h0 [L*D*B, H] in h_n's order (None =
+        zeros); returns the last layer's [T*B, H or 2H] (zeros past each
+        utterance's length); h_n holds the final states.  The two directions
+        of a layer write the two halves of one buffer."""
+        H, D, st = self.H, self.D, stream or 0
+        if self._shape != (T, B):
+            need = gru_workspace_bytes(T, B, H)
+            if not need:
+                raise AsrError(ASR_ERR_UNSUPPORTED, "asr_gru_workspace_bytes")
+            if self._work is None or self._work.nbytes < need:
+                self._work = DeviceBytes(need)
+            self.outputs = [DeviceMatrix(T * B, D * H) for _ in range(self.L)]
+            self.h_n = DeviceMatrix(self.L * D * B, H)
+            self._shape = (T, B)
+        assert h0 is None or (h0.rows == self.L * D * B and h0.cols == H), (h0.rows, h0.cols)
+        ln = None if lengths is None else device_lengths(lengths)
+        for l, dirs in enumerate(self.layers):
+            for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(dirs):
+                k = (l * D + d) * B
+                gru_fwd(x, w_ih, w_hh, b_ih, b_hh, self.outputs[l], T, B, self._work,
+                        h0=None if h0 is None else _DeviceView(h0, k, B), hT=_DeviceView(self.h_n, k, B),
+                        lengths=ln, reverse=d == 1, col=d * H, stream=st)
             x = self.outputs[l]
         if ln is not None:   # the kernels read it: keep it until they are done
             check(lib().asr_stream_sync(ctypes.c_void_p(st or None)), "asr_stream_sync")

@@ -238,7 +238,7 @@ int asr_rnn_bidir_fwd(const float* d_x, const float* d_h0, const float* const d_
  * bits do not depend on its batch.
  * ASR_ERR_ARG: a NULL required pointer, a non-positive size, ldh < H;
  * ASR_ERR_UNSUPPORTED: H % 16 != 0, H > 2048, B*4H*4 bytes beyond one buffer
- * resource (0x7ff00000).  No projection (proj_size), dropout or GRU. */
+ * resource (0x7ff00000).  No projection (proj_size) or dropout. */
 size_t asr_lstm_workspace_bytes(int T, int B, int H);
 int asr_lstm_fwd(const float* d_x, const float* d_h0, const float* d_c0, const float* d_W_ih,
                  const float* d_W_hh, const float* d_b_ih, const float* d_b_hh, float* d_hiddens,
@@ -255,6 +255,53 @@ int asr_lstm_recur_fwd(const float* d_P, const float* d_h0, const float* d_c0, c
                        const float* d_b_ih, const float* d_b_hh, float* d_hiddens, long ldh,
                        float* d_hT, float* d_cT, const int32_t* d_lengths, void* d_work, int T,
                        int B, int H, int reverse, asr_stream_t s);
+
+/* One GRU layer and direction over a whole sequence — torch.nn.GRU semantics
+ * (gate order r, z, n), the recurrent layer of DeepSpeech2-style and small
+ * streaming CTC acoustic models; no reference member.  x time-major
+ * [T*B, in]; W_ih [in, 3H], W_hh [H, 3H] in this library's [in][out] layout,
+ * gate q of hidden unit j at column q*H + j; b_ih, b_hh [3H].  With
+ * P = x_t.W_ih and a = h_{t-1}.W_hh, in this operation order:
+ *   r   = sigmoid((P_r + a_r) + (b_ir + b_hr))
+ *   z   = sigmoid((P_z + a_z) + (b_iz + b_hz))
+ *   n   = tanh((P_n + b_in) + r * (a_n + b_hn))
+ *   h_t = n + z * (h_{t-1} - n)            (= (1 - z) n + z h_{t-1})
+ * (the reset gate multiplies the hidden contribution of the candidate only,
+ * b_hn included).  Everything else is asr_lstm_fwd's contract without the cell
+ * state: d_h0 [B,H] (NULL = zeros); d_hiddens receives h_t at row t*B + b with
+ * row stride ldh >= H floats (columns outside [0, H) of a row are not
+ * touched, so ldh = 2H lets two calls fill the halves of one [T*B, 2H]
+ * buffer); reverse != 0 runs the frames T-1 .. 0; d_lengths (device int32
+ * [B], clamped to [0, T], NULL = all T): for frames t >= d_lengths[b]
+ * utterance b's h is carried unchanged and its output row is zeros, in
+ * reverse the utterance starts from h0 at its own last frame; d_hT [B,H]
+ * (NULL = not wanted) receives the state after each utterance's last valid
+ * frame, h0 for length 0 — pass it as the next call's d_h0 to stream.
+ * d_work: asr_gru_workspace_bytes(T,B,H) bytes, 16-B aligned: the input
+ * projection P [T*B, 3H] for all T, one GEMM that follows asr_set_dense_arith
+ * like asr_linear_fwd; the size is 0 for an invalid shape.
+ * The recurrence contracts on fp32 MFMA.  16 <= H <= 128: one launch with
+ * W_hh resident in registers, 16 utterances per workgroup; 128 < H <= 2048:
+ * one launch per frame (capturable in a graph; needs ldh % 4 == 0 and 16-B
+ * aligned d_hiddens / d_h0).  The kernel depends on H only, so an utterance's
+ * bits do not depend on its batch.  Asynchronous on s, no allocation.
+ * ASR_ERR_ARG: a NULL required pointer, a non-positive size, ldh < H;
+ * ASR_ERR_UNSUPPORTED: H % 16 != 0, H > 2048, B*3H*4 bytes beyond one buffer
+ * resource (0x7ff00000), T*B > INT_MAX, the step form's alignment rules.
+ * No projection, dropout or torch's legacy GRU variants. */
+size_t asr_gru_workspace_bytes(int T, int B, int H);
+int asr_gru_fwd(const float* d_x, const float* d_h0, const float* d_W_ih, const float* d_W_hh,
+                const float* d_b_ih, const float* d_b_hh, float* d_hiddens, long ldh, float* d_hT,
+                const int32_t* d_lengths, void* d_work, int T, int B, int in, int H, int reverse,
+                asr_stream_t s);
+
+/* The recurrence stage of asr_gru_fwd alone: d_P [T*B, 3H] holds x.W_ih
+ * (asr_linear_fwd(x, W_ih, NULL, P, T*B, in, 3H, ASR_EPI_NONE)) and is read
+ * only.  asr_gru_fwd is exactly that GEMM into d_work followed by this call,
+ * bit for bit.  It takes no workspace: a GRU has no cell state. */
+int asr_gru_recur_fwd(const float* d_P, const float* d_h0, const float* d_W_hh, const float* d_b_ih,
+                      const float* d_b_hh, float* d_hiddens, long ldh, float* d_hT,
+                      const int32_t* d_lengths, int T, int B, int H, int reverse, asr_stream_t s);
 
 /* ---- CTC prefix beam search: replaces CTCBeamSearch (CTCBeamSearch.h:107-150,
  *      CTCBeamSearch.cu:220-312) with the semantics of the CPU decoder
