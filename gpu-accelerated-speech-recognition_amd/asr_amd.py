@@ -22,6 +22,9 @@ include/asr_amd.h — it contains no arithmetic of its own:
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
                                           waveform -> log-mel / MFCC features
                                           (asr_fbank_*); no reference member
+    NGramLM.from_arpa(path).score(token_lists) / CTCDecoder.lm_rescore(...)
+                                          back-off n-gram LM scoring and n-best
+                                          rescoring (asr_lm_*); no reference member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -30,6 +33,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import os
 from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
@@ -66,6 +70,8 @@ EXPORTS = [
     "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
+    "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
+    "asr_lm_token_string", "asr_lm_score_host", "asr_lm_upload", "asr_lm_score",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -176,6 +182,15 @@ def lib() -> ctypes.CDLL:
         "asr_fbank_create": [_vp, ctypes.POINTER(_vp)],
         "asr_fbank_destroy": [_vp],
         "asr_fbank_fwd": [_vp, _vp, ctypes.c_long, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp, _i, _vp],
+        "asr_lm_create_arpa": [ctypes.c_char_p, _f, ctypes.POINTER(_vp)],
+        "asr_lm_create_arpa_mem": [ctypes.c_char_p, _sz, _f, ctypes.POINTER(_vp)],
+        "asr_lm_destroy": [_vp],
+        "asr_lm_get_info": [_vp, _vp],
+        "asr_lm_token_id": [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32)],
+        "asr_lm_token_string": [_vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p)],
+        "asr_lm_score_host": [_vp, _vp, ctypes.c_long, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_long],
+        "asr_lm_upload": [_vp],
+        "asr_lm_score": [_vp, _vp, ctypes.c_long, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_long, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -989,6 +1004,37 @@ class CTCDecoder:
             out.append(sorted(rows, key=lambda r: -r[1]))
         return out
 
+    def lm_rescore(self, max_hyps: int, lm: "NGramLM", alpha: float, beta: float, mapper, bos: bool = True,
+                   eos: bool = True, stream: int = 0) -> List[List[Tuple[List[int], float, float, float, int]]]:
+        """The final beam re-ranked with a language model: per utterance
+        [(labels, total, exact_ctc, lm_log10, n_tokens)], total descending (equal
+        totals keep their beam order), with ctcdecode's combination
+            total = exact_ctc + alpha * ln(10) * lm_log10 + beta * n_tokens.
+        exact_ctc is rescore()'s exact score (natural log); mapper turns a label
+        list into LM token ids (NGramLM.label_mapper); lm_log10 is the LM's
+        log10 probability of those tokens (one asr_lm_score launch for the whole
+        batch; lm.upload() first) and n_tokens the tokens scored without </s>.
+        After decode() / decode_device() of whole utterances, as rescore()."""
+        if self._last is None:
+            raise AsrError(ASR_ERR_STATE, "CTCDecoder.lm_rescore: no whole-utterance decode yet")
+        d_emis, fs, us, ln, is_log = self._last
+        hyps = self.beams(max_hyps)
+        targets = [lab for u in hyps for lab, _ in u]
+        utt = [b for b, u in enumerate(hyps) for _ in u]
+        if not targets:
+            return [[] for _ in hyps]
+        exact = ctc_score(d_emis, targets, lengths=ln, utt=utt, is_log=is_log, blank=self.blank,
+                          shape=(self.T, self.B, self.V), frame_stride=fs, utt_stride=us, stream=stream)
+        lm_log10, counts = lm.score([mapper(lab) for lab in targets], bos=bos, eos=eos, stream=stream)
+        n_tok = np.asarray(counts)[:, 0] - (1 if eos else 0)
+        out, k = [], 0
+        for u in hyps:
+            rows = [(lab, lm_total(float(exact[k + j]), float(lm_log10[k + j]), int(n_tok[k + j]), alpha, beta),
+                     float(exact[k + j]), float(lm_log10[k + j]), int(n_tok[k + j])) for j, (lab, _) in enumerate(u)]
+            k += len(u)
+            out.append(sorted(rows, key=lambda r: -r[1]))
+        return out
+
     def last_kernel_ms(self) -> float:
         ms = _f()
         check(lib().asr_ctc_last_kernel_ms(self.h, ctypes.byref(ms)), "asr_ctc_last_kernel_ms")
@@ -1123,6 +1169,152 @@ def ctc_align(emis, targets: Sequence[Sequence[int]], lengths: Optional[Sequence
     _, vscore, paths, spans = _ctc_align_call(emis, targets, lengths, utt, is_log, blank, batch_major, shape,
                                               frame_stride, utt_stride, stream, False, True, True)
     return vscore, paths, spans
+
+
+# ------------------------------------------------------- n-gram language model
+ASR_LM_MAX_ORDER = 8
+ASR_LM_BOS, ASR_LM_EOS = 1, 2
+LN10 = math.log(10.0)
+
+
+class LmInfo(ctypes.Structure):
+    """asr_lm_info (include/asr_amd.h)."""
+    _fields_ = [("order", ctypes.c_int32), ("vocab", ctypes.c_int32), ("bos_id", ctypes.c_int32),
+                ("eos_id", ctypes.c_int32), ("unk_id", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("ngrams", ctypes.c_int64 * ASR_LM_MAX_ORDER), ("nodes_inserted", ctypes.c_int64),
+                ("table_bytes", ctypes.c_int64)]
+
+
+def lm_total(exact_ctc: float, lm_log10: float, n_tokens: int, alpha: float, beta: float) -> float:
+    """ctcdecode's combination of an acoustic score (natural log), an LM score
+    (log10) and a word bonus."""
+    return exact_ctc + alpha * LN10 * lm_log10 + beta * n_tokens
+
+
+class NGramLM:
+    """Back-off n-gram language model (asr_lm_*; the semantics are in
+    include/asr_amd.h): an ARPA file parsed into an exact table on the host,
+    scored on the host (host=True) or, after upload(), on the device, one wave
+    per hypothesis.  No arithmetic here."""
+
+    def __init__(self, handle: int):
+        self.h = handle
+        info = LmInfo()
+        check(lib().asr_lm_get_info(self.h, ctypes.byref(info)), "asr_lm_get_info")
+        self.order, self.vocab_size = int(info.order), int(info.vocab)
+        self.bos_id, self.eos_id, self.unk_id = int(info.bos_id), int(info.eos_id), int(info.unk_id)
+
+    @classmethod
+    def from_arpa(cls, path, oov_log10: float = -100.0) -> "NGramLM":
+        h = _vp()
+        check(lib().asr_lm_create_arpa(os.fsencode(path), oov_log10, ctypes.byref(h)), "asr_lm_create_arpa")
+        return cls(h.value)
+
+    @classmethod
+    def from_string(cls, text, oov_log10: float = -100.0) -> "NGramLM":
+        data = text.encode() if isinstance(text, str) else bytes(text)
+        h = _vp()
+        check(lib().asr_lm_create_arpa_mem(data, len(data), oov_log10, ctypes.byref(h)), "asr_lm_create_arpa_mem")
+        return cls(h.value)
+
+    def info(self) -> dict:
+        info = LmInfo()
+        check(lib().asr_lm_get_info(self.h, ctypes.byref(info)), "asr_lm_get_info")
+        return {"order": int(info.order), "vocab": int(info.vocab), "bos_id": int(info.bos_id),
+                "eos_id": int(info.eos_id), "unk_id": int(info.unk_id),
+                "ngrams": [int(info.ngrams[k]) for k in range(int(info.order))],
+                "nodes_inserted": int(info.nodes_inserted), "table_bytes": int(info.table_bytes)}
+
+    def token_id(self, token: str) -> int:
+        """The token's id, -1 when the model does not have it."""
+        i = ctypes.c_int32(-1)
+        check(lib().asr_lm_token_id(self.h, token.encode(), ctypes.byref(i)), "asr_lm_token_id")
+        return int(i.value)
+
+    def token_string(self, token_id: int) -> str:
+        s = ctypes.c_char_p()
+        check(lib().asr_lm_token_string(self.h, int(token_id), ctypes.byref(s)), "asr_lm_token_string")
+        return s.value.decode()
+
+    def upload(self) -> None:
+        """Copy the tables to the current device (synchronous; once)."""
+        check(lib().asr_lm_upload(self.h), "asr_lm_upload")
+
+    def score(self, token_lists: Sequence[Sequence[int]], bos: bool = True, eos: bool = True, detail: bool = False,
+              host: bool = False, stream: int = 0):
+        """(log10 probability [N] float64, counts [N, 2] int32: tokens scored with
+        </s>, OOVs); with detail also the per-token log10 values and matched
+        orders as lists of arrays (the </s> entry last).  host=True runs
+        asr_lm_score_host; otherwise one asr_lm_score launch on stream."""
+        N = len(token_lists)
+        flags = (ASR_LM_BOS if bos else 0) | (ASR_LM_EOS if eos else 0)
+        if N == 0:
+            empty = (np.zeros(0, np.float64), np.zeros((0, 2), np.int32))
+            return empty + ([], []) if detail else empty
+        max_len = max(len(t) for t in token_lists)
+        ldt, ldd = max(max_len, 1), max_len + 1
+        tok = np.zeros((N, ldt), np.int32)
+        for n, t in enumerate(token_lists):
+            tok[n, :len(t)] = np.asarray(t, dtype=np.int32)
+        ln = np.array([len(t) for t in token_lists], np.int32)
+        if host:
+            logp, counts = np.zeros(N, np.float64), np.zeros((N, 2), np.int32)
+            tl = np.zeros((N, ldd), np.float64) if detail else None
+            to = np.zeros((N, ldd), np.int32) if detail else None
+            check(lib().asr_lm_score_host(self.h, _ptr(tok), ldt, _ptr(ln), N, max_len, flags, _ptr(logp),
+                                          _ptr(counts), _ptr(tl) if detail else None,
+                                          _ptr(to) if detail else None, ldd), "asr_lm_score_host")
+        else:
+            d_tok, d_ln = _upload(tok, stream), _upload(ln, stream)
+            d_logp, d_counts = DeviceBytes(8 * N), DeviceBytes(8 * N)
+            d_tl = DeviceBytes(8 * N * ldd) if detail else None
+            d_to = DeviceBytes(4 * N * ldd) if detail else None
+            check(lib().asr_lm_score(self.h, d_tok.ptr, ldt, d_ln.ptr, N, max_len, flags, d_logp.ptr, d_counts.ptr,
+                                     d_tl.ptr if detail else None, d_to.ptr if detail else None, ldd,
+                                     stream or None), "asr_lm_score")
+            logp = _download(d_logp, N, np.float64, stream)
+            counts = _download(d_counts, (N, 2), np.int32, stream)
+            tl = _download(d_tl, (N, ldd), np.float64, stream) if detail else None
+            to = _download(d_to, (N, ldd), np.int32, stream) if detail else None
+        if not detail:
+            return logp, counts
+        return (logp, counts, [tl[n, :counts[n, 0]].copy() for n in range(N)],
+                [to[n, :counts[n, 0]].copy() for n in range(N)])
+
+    def label_mapper(self, labels: Sequence[str], mode: str = "char", space: str = " "):
+        """A function from a hypothesis (label ids) to this model's token ids, on
+        the host.  labels[i] is label i's string.  "char": every label's string
+        is looked up as a token, labels with an empty string (the blank) are
+        dropped; "word": the label strings are joined, split at `space`, and
+        every non-empty word is looked up.  An unknown token maps to -1 (OOV)."""
+        if mode not in ("char", "word"):
+            raise ValueError(f"label_mapper: mode {mode!r}")
+        labels = list(labels)
+        cache: dict = {}
+
+        def lookup(s: str) -> int:
+            if s not in cache:
+                cache[s] = self.token_id(s)
+            return cache[s]
+
+        if mode == "char":
+            def mapper(hyp):
+                return [lookup(labels[c]) for c in hyp if labels[c] != ""]
+        else:
+            def mapper(hyp):
+                return [lookup(w) for w in "".join(labels[c] for c in hyp).split(space) if w != ""]
+        return mapper
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib().asr_lm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class PipelineConfig(ctypes.Structure):

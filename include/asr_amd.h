@@ -718,6 +718,113 @@ size_t asr_fbank_workspace_bytes(const asr_fbank_t* h, int T, int B);
 int asr_fbank_fwd(asr_fbank_t* h, const float* d_wave, long ldw, const int32_t* d_nsamples, int B, int S,
                   float* d_out, long ldo, int32_t* d_frames, void* d_work, int T, asr_stream_t s);
 
+/* ---- back-off n-gram language model: ARPA loader, exact table, scoring -----
+ * No reference member is replaced: the reference decodes without a language
+ * model, while every ctcdecode caller (baseline/main.py:10) passes one.  These
+ * entry points score given hypotheses (n-best rescoring of the final beam, with
+ * asr_ctc_align's exact CTC score); no decoder kernel uses them.
+ *
+ * Model: a back-off n-gram model in ARPA text format, orders 1 ..
+ * ASR_LM_MAX_ORDER.  Log10 probabilities and back-off weights are the fp32
+ * nearest to the decimal text; a missing back-off field is 0.  Tabs or spaces
+ * separate fields; -99 is a value like any other.  A token's id is the 0-based
+ * position of its line in the \1-grams: section; <s>, </s> and <unk> get ids
+ * like any other token and are reported as bos / eos / unk (-1 when absent).
+ *
+ * Recursion: let n = min(order, available context + 1) and the context h the
+ * last n-1 tokens, <s> included while it is within reach and ASR_LM_BOS is set.
+ *   p(w | h) = P(h w)               if the n-gram (h w) is in the model
+ *            = bo(h) + p(w | h')    otherwise
+ * with bo(h) = 0 when h is not in the model, h' = h without its earliest token,
+ * p(w | empty) = P(w).  The longest n-gram present wins even when its own
+ * suffix is absent (pruned models; no suffix closure is assumed).  A token's
+ * value is computed in fp64 from the widened fp32 entries, added left to right
+ * from 0.0: the back-offs from the longest context downward (0.0 for an absent
+ * one), then P.  Its matched order (1 .. n) is the length of the n-gram whose P
+ * was used.
+ * OOV: an id outside [0, vocab).  With <unk> in the model it is replaced by unk
+ * and scored as such, in contexts too; without, it scores oov_log10 (given at
+ * create; finite, <= 0), its matched order is 0 and it cuts the context: later
+ * tokens see no token at or before it.  It counts in n_oov either way.
+ * Flags: ASR_LM_BOS — the context starts as [<s>], <s> itself is never scored;
+ * ASR_LM_EOS — </s> is scored after the last token, also for an empty
+ * hypothesis.  A flag whose token the model lacks: ASR_ERR_ARG.
+ *
+ * Table: a trie keyed in reverse — the n-gram (w1..wk) sits on
+ * the path wk, wk-1, .., w1 — so that the walk w_i, w_i-1, .. finds the longest
+ * matching n-gram and the walk w_i-1, w_i-2, .. reads every nested context's
+ * back-off on the way down.  Per order: the word ids of every parent's
+ * children, sorted, and (P, back-off, first child) per node; unigrams are
+ * indexed directly.  Exact: no hashing.  Where an n-gram's suffix is absent the
+ * missing nodes are inserted without a probability (nodes_inserted); a match
+ * on one does not count as a match. */
+#define ASR_LM_MAX_ORDER 8
+enum { ASR_LM_BOS = 1, ASR_LM_EOS = 2 };
+typedef struct asr_lm asr_lm_t;
+typedef struct asr_lm_info {
+    int32_t order, vocab;
+    int32_t bos_id, eos_id, unk_id;           /* -1: absent */
+    int32_t reserved;
+    int64_t ngrams[ASR_LM_MAX_ORDER];         /* n-grams of order k+1 in the file */
+    int64_t nodes_inserted;                   /* trie nodes that carry no probability */
+    int64_t table_bytes;                      /* bytes of the tables (host = device) */
+} asr_lm_info;
+
+/* Host only, no HIP call (they work on a machine without a GPU): parse the
+ * file / the `bytes` bytes at `text` and build the tables.
+ * ASR_ERR_ARG: a NULL argument, oov_log10 not finite or > 0, an unreadable
+ * file, a missing \data\ or \end\, no unigram, orders that are not 1 .. n
+ * without a gap, a section whose count differs from its `ngram k=` line, a
+ * non-numeric, NaN or infinite value, a probability > 0, a token of a
+ * higher-order n-gram that has no unigram, a duplicate n-gram, a wrong number
+ * of fields (k + 1 or k + 2 for order k; a back-off given at the top order is
+ * read and never used); ASR_ERR_UNSUPPORTED: an order above
+ * ASR_LM_MAX_ORDER, 2^31 or more n-grams (or trie nodes) in one order;
+ * ASR_ERR_OOM: a host allocation failed.  Text before the \data\ line and
+ * after the \end\ line is ignored; a top order declared with 0 n-grams does
+ * not count as an order. */
+int asr_lm_create_arpa(const char* path, float oov_log10, asr_lm_t** out);
+int asr_lm_create_arpa_mem(const char* text, size_t bytes, float oov_log10, asr_lm_t** out);
+int asr_lm_destroy(asr_lm_t* h);
+int asr_lm_get_info(const asr_lm_t* h, asr_lm_info* info);
+/* *id = -1 when the token is absent (still ASR_OK). */
+int asr_lm_token_id(const asr_lm_t* h, const char* token, int32_t* id);
+/* *token points into the handle (valid until asr_lm_destroy); ASR_ERR_ARG for
+ * an id outside [0, vocab). */
+int asr_lm_token_string(const asr_lm_t* h, int32_t id, const char** token);
+
+/* Score N hypotheses.  tokens [N][ldt] token ids, ldt >= max_len; lengths [N]
+ * clamped to [0, max_len], NULL = max_len for every hypothesis.  Outputs, each
+ * may be NULL, at least one given:
+ *   logp [N]            total log10 probability (fp64);
+ *   counts [N][2]       tokens scored (</s> included) and OOVs;
+ *   tok_logp [N][ldd]   per-token log10 probability (fp64);
+ *   tok_order [N][ldd]  per-token matched order;
+ * ldd >= max_len + 1: the </s> entry is at index L; entries past the scored
+ * ones are not touched.  The total is the sum of 64 partial sums in a fixed
+ * tree (partial l: positions l, l+64, .. in increasing order, from 0.0; then
+ * partial[l] += partial[l + 32], + 16, .. + 1), so a hypothesis' results depend
+ * only on its own tokens and the flags: never on N, its row, ldt, max_len or
+ * which outputs were asked for.
+ * asr_lm_score_host: host arrays, plain C++ over the same tables, one thread,
+ * no HIP call — the library's CPU path; same results as the device, bit for
+ * bit.
+ * asr_lm_upload: copies the tables to the current device (synchronous; a
+ * second call is a no-op).  A handle serves the device it was uploaded on.
+ * asr_lm_score: device arrays; one launch, one wave per hypothesis (lane l
+ * takes positions l, l+64, ..), asynchronous on s, no allocation, no host sync.
+ * Checks, in this order, all before any HIP call — ASR_ERR_ARG: a NULL handle
+ * or tokens, a non-positive N, ldt < max_len, ldd < max_len + 1 with a detail
+ * output, no output, a flag whose token is absent; ASR_ERR_UNSUPPORTED:
+ * max_len > 65536 or < 0; ASR_ERR_STATE (asr_lm_score only): not uploaded. */
+int asr_lm_score_host(const asr_lm_t* h, const int32_t* h_tokens, long ldt, const int32_t* h_lengths, int N,
+                      int max_len, int flags, double* h_logp, int32_t* h_counts, double* h_tok_logp,
+                      int32_t* h_tok_order, long ldd);
+int asr_lm_upload(asr_lm_t* h);
+int asr_lm_score(const asr_lm_t* h, const int32_t* d_tokens, long ldt, const int32_t* d_lengths, int N,
+                 int max_len, int flags, double* d_logp, int32_t* d_counts, double* d_tok_logp,
+                 int32_t* d_tok_order, long ldd, asr_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
