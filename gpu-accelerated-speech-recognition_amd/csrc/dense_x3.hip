@@ -56,6 +56,10 @@ bool dense_x3_on() { return dense_arith() == ASR_DENSE_SPLIT_BF16; }
 #ifndef ASR_X3G_SGB
 #define ASR_X3G_SGB 0    // GEMM: sched_group_barrier order of reads / MFMAs
 #endif
+#ifndef ASR_X3G_RING
+#define ASR_X3G_RING 3   // GEMM, two-phase schedule: LDS tile buffers; 3: chunk 0's fragments are read ahead of the
+                         // hand-off barrier (1.08 ms vs 1.10-1.11 with 2 on the C4 input projection, 128 CUs)
+#endif
 #ifndef ASR_X3R_TANH
 #define ASR_X3R_TANH 0   // recurrence: branch-free exp2 / rcp tanh (<= 1.6 ulp)
 #endif
@@ -171,6 +175,28 @@ __device__ __forceinline__ void lds_barrier_x3() {
 //     ds_read_b128 per piece (row c15, k = 32c + 8g .. + 7).
 //   * Row tiles per workgroup: tpw > 0 a contiguous run of tpw tiles (short
 //     workgroups that free their CU soon), 0 persistent (stride gridDim.x).
+//   * PP (the default; ASR_X3G_PINGPONG=0 selects the one-phase loop above,
+//     read at each launch): the two halves of the workgroup (waves 0-3 and
+//     4-7; waves w and w + 4 share a SIMD) run half a tile apart.  Time is cut
+//     into slots, one workgroup barrier after each, two per tile: in slot 2i
+//     half 0 runs tile i's MFMAs while half 1 does its service work (the C
+//     stores of the tile it finished, split + LDS stores of its share of a
+//     coming tile from the registers loaded two slots earlier, the global
+//     loads of its share of the tile after that); in slot 2i + 1 the roles
+//     swap.  So each SIMD's matrix pipe has one wave in its MFMAs beside one
+//     in vector / LDS / memory work.  A thread's share of a tile is the
+//     elements it stages in the one-phase loop.  Tile j lives in LDS buffer
+//     j % ASR_X3G_RING.  Ring 3: tile j is written in slots 2j - 3 (half 0)
+//     and 2j - 2 (half 1), read in slots 2j - 1 .. 2j + 1 (chunk 0's fragments
+//     ahead of the hand-off barrier, then the MFMA slots of the two halves),
+//     and tile j + 3 is written from slot 2j + 3.  Ring 2: written in slots
+//     2j - 2 (half 1) and 2j - 1 (half 0), read in 2j and 2j + 1.  Each half
+//     has its own loop over the workgroup's tile count (from blockIdx, gridDim
+//     and the arguments only) with one barrier after each of its two slots, so
+//     every wave executes the prologue barrier and two per tile, whatever its
+//     half or columns.  Column ownership,
+//     chunk order, X3_PRODUCTS and the accumulators are those of the one-phase
+//     loop: same bits.
 // ---------------------------------------------------------------------------
 constexpr int X3_ROWS = 16;
 constexpr int X3_WAVES = 8;
@@ -185,12 +211,15 @@ constexpr int X3_NCOL = 32 * X3_WAVES;
 // M % 16 == 0, no bias.
 constexpr int X3_EPI_FRAG = 8;
 
-template <int NCH>
+constexpr int X3_RING = ASR_X3G_RING;
+static_assert(X3_RING == 2 || X3_RING == 3, "ASR_X3G_RING: 2 or 3 tile buffers");
+
+template <int NCH, bool PP>
 constexpr int x3_gemm_lds() {
-    return 2 * 3 * X3_ROWS * (NCH * 32 + 8) * 2;
+    return (PP ? X3_RING : 2) * 3 * X3_ROWS * (NCH * 32 + 8) * 2;
 }
 
-template <int NCH, int EPI>
+template <int NCH, int EPI, bool PP>
 __global__ __launch_bounds__(64 * X3_WAVES) void gemm_x3_kernel(GemmArgs g, int tpw) {
     constexpr int KC = NCH * 32;              // staged k columns (zero past K)
     constexpr int AS = KC + 8;                // LDS row stride (bf16): rows 16 B apart in banks
@@ -246,7 +275,8 @@ __global__ __launch_bounds__(64 * X3_WAVES) void gemm_x3_kernel(GemmArgs g, int 
             const int idx = tid + 64 * X3_WAVES * i;
             const int row = idx / (KC / 4), k = (idx % (KC / 4)) * 4;
             f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (row * (int)g.sam + k) * 4, 0, 0));
-            if (k >= g.K || idx >= NV4) v = f32x4{0.f, 0.f, 0.f, 0.f};
+            // PP zeroes past K in stage(), so that nothing in the slot that issues the load waits for its data
+            if (!PP && (k >= g.K || idx >= NV4)) v = f32x4{0.f, 0.f, 0.f, 0.f};
             st[i] = v;
         }
     };
@@ -257,11 +287,12 @@ __global__ __launch_bounds__(64 * X3_WAVES) void gemm_x3_kernel(GemmArgs g, int 
             const int idx = tid + 64 * X3_WAVES * i;
             if (NV4 % (64 * X3_WAVES) != 0 && idx >= NV4) continue;
             const int row = idx / (KC / 4), k = (idx % (KC / 4)) * 4;
+            const f32x4 v = (!PP || k < g.K) ? st[i] : f32x4{0.f, 0.f, 0.f, 0.f};
             bf16x4 h, m, l;
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 __bf16 a, b, c;
-                split3(st[i][e], a, b, c);
+                split3(v[e], a, b, c);
                 h[e] = a;
                 m[e] = b;
                 l[e] = c;
@@ -272,6 +303,121 @@ __global__ __launch_bounds__(64 * X3_WAVES) void gemm_x3_kernel(GemmArgs g, int 
             *reinterpret_cast<bf16x4*>(p + 2 * PIECE) = l;
         }
     };
+    auto store_c = [&](int tl, const f32x4 (&acc)[2]) {
+        const long r0 = (long)tl * X3_ROWS;
+        if (EPI == X3_EPI_FRAG) {
+            if (32 * w < g.N) {
+                f32x4* dst = reinterpret_cast<f32x4*>(g.C + r0 * g.N + (long)(64 * w + lane) * 8);
+                dst[0] = acc[0];
+                dst[1] = acc[1];
+            }
+        } else {
+            // row 4 gq + j through a resource that starts at row j (scalar
+            // arithmetic): one lane offset per column tile for the four rows
+            const long rows = min((long)X3_ROWS, (long)g.M - r0);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const auto cs = brsrc(g.C + (r0 + j) * g.ldc, max(0L, rows - j) * g.ldc * 4);
+#pragma unroll
+                for (int ct = 0; ct < 2; ct++) {
+                    if (ncol[ct] < g.N) {
+                        float y = acc[ct][j];
+                        if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) y = y + bias[ct];
+                        if (EPI == EPI_BIAS_RELU && y < 0.f) y = 0.f;
+                        bstore(cs, (4 * gq * (int)g.ldc + ncol[ct]) * 4, y);
+                    }
+                }
+            }
+        }
+    };
+    if constexpr (PP) {
+        // the two-phase schedule (header): slot s belongs to the MFMAs of half
+        // s & 1; every value that steers a loop or a branch around a barrier
+        // (half, nt) is the same in all lanes of a wave, and nt in all waves
+        // of the workgroup
+        const int half = __builtin_amdgcn_readfirstlane(w >> 2);
+        const int nt = tile < tend ? (tend - tile + tstep - 1) / tstep : 0;   // this workgroup's tiles
+        f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        bf16x8 fa[2][3];
+        auto rd = [&](const __bf16* pb, int c, int sl) {
+            const int off = c15 * AS + 32 * c + 8 * gq;
+            fa[sl][0] = *reinterpret_cast<const bf16x8*>(pb + off);
+            fa[sl][1] = *reinterpret_cast<const bf16x8*>(pb + PIECE + off);
+            fa[sl][2] = *reinterpret_cast<const bf16x8*>(pb + 2 * PIECE + off);
+        };
+        auto next = [](int b) { return b + 1 == X3_RING ? 0 : b + 1; };
+        // prologue: tile 0 whole; st = this thread's share of tile 1, which
+        // with three buffers half 0 stages here (its slot would be -1)
+        load(tile);
+        stage(0);
+        load(tile + tstep);
+        int tl = tile + 2 * tstep;   // the tile whose share this wave loads next
+        int sb = 1;                  // the buffer of the tile in st
+        if (X3_RING == 3 && half == 0) {
+            stage(1);
+            load(tl);
+            tl += tstep;
+            sb = 2;
+        }
+        lds_barrier_x3();
+        if (X3_RING == 3 && half == 0) rd(x3s, 0, 0);
+        int cb = 0;        // the buffer of the tile this wave computes next
+        int tcomp = tile;  // that tile
+        int tlast = -1;    // the tile in acc, not stored yet
+        auto compute = [&]() {
+            const __bf16* pb = x3s + cb * 3 * PIECE;
+            acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+            acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (X3_RING != 3) rd(pb, 0, 0);
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                if (c + 1 < NCH) rd(pb, c + 1, (c + 1) & 1);
+                X3_PRODUCTS(2, acc, fa[c & 1][0], fa[c & 1][1], fa[c & 1][2], bh, bm, bl, c)
+            }
+            tlast = tcomp;
+            tcomp += tstep;
+            cb = next(cb);
+        };
+        // st's loads were issued two slots ago; the new ones (zeros past the
+        // workgroup's last tile) are not waited for here
+        auto service = [&]() {
+            if (tl - tstep < tend) stage(sb);
+            sb = next(sb);
+            load(tl);
+            tl += tstep;
+            if (tlast >= 0) store_c(tlast, acc);
+            tlast = -1;
+            if (X3_RING == 3) rd(x3s + cb * 3 * PIECE, 0, 0);
+        };
+        // Each half runs straight-line code (no register shuffling between the
+        // two roles): nt iterations of two slots, one barrier after each slot,
+        // in either branch.
+        // The barrier orders LDS accesses only, so the instruction scheduler
+        // is told as well to keep a slot's MFMAs on its side of the hand-off
+        // (it moved a fifth of them past it: 1.14-1.16 -> 1.10-1.11 ms).
+        auto slot_end = [&]() {
+            __builtin_amdgcn_sched_barrier(0);
+            lds_barrier_x3();
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        if (half == 0) {
+            for (int i = 0; i < nt; i++) {
+                compute();
+                slot_end();
+                service();
+                slot_end();
+            }
+        } else {
+            for (int i = 0; i < nt; i++) {
+                service();
+                slot_end();
+                compute();
+                slot_end();
+            }
+        }
+        if (tlast >= 0) store_c(tlast, acc);   // half 1's last tile
+        return;
+    }
     load(tile);
     stage(0);
     load(tile + tstep);
@@ -314,37 +460,17 @@ __global__ __launch_bounds__(64 * X3_WAVES) void gemm_x3_kernel(GemmArgs g, int 
 #endif
         stage(cur ^ 1);
         load(tile + 2 * tstep);
-        const long r0 = (long)tile * X3_ROWS;
-        if (EPI == X3_EPI_FRAG) {
-            if (32 * w < g.N) {
-                f32x4* dst = reinterpret_cast<f32x4*>(g.C + r0 * g.N + (long)(64 * w + lane) * 8);
-                dst[0] = acc[0];
-                dst[1] = acc[1];
-            }
-        } else {
-        const auto cs = brsrc(g.C + r0 * g.ldc, min((long)X3_ROWS, (long)g.M - r0) * g.ldc * 4);
-#pragma unroll
-        for (int ct = 0; ct < 2; ct++) {
-            if (ncol[ct] < g.N) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    float y = acc[ct][j];
-                    if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) y = y + bias[ct];
-                    if (EPI == EPI_BIAS_RELU && y < 0.f) y = 0.f;
-                    bstore(cs, ((4 * gq + j) * (int)g.ldc + ncol[ct]) * 4, y);
-                }
-            }
-        }
-        }
+        store_c(tile, acc);
         __syncthreads();
         cur ^= 1;
     }
 }
 
-template <int NCH, int EPI>
+template <int NCH, int EPI, bool PP>
 static int launch_gemm_x3_k(const GemmArgs& g, int tpw, hipStream_t s) {
+    constexpr int lds = x3_gemm_lds<NCH, PP>();
     static AsrAttrOnce attr;
-    if (int r_ = attr.set((const void*)gemm_x3_kernel<NCH, EPI>, x3_gemm_lds<NCH>())) return r_;
+    if (int r_ = attr.set((const void*)gemm_x3_kernel<NCH, EPI, PP>, lds)) return r_;
     const int ntile = (g.M + X3_ROWS - 1) / X3_ROWS;
     const int ncol = (g.N + X3_NCOL - 1) / X3_NCOL;
     int rows;
@@ -357,18 +483,29 @@ static int launch_gemm_x3_k(const GemmArgs& g, int tpw, hipStream_t s) {
             ncu = 256;
         rows = max(1, min(ntile, ncu / max(1, ncol)));   // one workgroup per CU (2 waves per SIMD)
     }
-    hipLaunchKernelGGL((gemm_x3_kernel<NCH, EPI>), dim3((unsigned)rows, (unsigned)ncol), dim3(64 * X3_WAVES),
-                       x3_gemm_lds<NCH>(), s, g, tpw);
+    hipLaunchKernelGGL((gemm_x3_kernel<NCH, EPI, PP>), dim3((unsigned)rows, (unsigned)ncol), dim3(64 * X3_WAVES),
+                       lds, s, g, tpw);
     ASR_LAUNCH_TRY();
     return ASR_OK;
 }
 
+// ASR_X3G_PINGPONG=0: the one-phase loop (the bit-for-bit reference and A/B baseline).
+static bool pingpong_off() {
+    const char* e = getenv("ASR_X3G_PINGPONG");
+    return e && e[0] == '0';
+}
+
+template <int EPI, bool PP>
+static int launch_gemm_x3_pp(const GemmArgs& g, int tpw, hipStream_t s) {
+    if (g.K <= 32) return launch_gemm_x3_k<1, EPI, PP>(g, tpw, s);
+    if (g.K <= 64) return launch_gemm_x3_k<2, EPI, PP>(g, tpw, s);
+    if (g.K <= 128) return launch_gemm_x3_k<4, EPI, PP>(g, tpw, s);
+    return launch_gemm_x3_k<8, EPI, PP>(g, tpw, s);
+}
+
 template <int EPI>
 static int launch_gemm_x3_epi(const GemmArgs& g, int tpw, hipStream_t s) {
-    if (g.K <= 32) return launch_gemm_x3_k<1, EPI>(g, tpw, s);
-    if (g.K <= 64) return launch_gemm_x3_k<2, EPI>(g, tpw, s);
-    if (g.K <= 128) return launch_gemm_x3_k<4, EPI>(g, tpw, s);
-    return launch_gemm_x3_k<8, EPI>(g, tpw, s);
+    return pingpong_off() ? launch_gemm_x3_pp<EPI, false>(g, tpw, s) : launch_gemm_x3_pp<EPI, true>(g, tpw, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -47,7 +47,7 @@ def load(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mfma", required=True)
-    ap.add_argument("--valu", required=True)
+    ap.add_argument("--valu", default=None, help="omit: only mfma.json is written")
     ap.add_argument("--workload", default="C4")
     ap.add_argument("--cus", action="append", default=[], help="kernel=CUs it ran on (its stream's CU mask)")
     ap.add_argument("--slice-cus", type=int, default=0,
@@ -116,6 +116,9 @@ def main():
                            "note": "rocprofv3 --pmc (dispatches serialised); mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES "
                                    "/ (4 SIMDs x CUs x GRBM_GUI_ACTIVE/8)"}
     p.write_text(json.dumps(allw, indent=1))
+    if not args.valu:
+        print(json.dumps({"mfma": out}, indent=1)[:4000])
+        return
     # decoder VALU mix
     vper, vmeta = load(args.valu)
     dec = [(c, vmeta[d][1]) for d, c in vper.items() if args.decoder in vmeta[d][0]]
