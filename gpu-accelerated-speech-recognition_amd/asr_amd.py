@@ -72,6 +72,7 @@ EXPORTS = [
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
     "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
     "asr_lm_token_string", "asr_lm_score_host", "asr_lm_upload", "asr_lm_score",
+    "asr_edit_distance", "asr_edit_distance_host", "asr_nbest_mbr", "asr_nbest_mbr_host",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -191,6 +192,12 @@ def lib() -> ctypes.CDLL:
         "asr_lm_score_host": [_vp, _vp, ctypes.c_long, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_long],
         "asr_lm_upload": [_vp],
         "asr_lm_score": [_vp, _vp, ctypes.c_long, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_long, _vp],
+        "asr_edit_distance": [_vp, ctypes.c_long, _vp, _i, _i, _vp, ctypes.c_long, _vp, _i, _i, _vp, _vp, _i, _vp, _vp,
+                              _vp],
+        "asr_edit_distance_host": [_vp, ctypes.c_long, _vp, _i, _i, _vp, ctypes.c_long, _vp, _i, _i, _vp, _vp, _i, _vp,
+                                   _vp],
+        "asr_nbest_mbr": [_vp, ctypes.c_long, _vp, _i, _i, _vp, _i, _i, _vp, _vp, ctypes.c_long, _vp, _vp, _vp],
+        "asr_nbest_mbr_host": [_vp, ctypes.c_long, _vp, _i, _i, _vp, _i, _i, _vp, _vp, ctypes.c_long, _vp, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -1035,6 +1042,32 @@ class CTCDecoder:
             out.append(sorted(rows, key=lambda r: -r[1]))
         return out
 
+    def mbr_rescore(self, max_hyps: int, scale: float = 1.0, lm: Optional["NGramLM"] = None, alpha: float = 0.0,
+                    beta: float = 0.0, mapper=None, tokens=None,
+                    stream: int = 0) -> List[List[Tuple[List[int], float, float]]]:
+        """The final beam re-ranked by minimum Bayes risk: per utterance [(labels,
+        risk, total)], risk ascending (equal risks keep the order of the ranking
+        they came from).  risk is the expected edit distance to the other
+        hypotheses of the beam under the weights scale * total (natural log),
+        where total is rescore()'s exact CTC score or, with lm, lm_rescore()'s
+        total (alpha, beta and mapper as there).  Distances are taken over the
+        labels, or over tokens(labels) when tokens is given (word_tokens for word
+        error).  One asr_nbest_mbr call for the whole batch (max_hyps <=
+        ASR_MBR_MAX_HYPS).  After decode() / decode_device() of whole utterances,
+        as rescore()."""
+        if self._last is None:
+            raise AsrError(ASR_ERR_STATE, "CTCDecoder.mbr_rescore: no whole-utterance decode yet")
+        if lm is not None:
+            ranked = [[(r[0], r[1]) for r in u] for u in self.lm_rescore(max_hyps, lm, alpha, beta, mapper,
+                                                                         stream=stream)]
+        else:
+            ranked = [[(r[0], r[1]) for r in u] for u in self.rescore(max_hyps, stream=stream)]
+        seqs = [[list(tokens(lab)) if tokens is not None else lab for lab, _ in u] for u in ranked]
+        weights = [[scale * total for _, total in u] for u in ranked]
+        risks, _, _ = nbest_mbr(seqs, weights, stream=stream)
+        return [sorted(((lab, float(risks[b][j]), total) for j, (lab, total) in enumerate(u)), key=lambda r: r[1])
+                for b, u in enumerate(ranked)]
+
     def last_kernel_ms(self) -> float:
         ms = _f()
         check(lib().asr_ctc_last_kernel_ms(self.h, ctypes.byref(ms)), "asr_ctc_last_kernel_ms")
@@ -1315,6 +1348,126 @@ class NGramLM:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------ edit distance, WER and n-best MBR rescoring
+ASR_EDIT_MAX_LEN = 1024
+ASR_MBR_MAX_HYPS = 256
+
+
+def _pack_rows(rows: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Token lists as (table [n][ld] int32, lengths [n], longest length)."""
+    max_len = max([len(r) for r in rows] + [0])
+    tab = np.zeros((len(rows), max(max_len, 1)), np.int32)
+    for n, r in enumerate(rows):
+        tab[n, :len(r)] = np.asarray(r, dtype=np.int32)
+    return tab, np.array([len(r) for r in rows], np.int32), max_len
+
+
+def edit_distance(refs: Sequence[Sequence[int]], hyps: Sequence[Sequence[int]], pairs=None, detail: bool = False,
+                  host: bool = False, stream: int = 0):
+    """Levenshtein distance of token lists (the semantics are in
+    include/asr_amd.h): int32 [P]; with detail also the [P, 4] counts (hits,
+    substitutions, deletions, insertions) of the alignment the tie rule fixes.
+    Pair p is (refs[p], hyps[p]), or (refs[i], hyps[j]) for pairs[p] = (i, j);
+    an index outside its list gives -1.  host=True runs asr_edit_distance_host;
+    otherwise one asr_edit_distance launch on stream."""
+    if pairs is None:
+        if len(refs) != len(hyps):
+            raise ValueError("edit_distance: refs and hyps differ in number and no pairs are given")
+        P, ri, hi = len(refs), None, None
+    else:
+        idx = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        P, ri, hi = len(idx), np.ascontiguousarray(idx[:, 0]), np.ascontiguousarray(idx[:, 1])
+    if P == 0:
+        return (np.zeros(0, np.int32), np.zeros((0, 4), np.int32)) if detail else np.zeros(0, np.int32)
+    rt, rl, rmax = _pack_rows(refs)
+    ht, hl, hmax = _pack_rows(hyps)
+    dist = np.zeros(P, np.int32)
+    ops = np.zeros((P, 4), np.int32) if detail else None
+    if host:
+        check(lib().asr_edit_distance_host(_ptr(rt), rt.shape[1], _ptr(rl), len(refs), rmax, _ptr(ht), ht.shape[1],
+                                           _ptr(hl), len(hyps), hmax, None if ri is None else _ptr(ri),
+                                           None if hi is None else _ptr(hi), P, _ptr(dist),
+                                           _ptr(ops) if detail else None), "asr_edit_distance_host")
+    else:
+        d_rt, d_rl, d_ht, d_hl = (_upload(a, stream) for a in (rt, rl, ht, hl))
+        d_ri = None if ri is None else _upload(ri, stream)
+        d_hi = None if hi is None else _upload(hi, stream)
+        d_dist = DeviceBytes(4 * P)
+        d_ops = DeviceBytes(16 * P) if detail else None
+        check(lib().asr_edit_distance(d_rt.ptr, rt.shape[1], d_rl.ptr, len(refs), rmax, d_ht.ptr, ht.shape[1],
+                                      d_hl.ptr, len(hyps), hmax, d_ri.ptr if d_ri else None,
+                                      d_hi.ptr if d_hi else None, P, d_dist.ptr, d_ops.ptr if detail else None,
+                                      stream or None), "asr_edit_distance")
+        dist = _download(d_dist, P, np.int32, stream)
+        ops = _download(d_ops, (P, 4), np.int32, stream) if detail else None
+    return (dist, ops) if detail else dist
+
+
+def wer(refs: Sequence[Sequence[int]], hyps: Sequence[Sequence[int]], host: bool = False) -> dict:
+    """Corpus error rate of hyps[p] against refs[p] over tokens (labels: CER,
+    word ids from word_tokens: WER): errors, ref_tokens, hits, sub, del, ins and
+    wer = errors / ref_tokens (inf for errors against no reference token, 0.0
+    for none of either)."""
+    _, ops = edit_distance(refs, hyps, detail=True, host=host)
+    h, s, d, i = (int(x) for x in ops.astype(np.int64).sum(axis=0)) if len(ops) else (0, 0, 0, 0)
+    errors, ref_tokens = s + d + i, h + s + d
+    rate = errors / ref_tokens if ref_tokens else (math.inf if errors else 0.0)
+    return {"errors": errors, "ref_tokens": ref_tokens, "hits": h, "sub": s, "del": d, "ins": i, "wer": rate}
+
+
+def word_tokens(label_lists: Sequence[Sequence[int]], labels: Sequence[str], space: str = " ") -> List[List[int]]:
+    """Hypotheses of label ids as lists of word ids: the label strings are joined,
+    split at `space`, and every non-empty word gets an id from one dictionary
+    that grows over the call (first seen, first numbered), so that references
+    and hypotheses passed together share their ids."""
+    labels = list(labels)
+    ids: dict = {}
+    return [[ids.setdefault(w, len(ids)) for w in "".join(labels[c] for c in hyp).split(space) if w != ""]
+            for hyp in label_lists]
+
+
+def nbest_mbr(token_lists_per_utt: Sequence[Sequence[Sequence[int]]], log_weights_per_utt=None, host: bool = False,
+              stream: int = 0):
+    """Minimum-Bayes-risk scores of n-best lists (asr_nbest_mbr): per utterance
+    the hypotheses' token lists and their natural-log weights (None: uniform).
+    Returns (risks: a float64 array per utterance, best: int32 [utterances], the
+    index of the smallest risk, -1 for an empty list; distances: an int32 [n, n]
+    matrix per utterance).  host=True runs asr_nbest_mbr_host; otherwise one
+    asr_nbest_mbr call (two launches) on stream."""
+    G = len(token_lists_per_utt)
+    sizes = [len(u) for u in token_lists_per_utt]
+    N = sum(sizes)
+    if N == 0:
+        return [np.zeros(0, np.float64) for _ in sizes], np.full(G, -1, np.int32), \
+            [np.zeros((0, 0), np.int32) for _ in sizes]
+    tok, ln, max_len = _pack_rows([t for u in token_lists_per_utt for t in u])
+    gs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    max_hyps = max(sizes)
+    w = None
+    if log_weights_per_utt is not None:
+        w = np.ascontiguousarray([x for u in log_weights_per_utt for x in u], dtype=np.float64)
+        if w.shape != (N,):
+            raise ValueError("nbest_mbr: one weight per hypothesis")
+    dist = np.zeros((N, max_hyps), np.int32)
+    risk, best = np.zeros(N, np.float64), np.zeros(G, np.int32)
+    if host:
+        check(lib().asr_nbest_mbr_host(_ptr(tok), tok.shape[1], _ptr(ln), N, max_len, _ptr(gs), G, max_hyps,
+                                       None if w is None else _ptr(w), _ptr(dist), max_hyps, _ptr(risk), _ptr(best)),
+              "asr_nbest_mbr_host")
+    else:
+        d_tok, d_ln, d_gs = _upload(tok, stream), _upload(ln, stream), _upload(gs, stream)
+        d_w = None if w is None else _upload(w, stream)
+        d_dist, d_risk, d_best = DeviceBytes(4 * N * max_hyps), DeviceBytes(8 * N), DeviceBytes(max(4 * G, 16))
+        check(lib().asr_nbest_mbr(d_tok.ptr, tok.shape[1], d_ln.ptr, N, max_len, d_gs.ptr, G, max_hyps,
+                                  d_w.ptr if d_w else None, d_dist.ptr, max_hyps, d_risk.ptr, d_best.ptr,
+                                  stream or None), "asr_nbest_mbr")
+        dist = _download(d_dist, (N, max_hyps), np.int32, stream)
+        risk = _download(d_risk, N, np.float64, stream)
+        best = _download(d_best, G, np.int32, stream)
+    return ([risk[gs[g]:gs[g + 1]].copy() for g in range(G)], best,
+            [dist[gs[g]:gs[g + 1], :sizes[g]].copy() for g in range(G)])
 
 
 class PipelineConfig(ctypes.Structure):

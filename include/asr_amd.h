@@ -825,6 +825,84 @@ int asr_lm_score(const asr_lm_t* h, const int32_t* d_tokens, long ldt, const int
                  int max_len, int flags, double* d_logp, int32_t* d_counts, double* d_tok_logp,
                  int32_t* d_tok_order, long ldd, asr_stream_t s);
 
+/* ---- edit distance, WER counts and n-best minimum-Bayes-risk rescoring -----
+ * No reference member is replaced: the reference neither scores a decode
+ * against a transcript nor re-ranks its beam.  These entry points score given
+ * token rows; no decoder kernel uses them.
+ *
+ * Sequences are rows of int32 tokens (label ids, word ids, anything); tokens
+ * are compared by equality only, so every int32 value is legal.  For a pair
+ * (reference a of length la, hypothesis b of length lb):
+ *   D[i][0] = i (i deletions)      D[0][j] = j (j insertions)
+ *   D[i][j] = min( D[i-1][j-1] + (a_i != b_j),    diagonal: hit or substitution
+ *                  D[i-1][j]   + 1,               up: deletion (a_i has no partner)
+ *                  D[i][j-1]   + 1 )              left: insertion (b_j has no partner)
+ * The distance is D[la][lb].  The counts (hits, substitutions, deletions,
+ * insertions) are those of the one alignment fixed by the tie rule: at every
+ * cell the diagonal wins among equal minima, then up, then left.  The counts
+ * are carried forward with the cell (a cell's counts are its chosen
+ * predecessor's plus its own operation); no back-pointers are kept.  Always
+ * S + D + I = distance, H + S + D = la, H + S + I = lb.  kitten / sitting: 3 and
+ * (4, 2, 0, 1); ab / ba: 2 and (0, 2, 0, 0); abcd / bcde: 2 and (3, 0, 1, 1).
+ * Lengths are clamped to [0, the call's maximum length]; a NULL length array
+ * means the maximum length for every row.
+ *
+ * asr_edit_distance: pair p scores row d_ref_idx[p] of ref [n_ref][ldr]
+ * against row d_hyp_idx[p] of hyp [n_hyp][ldh]; a NULL index array means row
+ * p (then P <= that table's row count).  Outputs, each may be NULL, at least
+ * one given: dist [P]; ops [P][4] = (H, S, D, I).  An index outside its table
+ * gives distance -1 and counts -1 and is never used for a read.  One launch,
+ * one wave per pair (the DP in registers), asynchronous on s, no allocation,
+ * no workspace, no host sync.
+ *
+ * asr_nbest_mbr: group g is rows [gs[g], gs[g+1]) of tokens [N][ldt], gs =
+ * group_start [G + 1]; a group with gs[g] < 0, gs[g+1] > N or gs[g+1] < gs[g]
+ * is empty; rows of a group beyond its first max_hyps are not part of it and
+ * nothing of theirs is written.  Hypothesis j of a group of n has the natural-
+ * log weight w_j (weight [N], by row; NULL: uniform).  A NaN weight counts as
+ * -inf; with m = max_j w_j: e_j = exp(w_j - m) for a finite m, e_j = 1 for
+ * every j when m = -inf, e_j = (w_j == +inf) when m = +inf.  Then
+ *   Z = sum_j e_j     risk_k = (sum_j e_j * d(k, j)) / Z
+ * both sums in asr_lm_score's fixed tree (partial l: j = l, l+64, l+128, l+192
+ * in increasing order from 0.0; then partial[l] += partial[l + 32], + 16, ..
+ * + 1), e_j * d one rounded product and one rounded add (no fma).
+ *   dist [N][ldm], ldm >= max_hyps, required: row k, column j - gs[g] is
+ *     d(k, j) over the group's members (symmetric, 0 diagonal); columns >= n
+ *     are not touched.  It is the intermediate and an output.
+ *   risk [N] and best [G] (the row, within its group, of the smallest risk,
+ *     the lowest on ties; -1 for an empty group) may each be NULL, not both.
+ * Two launches (the pair distances, then the risks), a linear chain on s that
+ * can be captured; no allocation, no host sync.
+ *
+ * The _host twins take host arrays: plain C++ on one thread, no HIP call — the
+ * library's CPU path.  The cell update and the risk sum are the kernels' own
+ * functions, so integers agree exactly and risks differ only through exp().
+ * A pair's results depend on its two sequences only — never on P, N, its
+ * position, the leading dimensions, the maximum lengths of the call or which
+ * outputs were asked for; a group's on its own rows and weights only.
+ * Checks, in this order, all before any HIP call — ASR_ERR_ARG: a NULL
+ * required pointer (ref, hyp; tokens, group_start, dist), a non-positive P, N,
+ * G, row count or max_hyps, a leading dimension below its maximum length or
+ * ldm < max_hyps, no output, a NULL index array with P above that table's row
+ * count; ASR_ERR_UNSUPPORTED: a maximum length above ASR_EDIT_MAX_LEN or
+ * negative, max_hyps > ASR_MBR_MAX_HYPS. */
+#define ASR_EDIT_MAX_LEN 1024
+#define ASR_MBR_MAX_HYPS 256
+int asr_edit_distance(const int32_t* d_ref, long ldr, const int32_t* d_ref_len, int n_ref, int max_ref_len,
+                      const int32_t* d_hyp, long ldh, const int32_t* d_hyp_len, int n_hyp, int max_hyp_len,
+                      const int32_t* d_ref_idx, const int32_t* d_hyp_idx, int P,
+                      int32_t* d_dist, int32_t* d_ops, asr_stream_t s);
+int asr_edit_distance_host(const int32_t* h_ref, long ldr, const int32_t* h_ref_len, int n_ref, int max_ref_len,
+                           const int32_t* h_hyp, long ldh, const int32_t* h_hyp_len, int n_hyp, int max_hyp_len,
+                           const int32_t* h_ref_idx, const int32_t* h_hyp_idx, int P,
+                           int32_t* h_dist, int32_t* h_ops);
+int asr_nbest_mbr(const int32_t* d_tokens, long ldt, const int32_t* d_lengths, int N, int max_len,
+                  const int32_t* d_group_start, int G, int max_hyps, const double* d_weight,
+                  int32_t* d_dist, long ldm, double* d_risk, int32_t* d_best, asr_stream_t s);
+int asr_nbest_mbr_host(const int32_t* h_tokens, long ldt, const int32_t* h_lengths, int N, int max_len,
+                       const int32_t* h_group_start, int G, int max_hyps, const double* h_weight,
+                       int32_t* h_dist, long ldm, double* h_risk, int32_t* h_best);
+
 #ifdef __cplusplus
 }
 #endif
