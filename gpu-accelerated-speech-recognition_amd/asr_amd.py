@@ -19,6 +19,10 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           torch.nn.LSTM; no reference member
     GRU(input_size, hidden_size, num_layers, bidirectional).forward
                                           torch.nn.GRU; no reference member
+    Conv1d(c_in, c_out, kernel, stride, dilation, padding, groups, act).forward
+                                          torch.nn.Conv1d over time, time-major,
+                                          bias and activation fused
+                                          (asr_conv1d_fwd); no reference member
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
                                           waveform -> log-mel / MFCC features
                                           (asr_fbank_*); no reference member
@@ -68,6 +72,7 @@ EXPORTS = [
     "asr_rnn_cell_fwd", "asr_rnn_fwd", "asr_rnn_recur_fwd", "asr_rnn_persist_stats", "asr_rnn_emit_fwd", "asr_rnn_bidir_workspace_bytes", "asr_rnn_bidir_fwd",
     "asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd",
     "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
+    "asr_conv1d_out_frames", "asr_conv1d_fwd",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
     "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
@@ -177,6 +182,8 @@ def lib() -> ctypes.CDLL:
         "asr_gru_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp,
                         _i, _i, _i, _i, _i, _vp],
         "asr_gru_recur_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _i, _vp],
+        "asr_conv1d_out_frames": [_vp, _i],
+        "asr_conv1d_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i, _vp],
         "asr_fbank_num_frames": [_vp, _i],
         "asr_fbank_feature_dim": [_vp],
         "asr_fbank_host_tables": [_vp, _vp, _vp, _vp],
@@ -588,9 +595,11 @@ class LSTM:
 
     def forward(self, x: DeviceMatrix, T: int, B: int, lengths: Optional[Sequence[int]] = None,
                 stream: Optional[int] = None) -> DeviceMatrix:
-        """x time-major [T*B, input_size]; returns the last layer's [T*B, H or 2H]
-        (zeros past each utterance's length); h_n / c_n hold the final states.
-        The two directions of a layer write the two halves of one buffer."""
+        """x time-major [T*B, input_size]; lengths: a sequence of B counts or a
+        device int32 [B] (DeviceBytes, e.g. Conv1d.forward's out_lengths);
+        returns the last layer's [T*B, H or 2H] (zeros past each utterance's
+        length); h_n / c_n hold the final states.  The two directions of a layer
+        write the two halves of one buffer."""
         H, D, st = self.H, self.D, stream or 0
         if self._shape != (T, B):
             need = lstm_workspace_bytes(T, B, H)
@@ -601,7 +610,7 @@ class LSTM:
             self.outputs = [DeviceMatrix(T * B, D * H) for _ in range(self.L)]
             self.h_n, self.c_n = DeviceMatrix(self.L * D * B, H), DeviceMatrix(self.L * D * B, H)
             self._shape = (T, B)
-        ln = None if lengths is None else device_lengths(lengths)
+        ln = lengths if lengths is None or isinstance(lengths, DeviceBytes) else device_lengths(lengths)
         for l, dirs in enumerate(self.layers):
             for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(dirs):
                 k = (l * D + d) * B
@@ -706,9 +715,11 @@ class GRU:
     def forward(self, x: DeviceMatrix, T: int, B: int, lengths: Optional[Sequence[int]] = None,
                 h0: Optional[DeviceMatrix] = None, stream: Optional[int] = None) -> DeviceMatrix:
         """x time-major [T*B, input_size]; h0 [L*D*B, H] in h_n's order (None =
-        zeros); returns the last layer's [T*B, H or 2H] (zeros past each
-        utterance's length); h_n holds the final states.  The two directions
-        of a layer write the two halves of one buffer."""
+        zeros); lengths: a sequence of B counts or a device int32 [B]
+        (DeviceBytes, e.g. Conv1d.forward's out_lengths); returns the last
+        layer's [T*B, H or 2H] (zeros past each utterance's length); h_n holds
+        the final states.  The two directions of a layer write the two halves
+        of one buffer."""
         H, D, st = self.H, self.D, stream or 0
         if self._shape != (T, B):
             need = gru_workspace_bytes(T, B, H)
@@ -720,7 +731,7 @@ class GRU:
             self.h_n = DeviceMatrix(self.L * D * B, H)
             self._shape = (T, B)
         assert h0 is None or (h0.rows == self.L * D * B and h0.cols == H), (h0.rows, h0.cols)
-        ln = None if lengths is None else device_lengths(lengths)
+        ln = lengths if lengths is None or isinstance(lengths, DeviceBytes) else device_lengths(lengths)
         for l, dirs in enumerate(self.layers):
             for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(dirs):
                 k = (l * D + d) * B
@@ -731,6 +742,156 @@ class GRU:
         if ln is not None:   # the kernels read it: keep it until they are done
             check(lib().asr_stream_sync(ctypes.c_void_p(st or None)), "asr_stream_sync")
         return self.outputs[-1]
+
+
+# -------------------------------------------------------------------- Conv1d
+CONV_ACT_NONE, CONV_ACT_RELU, CONV_ACT_CLIP = 0, 1, 2
+CONV_ACTS = {None: CONV_ACT_NONE, "none": CONV_ACT_NONE, "relu": CONV_ACT_RELU, "clip": CONV_ACT_CLIP}
+
+
+class Conv1dDesc(ctypes.Structure):
+    """asr_conv1d_desc (include/asr_amd.h)."""
+    _fields_ = [("c_in", _i), ("c_out", _i), ("kernel", _i), ("stride", _i), ("dilation", _i),
+                ("pad_left", _i), ("pad_right", _i), ("groups", _i), ("act", _i), ("clip", _f)]
+
+
+def conv1d_desc(c_in: int, c_out: int, kernel: int, stride: int = 1, dilation: int = 1, pad_left: int = 0,
+                pad_right: int = 0, groups: int = 1, act=None, clip: float = 20.0) -> Conv1dDesc:
+    """A Conv1dDesc from keywords; act: None, "relu", "clip" or an ASR_CONV_ACT_* value."""
+    a = CONV_ACTS[act.lower()] if isinstance(act, str) else CONV_ACT_NONE if act is None else int(act)
+    return Conv1dDesc(c_in, c_out, kernel, stride, dilation, pad_left, pad_right, groups, a, clip)
+
+
+def conv1d_out_frames(desc, n: int) -> int:
+    """asr_conv1d_out_frames: frames out for n frames in (< 0 for a bad
+    descriptor); desc is a Conv1dDesc or the keywords of conv1d_desc."""
+    d = desc if isinstance(desc, Conv1dDesc) else conv1d_desc(**desc)
+    return int(lib().asr_conv1d_out_frames(ctypes.byref(d), int(n)))
+
+
+def conv1d_fwd(x: DeviceMatrix, W: DeviceMatrix, b: Optional[DeviceMatrix], out: DeviceMatrix, T: int, B: int,
+               desc: Conv1dDesc, lengths: Optional[DeviceBytes] = None, out_lengths: Optional[DeviceBytes] = None,
+               col: int = 0, stream: int = 0) -> DeviceMatrix:
+    """One convolution over time (asr_conv1d_fwd): x [T*B, >= c_in] time-major
+    (the row stride is x.cols), W [k * c_in / groups, c_out], b [c_out] or None,
+    the result into columns [col, col + c_out) of out [T_out*B, >= c_out] (the
+    row stride is out.cols); lengths from device_lengths(), out_lengths a
+    DeviceBytes of 4*B bytes."""
+    T_out = conv1d_out_frames(desc, T)
+    assert x.rows == T * B and x.cols >= desc.c_in, (x.rows, x.cols)
+    assert T_out <= 0 or out.rows == T_out * B, (out.rows, T_out, B)
+    assert 0 <= col and col + desc.c_out <= out.cols, (out.cols, col)
+    assert W.rows * W.cols == desc.kernel * (desc.c_in // max(desc.groups, 1)) * desc.c_out, (W.rows, W.cols)
+    assert out_lengths is None or out_lengths.nbytes >= 4 * B
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_conv1d_fwd(ctypes.byref(desc), x.ptr, x.cols, opt(lengths), W.ptr, opt(b), out.ptr + 4 * col,
+                               out.cols, opt(out_lengths), T, B, stream), "asr_conv1d_fwd")
+    return out
+
+
+class Conv1d:
+    """torch.nn.Conv1d(c_in, c_out, kernel, stride, dilation=..., groups=...)
+    over time for inference on asr_conv1d_fwd, time-major in and out, bias and
+    activation fused; no arithmetic here.  padding: an int (both sides),
+    (left, right), 'valid', 'same' (stride 1 only; left = total // 2, right =
+    total - left, as torch) or 'causal' (left = dilation * (kernel - 1));
+    groups 1 or c_in == c_out == groups; act None, 'relu' or 'clip'
+    (min(max(v, 0), clip)); weight [k][c_in / groups][c_out] and bias [c_out]
+    in this library's layout (zeros if None; pack_torch makes them from a torch
+    module)."""
+
+    def __init__(self, c_in: int, c_out: int, kernel: int, stride: int = 1, dilation: int = 1, padding=0,
+                 groups: int = 1, act=None, clip: float = 20.0, weight=None, bias=None):
+        pl, pr = self.parse_padding(padding, kernel, stride, dilation)
+        self.desc = conv1d_desc(c_in, c_out, kernel, stride, dilation, pl, pr, groups, act, clip)
+        rc = conv1d_out_frames(self.desc, 1)
+        if rc < 0:
+            raise AsrError(-rc, "asr_conv1d_out_frames")
+        shape = (kernel * (c_in // groups), c_out)
+        w = np.zeros(shape, np.float32) if weight is None else np.asarray(weight, np.float32).reshape(shape)
+        b = np.zeros(c_out, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(c_out)
+        self.W, self.b = DeviceMatrix.from_numpy(w), DeviceMatrix.from_numpy(b.reshape(-1, 1))
+        self._keep = None   # the last call's uploaded lengths: alive until its kernel is done
+
+    @staticmethod
+    def parse_padding(padding, kernel: int, stride: int = 1, dilation: int = 1) -> Tuple[int, int]:
+        """(pad_left, pad_right) of a padding argument."""
+        total = dilation * (kernel - 1)
+        if isinstance(padding, str):
+            if padding == "valid":
+                return 0, 0
+            if padding == "causal":
+                return total, 0
+            if padding == "same":
+                if stride != 1:
+                    raise ValueError("Conv1d: padding='same' takes stride 1 only")
+                return total // 2, total - total // 2
+            raise ValueError(f"Conv1d: unknown padding {padding!r}")
+        if isinstance(padding, (tuple, list)):
+            if len(padding) == 1:
+                return int(padding[0]), int(padding[0])
+            if len(padding) != 2:
+                raise ValueError(f"Conv1d: padding {padding!r}")
+            return int(padding[0]), int(padding[1])
+        return int(padding), int(padding)
+
+    @staticmethod
+    def pack_torch(conv, bn=None):
+        """(W [k][c_in/g][c_out] float32, b [c_out] float32, keywords of Conv1d)
+        from a torch.nn.Conv1d; with bn an eval-mode torch.nn.BatchNorm1d is
+        folded in float64 (W' = W g / sqrt(var + eps) per output channel,
+        b' = (b - mean) g / sqrt(var + eps) + beta) and the result rounded to
+        fp32 once.  No device call."""
+        if conv.padding_mode != "zeros":
+            raise ValueError(f"Conv1d.pack_torch: padding_mode {conv.padding_mode!r} is not supported")
+        c_in, c_out, g = conv.in_channels, conv.out_channels, conv.groups
+        if g != 1 and not (g == c_in == c_out):
+            raise ValueError("Conv1d.pack_torch: groups must be 1 or c_in == c_out == groups")
+        k, s, d = conv.kernel_size[0], conv.stride[0], conv.dilation[0]
+        w = conv.weight.detach().cpu().double().numpy()                  # [c_out][c_in/g][k]
+        b = (conv.bias.detach().cpu().double().numpy() if conv.bias is not None else np.zeros(c_out, np.float64))
+        if bn is not None:
+            if bn.training or bn.running_mean is None or bn.running_var is None:
+                raise ValueError("Conv1d.pack_torch: the BatchNorm1d must be in eval() with running statistics")
+            if bn.num_features != c_out:
+                raise ValueError("Conv1d.pack_torch: BatchNorm1d features != c_out")
+            mean = bn.running_mean.detach().cpu().double().numpy()
+            var = bn.running_var.detach().cpu().double().numpy()
+            gamma = bn.weight.detach().cpu().double().numpy() if bn.affine else np.ones(c_out)
+            beta = bn.bias.detach().cpu().double().numpy() if bn.affine else np.zeros(c_out)
+            scale = gamma / np.sqrt(var + bn.eps)
+            w = w * scale[:, None, None]
+            b = (b - mean) * scale + beta
+        W = np.ascontiguousarray(w.transpose(2, 1, 0)).astype(np.float32)   # [k][c_in/g][c_out]
+        pad = conv.padding if isinstance(conv.padding, str) else tuple(int(v) for v in conv.padding)
+        pl, pr = Conv1d.parse_padding(pad, k, s, d)
+        kwargs = dict(c_in=c_in, c_out=c_out, kernel=k, stride=s, dilation=d, padding=(pl, pr), groups=g)
+        return W, b.astype(np.float32), kwargs
+
+    @classmethod
+    def from_torch(cls, conv, bn=None, act=None, clip: float = 20.0) -> "Conv1d":
+        W, b, kw = cls.pack_torch(conv, bn)
+        return cls(**kw, act=act, clip=clip, weight=W, bias=b)
+
+    def out_frames(self, n: int) -> int:
+        return conv1d_out_frames(self.desc, n)
+
+    def forward(self, x: DeviceMatrix, T: int, B: int, lengths=None, stream: int = 0):
+        """x time-major [T*B, c_in]; lengths None, a sequence of B counts or a
+        DeviceBytes of int32 [B].  Returns (out DeviceMatrix [T_out*B, c_out]
+        with zero rows past each utterance's count, T_out, out_lengths): the
+        last a DeviceBytes of int32 [B] that GRU.forward / LSTM.forward take as
+        lengths, or None when no lengths were given.  Asynchronous on stream."""
+        T_out = self.out_frames(T)
+        if T_out <= 0:
+            raise AsrError(ASR_ERR_ARG if T_out == 0 else -T_out, "asr_conv1d_out_frames")
+        if lengths is not None and not isinstance(lengths, DeviceBytes):
+            lengths = device_lengths(lengths)
+        out = DeviceMatrix(T_out * B, self.desc.c_out)
+        oln = None if lengths is None else DeviceBytes(4 * B)
+        conv1d_fwd(x, self.W, self.b, out, T, B, self.desc, lengths=lengths, out_lengths=oln, stream=stream or 0)
+        self._keep = lengths
+        return out, T_out, oln
 
 
 # ----------------------------------------------------------------- front end

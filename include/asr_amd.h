@@ -303,6 +303,73 @@ int asr_gru_recur_fwd(const float* d_P, const float* d_h0, const float* d_W_hh, 
                       const float* d_b_hh, float* d_hiddens, long ldh, float* d_hT,
                       const int32_t* d_lengths, int T, int B, int H, int reverse, asr_stream_t s);
 
+/* One convolution layer over time — torch.nn.Conv1d semantics in this
+ * library's time-major layout, with bias and activation fused: the layer
+ * between the features (asr_fbank_fwd) and the recurrence (asr_gru_fwd,
+ * asr_lstm_fwd) of DeepSpeech2-style models, and the whole body of
+ * wav2letter / Jasper / QuartzNet ones; no reference member.
+ * Frames out for n frames in, with k = kernel, s = stride, d = dilation,
+ * pl / pr = pad_left / pad_right:
+ *   out_frames(n) = 0                                        if n <= 0 or n + pl + pr < d (k-1) + 1
+ *                 = floor((n + pl + pr - d (k-1) - 1) / s) + 1   otherwise
+ * (torch's output length); T_out = out_frames(T).
+ * d_x: row t*B + b holds c_in floats, row stride ldx >= c_in.  d_out: row
+ * t'*B + b receives c_out floats, row stride ldo >= c_out; columns >= c_out of
+ * a row are not touched (ldo = 2 c_out lets two calls fill the halves of one
+ * buffer).  d_W [k][c_in / groups][c_out] row-major, the [in][out] layout per
+ * tap (depthwise: [k][C]); d_b [c_out] or NULL for zeros.
+ *   out(t', b, co) = act((sum_{j<k} sum_{ci} xh(t' s - pl + j d, b, ci) W[j][ci][co]) + b[co])
+ * where xh is x inside the utterance and exactly 0 outside it.  The order is
+ * fixed: taps ascending, channels ascending within a tap, from a zero
+ * accumulator (dense: on fp32 MFMA, channels in groups of 4 with a zero-filled
+ * tail when c_in % 4 != 0; depthwise: one fmaf chain over the taps), then the
+ * bias is added, then the activation: ASR_CONV_ACT_NONE, _RELU max(v, 0), or
+ * _CLIP min(max(v, 0), clip) (DeepSpeech2's Hardtanh(0, 20)).  Always fp32
+ * arithmetic, whatever asr_set_dense_arith says.
+ * Lengths as in asr_lstm_fwd: d_lengths device int32 [B], clamped to [0, T],
+ * NULL = all T.  Input frames t >= len[b] are read as zero whatever the buffer
+ * holds (the kernel selects the zero, it does not multiply by a mask: padding
+ * may hold NaN).  Output rows t' >= out_frames(len[b]) are all zeros;
+ * d_out_lengths (device int32 [B], may be NULL, must not overlap d_lengths)
+ * receives out_frames(len[b]) and can be passed unchanged as d_lengths of
+ * asr_gru_fwd, asr_lstm_fwd or asr_ctc_align.  For t' below that count the
+ * result is torch.nn.functional.conv1d on the utterance's own len[b] frames
+ * with zero padding (pl, pr).
+ * An output row's bits depend only on the values in its receptive field, the
+ * weights, the bias and the descriptor: never on T, B, the row's position,
+ * other utterances' lengths, ldx / ldo, pointer alignment, or whether a zero
+ * came from padding, from a length or from data (the kernel is chosen by the
+ * descriptor alone; 16-byte loads of aligned rows give the scalar path's
+ * bits).  So a causal layer (pl = d (k-1), pr = 0) run over chunks with their
+ * d (k-1) history frames prepended and pad_left = 0 gives the whole call's bits.
+ * One launch, asynchronous on s, no allocation, no workspace, no host sync;
+ * d_out must not overlap d_x.  Checks, in this order, all before any HIP call —
+ * ASR_ERR_ARG: a NULL descriptor, d_x, d_W or d_out; non-positive T, B, c_in,
+ * c_out, kernel, stride or dilation; negative padding; ldx < c_in or
+ * ldo < c_out; an unknown act; ASR_CONV_ACT_CLIP with a clip that is not
+ * finite or <= 0; T_out = 0.  ASR_ERR_UNSUPPORTED: groups other than 1 or
+ * c_in == c_out == groups; kernel > 128; stride or dilation > 16; c_in or
+ * c_out > 4096; T + pad_left + pad_right > INT_MAX - 4096; T*B or
+ * T_out*B > INT_MAX; depthwise: B * ceil(T_out / 64) * ceil(C / 64) > INT_MAX
+ * (one grid dimension).
+ * asr_conv1d_out_frames is host only, no HIP call: out_frames(n_frames), or
+ * minus the status asr_conv1d_fwd would refuse the descriptor with (< 0). */
+enum { ASR_CONV_ACT_NONE = 0, ASR_CONV_ACT_RELU = 1, ASR_CONV_ACT_CLIP = 2 };
+typedef struct asr_conv1d_desc {
+    int c_in, c_out;          /* channels; rows of x have c_in floats, rows of out c_out */
+    int kernel;               /* k taps, 1 .. 128 */
+    int stride, dilation;     /* s, d: 1 .. 16 each */
+    int pad_left, pad_right;  /* zero frames before frame 0 / after the last frame, >= 0
+                                 (causal: pad_left = d (k-1), pad_right = 0) */
+    int groups;               /* 1 (dense) or c_in == c_out == groups (depthwise) */
+    int act;                  /* ASR_CONV_ACT_* */
+    float clip;               /* ASR_CONV_ACT_CLIP: min(max(v, 0), clip), clip > 0 */
+} asr_conv1d_desc;
+int asr_conv1d_out_frames(const asr_conv1d_desc* d, int n_frames);
+int asr_conv1d_fwd(const asr_conv1d_desc* d, const float* d_x, long ldx, const int32_t* d_lengths,
+                   const float* d_W, const float* d_b, float* d_out, long ldo,
+                   int32_t* d_out_lengths, int T, int B, asr_stream_t s);
+
 /* ---- CTC prefix beam search: replaces CTCBeamSearch (CTCBeamSearch.h:107-150,
  *      CTCBeamSearch.cu:220-312) with the semantics of the CPU decoder
  *      CTCBeamSearch.cpp:50-187 (fixes F1-F3, fp64 log domain). ---- */
