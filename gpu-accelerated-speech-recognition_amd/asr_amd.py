@@ -23,6 +23,13 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           torch.nn.Conv1d over time, time-major,
                                           bias and activation fused
                                           (asr_conv1d_fwd); no reference member
+    MultiheadAttention.from_torch(mha, chunk, left, right).forward
+    LayerNorm.from_torch(ln).forward / TransformerEncoderLayer.from_torch(layer).forward
+                                          torch.nn.MultiheadAttention (self-attention
+                                          with lengths and a chunked window),
+                                          LayerNorm and TransformerEncoderLayer,
+                                          time-major (asr_attention_fwd,
+                                          asr_layernorm_fwd); no reference member
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
                                           waveform -> log-mel / MFCC features
                                           (asr_fbank_*); no reference member
@@ -73,6 +80,7 @@ EXPORTS = [
     "asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd",
     "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
     "asr_conv1d_out_frames", "asr_conv1d_fwd",
+    "asr_attention_fwd", "asr_layernorm_fwd", "asr_mask_rows",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
     "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
@@ -184,6 +192,11 @@ def lib() -> ctypes.CDLL:
         "asr_gru_recur_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _i, _vp],
         "asr_conv1d_out_frames": [_vp, _i],
         "asr_conv1d_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i, _vp],
+        "asr_attention_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp,
+                              ctypes.c_long, _i, _i, _i, _i, _i, _vp],
+        "asr_layernorm_fwd": [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _f, _vp, _vp, ctypes.c_long,
+                              _i, _i, _i, _vp],
+        "asr_mask_rows": [_vp, ctypes.c_long, _vp, _i, _i, _i, _vp],
         "asr_fbank_num_frames": [_vp, _i],
         "asr_fbank_feature_dim": [_vp],
         "asr_fbank_host_tables": [_vp, _vp, _vp, _vp],
@@ -892,6 +905,259 @@ class Conv1d:
         conv1d_fwd(x, self.W, self.b, out, T, B, self.desc, lengths=lengths, out_lengths=oln, stream=stream or 0)
         self._keep = lengths
         return out, T_out, oln
+
+
+# ------------------------------------------------- attention and LayerNorm
+ATTN_KEY_BLOCK = 64   # ASR_ATTN_KEY_BLOCK
+
+
+class AttnDesc(ctypes.Structure):
+    """asr_attn_desc (include/asr_amd.h)."""
+    _fields_ = [("heads", _i), ("head_dim", _i), ("scale", _f), ("chunk", _i), ("left", _i), ("right", _i)]
+
+
+def attn_desc(heads: int, head_dim: int, scale: float = 0.0, chunk: int = 1, left: int = -1,
+              right: int = -1) -> AttnDesc:
+    """An AttnDesc from keywords: scale 0 = 1/sqrt(head_dim); query p sees key r
+    iff p//chunk - left <= r//chunk <= p//chunk + right (-1 drops that side)."""
+    return AttnDesc(heads, head_dim, scale, chunk, left, right)
+
+
+class ColumnView:
+    """Columns [col, ...) of the rows of a device matrix, without owning them:
+    ptr addresses (row 0, column col), cols stays the owner's row stride."""
+
+    def __init__(self, m, col: int):
+        assert 0 <= col < m.cols, (col, m.cols)
+        self.ptr, self.rows, self.cols, self._keep = m.ptr + 4 * col, m.rows, m.cols, m
+
+
+def _device_lengths_or_none(lengths):
+    if lengths is None or isinstance(lengths, DeviceBytes):
+        return lengths
+    return device_lengths(lengths)
+
+
+def attention_fwd(q, k, v, out, Tq: int, Tk: int, B: int, desc: AttnDesc, lengths: Optional[DeviceBytes] = None,
+                  q_pos0: int = 0, k_pos0: int = 0, ldq: Optional[int] = None, ldk: Optional[int] = None,
+                  ldv: Optional[int] = None, ldo: Optional[int] = None, stream: int = 0):
+    """softmax(Q K^T scale) V per head over time (asr_attention_fwd): q, out
+    [Tq*B, >= E] and k, v [Tk*B, >= E] time-major, E = heads*head_dim; anything
+    with .ptr and .cols (the row stride unless ld* is given), so q, k and v may
+    be ColumnViews of one [T*B, 3E] projection buffer; lengths from
+    device_lengths(), in absolute frames."""
+    ld = lambda m, given: int(m.cols if given is None else given)   # noqa: E731
+    check(lib().asr_attention_fwd(ctypes.byref(desc), q.ptr, ld(q, ldq), k.ptr, ld(k, ldk), v.ptr, ld(v, ldv),
+                                  lengths.ptr if lengths is not None else None, out.ptr, ld(out, ldo),
+                                  Tq, q_pos0, Tk, k_pos0, B, stream), "asr_attention_fwd")
+    return out
+
+
+def layernorm_fwd(x, out, T: int, B: int, N: int, gamma=None, beta=None, eps: float = 1e-5, res=None,
+                  lengths: Optional[DeviceBytes] = None, stream: int = 0):
+    """LayerNorm over the first N columns of each row of x (+ res) into out
+    (asr_layernorm_fwd); x, res, out: anything with .ptr and .cols (the row
+    stride); out may be x or res; rows past lengths become zeros."""
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_layernorm_fwd(x.ptr, x.cols, opt(res), res.cols if res is not None else 0, opt(gamma),
+                                  opt(beta), eps, opt(lengths), out.ptr, out.cols, T, B, N, stream),
+          "asr_layernorm_fwd")
+    return out
+
+
+def mask_rows(x, T: int, B: int, N: int, lengths: Optional[DeviceBytes], stream: int = 0):
+    """Zero the first N columns of rows t >= len[b] of x in place (asr_mask_rows)."""
+    check(lib().asr_mask_rows(x.ptr, x.cols, lengths.ptr if lengths is not None else None, T, B, N, stream),
+          "asr_mask_rows")
+    return x
+
+
+class _Scratch:
+    """Device buffers of a layer, kept between calls and reallocated on a new shape."""
+
+    def __init__(self):
+        self._bufs = {}
+
+    def get(self, name: str, rows: int, cols: int) -> DeviceMatrix:
+        m = self._bufs.get(name)
+        if m is None or (m.rows, m.cols) != (rows, cols):
+            m = self._bufs[name] = DeviceMatrix(rows, cols)
+        return m
+
+
+class LayerNorm:
+    """torch.nn.LayerNorm(N) over the columns of time-major rows for inference
+    on asr_layernorm_fwd; weight / bias [N] or None (1 / 0)."""
+
+    def __init__(self, N: int, eps: float = 1e-5, weight=None, bias=None):
+        self.N, self.eps = int(N), float(eps)
+        up = lambda a: None if a is None else DeviceMatrix.from_numpy(   # noqa: E731
+            np.asarray(a, np.float32).reshape(self.N, 1))
+        self.gamma, self.beta = up(weight), up(bias)
+        self._keep = None
+
+    @classmethod
+    def from_torch(cls, ln) -> "LayerNorm":
+        shape = tuple(ln.normalized_shape)
+        if len(shape) != 1:
+            raise ValueError(f"LayerNorm.from_torch: normalized_shape {shape} is not one dimension")
+        host = lambda p: None if p is None else p.detach().cpu().float().numpy()   # noqa: E731
+        return cls(shape[0], ln.eps, host(getattr(ln, "weight", None)), host(getattr(ln, "bias", None)))
+
+    def forward(self, x, T: int, B: int, lengths=None, res=None, out=None, stream: int = 0):
+        """LayerNorm(x + res) (res None: of x) of time-major x [T*B, N]; lengths
+        None, a sequence of B counts or a DeviceBytes of int32 [B]: rows past
+        them are zeros.  out defaults to a new DeviceMatrix; it may be x or res."""
+        lengths = _device_lengths_or_none(lengths)
+        out = DeviceMatrix(T * B, self.N) if out is None else out
+        layernorm_fwd(x, out, T, B, self.N, self.gamma, self.beta, self.eps, res, lengths, stream or 0)
+        self._keep = lengths
+        return out
+
+
+class MultiheadAttention:
+    """torch.nn.MultiheadAttention(E, heads) as self-attention for inference:
+    asr_linear_fwd to [T*B, 3E], one asr_attention_fwd on its three column
+    ranges, asr_linear_fwd; time-major, no arithmetic here.  w_in [E, 3E] and
+    w_out [E, E] in this library's [in][out] layout, b_in [3E], b_out [E]
+    (zeros if None).  chunk / left / right: the window of asr_attn_desc
+    (defaults: full attention).  Dropout is ignored."""
+
+    def __init__(self, embed_dim: int, heads: int, w_in=None, b_in=None, w_out=None, b_out=None, chunk: int = 1,
+                 left: int = -1, right: int = -1):
+        E = int(embed_dim)
+        if heads <= 0 or E <= 0 or E % heads:
+            raise ValueError(f"MultiheadAttention: embed_dim {E} is not a multiple of heads {heads}")
+        hd = E // heads
+        if hd % 4 or hd > 128 or E > 4096:
+            raise ValueError(f"MultiheadAttention: head_dim {hd} (% 4 == 0, <= 128) / embed_dim {E} (<= 4096) "
+                             "outside what asr_attention_fwd takes")
+        if chunk < 1 or left < -1 or right < -1:
+            raise ValueError(f"MultiheadAttention: window chunk {chunk}, left {left}, right {right}")
+        self.E, self.heads = E, heads
+        self.desc = attn_desc(heads, hd, 0.0, chunk, left, right)
+        arr = lambda a, shape: (np.zeros(shape, np.float32) if a is None   # noqa: E731
+                                else np.asarray(a, np.float32).reshape(shape))
+        self.w_in, self.b_in = DeviceMatrix.from_numpy(arr(w_in, (E, 3 * E))), DeviceMatrix.from_numpy(
+            arr(b_in, (3 * E, 1)))
+        self.w_out, self.b_out = DeviceMatrix.from_numpy(arr(w_out, (E, E))), DeviceMatrix.from_numpy(
+            arr(b_out, (E, 1)))
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_torch(mha):
+        """(w_in [E, 3E], b_in [3E], w_out [E, E], b_out [E]) float32 from a
+        torch.nn.MultiheadAttention: in_proj_weight [3E, E] and out_proj.weight
+        [E, E] transposed into the [in][out] layout.  No device call."""
+        E = mha.embed_dim
+        if not getattr(mha, "_qkv_same_embed_dim", mha.kdim == E and mha.vdim == E):
+            raise ValueError("MultiheadAttention.from_torch: kdim / vdim != embed_dim is not supported")
+        if mha.bias_k is not None or mha.bias_v is not None or mha.add_zero_attn:
+            raise ValueError("MultiheadAttention.from_torch: bias_k / bias_v / add_zero_attn are not supported")
+        host = lambda p: p.detach().cpu().float().numpy()   # noqa: E731
+        w_in = np.ascontiguousarray(host(mha.in_proj_weight).T)
+        b_in = host(mha.in_proj_bias) if mha.in_proj_bias is not None else np.zeros(3 * E, np.float32)
+        w_out = np.ascontiguousarray(host(mha.out_proj.weight).T)
+        b_out = host(mha.out_proj.bias) if mha.out_proj.bias is not None else np.zeros(E, np.float32)
+        return w_in, b_in, w_out, b_out
+
+    @classmethod
+    def from_torch(cls, mha, chunk: int = 1, left: int = -1, right: int = -1) -> "MultiheadAttention":
+        w_in, b_in, w_out, b_out = cls.pack_torch(mha)
+        return cls(mha.embed_dim, mha.num_heads, w_in, b_in, w_out, b_out, chunk, left, right)
+
+    def forward(self, x, T: int, B: int, lengths=None, out=None, zero_padding: bool = True, stream: int = 0):
+        """Self-attention of time-major x [T*B, E]; lengths None, a sequence of B
+        counts or a DeviceBytes of int32 [B].  Returns out [T*B, E] (a buffer of
+        this layer, reused by its next call, unless given); rows past the lengths
+        are zeros (asr_mask_rows after the output projection) unless
+        zero_padding is False, in which case they hold the output bias."""
+        E, M, st = self.E, T * B, stream or 0
+        lengths = _device_lengths_or_none(lengths)
+        qkv = self._scratch.get("qkv", M, 3 * E)
+        ctx = self._scratch.get("ctx", M, E)
+        out = self._scratch.get("out", M, E) if out is None else out
+        linear_fwd(x, self.w_in, self.b_in, qkv, EPI_BIAS, st)
+        attention_fwd(ColumnView(qkv, 0), ColumnView(qkv, E), ColumnView(qkv, 2 * E), ctx, T, T, B, self.desc,
+                      lengths=lengths, stream=st)
+        linear_fwd(ctx, self.w_out, self.b_out, out, EPI_BIAS, st)
+        if zero_padding and lengths is not None:
+            mask_rows(out, T, B, E, lengths, st)
+        self._keep = lengths
+        return out
+
+
+class TransformerEncoderLayer:
+    """torch.nn.TransformerEncoderLayer (ReLU feed-forward, norm_first either
+    way) for inference, time-major: MultiheadAttention, two LayerNorms and two
+    asr_linear_fwd (the first with bias + ReLU fused).  Post-norm uses the
+    fused residual of asr_layernorm_fwd, pre-norm asr_matadd.  Dropout is
+    ignored."""
+
+    def __init__(self, attn: MultiheadAttention, norm1: LayerNorm, norm2: LayerNorm, w1, b1, w2, b2,
+                 norm_first: bool = False):
+        E = attn.E
+        w1, w2 = np.asarray(w1, np.float32), np.asarray(w2, np.float32)
+        F = w1.shape[1]
+        assert w1.shape == (E, F) and w2.shape == (F, E), (w1.shape, w2.shape)
+        self.E, self.F, self.norm_first = E, F, bool(norm_first)
+        self.attn, self.norm1, self.norm2 = attn, norm1, norm2
+        self.w1, self.w2 = DeviceMatrix.from_numpy(w1), DeviceMatrix.from_numpy(w2)
+        self.b1 = DeviceMatrix.from_numpy(np.asarray(b1, np.float32).reshape(F, 1))
+        self.b2 = DeviceMatrix.from_numpy(np.asarray(b2, np.float32).reshape(E, 1))
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_torch(layer):
+        """(w1 [E, F], b1 [F], w2 [F, E], b2 [E]) float32 of the feed-forward
+        of a torch.nn.TransformerEncoderLayer, in the [in][out] layout; raises
+        ValueError for an activation other than ReLU.  No device call."""
+        act = layer.activation
+        name = getattr(act, "__name__", type(act).__name__).lower()
+        if name != "relu":
+            raise ValueError(f"TransformerEncoderLayer.from_torch: activation {name!r} is not supported (ReLU only)")
+        host = lambda p: p.detach().cpu().float().numpy()   # noqa: E731
+        bias = lambda lin: (host(lin.bias) if lin.bias is not None   # noqa: E731
+                            else np.zeros(lin.out_features, np.float32))
+        return (np.ascontiguousarray(host(layer.linear1.weight).T), bias(layer.linear1),
+                np.ascontiguousarray(host(layer.linear2.weight).T), bias(layer.linear2))
+
+    @classmethod
+    def from_torch(cls, layer, chunk: int = 1, left: int = -1, right: int = -1) -> "TransformerEncoderLayer":
+        w1, b1, w2, b2 = cls.pack_torch(layer)
+        return cls(MultiheadAttention.from_torch(layer.self_attn, chunk, left, right),
+                   LayerNorm.from_torch(layer.norm1), LayerNorm.from_torch(layer.norm2), w1, b1, w2, b2,
+                   layer.norm_first)
+
+    def forward(self, x, T: int, B: int, lengths=None, stream: int = 0) -> DeviceMatrix:
+        """x time-major [T*B, E]; lengths None, a sequence of B counts or a
+        DeviceBytes of int32 [B] (e.g. Conv1d.forward's out_lengths).  Returns a
+        new DeviceMatrix [T*B, E] with zero rows past the lengths."""
+        E, F, M, st = self.E, self.F, T * B, stream or 0
+        lengths = _device_lengths_or_none(lengths)
+        sc = self._scratch
+        h, ff = sc.get("h", M, E), sc.get("ff", M, F)
+        out = DeviceMatrix(M, E)
+        if self.norm_first:
+            n = sc.get("n", M, E)
+            self.norm1.forward(x, T, B, lengths, out=n, stream=st)
+            a = self.attn.forward(n, T, B, lengths, zero_padding=False, stream=st)
+            check(lib().asr_matadd(x.ptr, a.ptr, h.ptr, M, E, 1.0, st), "asr_matadd")
+            self.norm2.forward(h, T, B, lengths, out=n, stream=st)
+            linear_fwd(n, self.w1, self.b1, ff, EPI_BIAS_RELU, st)
+            linear_fwd(ff, self.w2, self.b2, n, EPI_BIAS, st)
+            check(lib().asr_matadd(h.ptr, n.ptr, out.ptr, M, E, 1.0, st), "asr_matadd")
+            if lengths is not None:
+                mask_rows(out, T, B, E, lengths, st)
+        else:
+            a = self.attn.forward(x, T, B, lengths, zero_padding=False, stream=st)
+            self.norm1.forward(a, T, B, lengths, res=x, out=h, stream=st)
+            f2 = sc.get("f2", M, E)
+            linear_fwd(h, self.w1, self.b1, ff, EPI_BIAS_RELU, st)
+            linear_fwd(ff, self.w2, self.b2, f2, EPI_BIAS, st)
+            self.norm2.forward(f2, T, B, lengths, res=h, out=out, stream=st)
+        self._keep = lengths
+        return out
 
 
 # ----------------------------------------------------------------- front end

@@ -370,6 +370,97 @@ int asr_conv1d_fwd(const asr_conv1d_desc* d, const float* d_x, long ldx, const i
                    const float* d_W, const float* d_b, float* d_out, long ldo,
                    int32_t* d_out_lengths, int T, int B, asr_stream_t s);
 
+/* Scaled dot-product self-attention over time, all heads in one launch —
+ * softmax(Q K^T * scale) V per head with per-utterance lengths and an optional
+ * chunked window: the hot path of torch.nn.MultiheadAttention in Transformer /
+ * Conformer CTC encoders (the projections are asr_linear_fwd, the residual
+ * asr_matadd, the norm asr_layernorm_fwd); no reference member.  No workspace:
+ * the score matrix is never materialised (online softmax over key blocks).
+ * Layout, time-major as everywhere: row i*B + b of d_q holds heads*head_dim
+ * floats, row stride ldq, head h at columns [h*head_dim, (h+1)*head_dim); d_k
+ * and d_v have Tk frames (strides ldk, ldv), d_out has Tq frames (stride ldo);
+ * columns >= heads*head_dim of a row of d_out are not touched.  Q, K and V may
+ * be three column ranges of one [T*B, 3E] projection buffer (ld = 3E, pointers
+ * offset by E).  d_out must not overlap Q, K or V.
+ * Positions and mask: query row i stands at absolute frame p = q_pos0 + i, key
+ * row j at r = k_pos0 + j (a plain call: both 0, Tq == Tk).  Key r exists for
+ * utterance b iff 0 <= j < Tk and r < len[b]; d_lengths is device int32 [B] in
+ * ABSOLUTE frames, negative values clamp to 0, NULL = no bound.  Query p sees
+ * key r iff the key exists and
+ *   p / chunk - left <= r / chunk <= p / chunk + right      (integer division),
+ * a -1 dropping that side: left = right = -1 is full attention, chunk = 1 with
+ * right = 0 is causal.  Query rows with p >= len[b], and rows that see no key,
+ * are exact zeros (the zero-past-length convention of asr_lstm_fwd and
+ * asr_conv1d_fwd).  K and V of keys that do not exist are selected as zero
+ * where they are fetched, never multiplied by a mask: padding rows of K and V,
+ * and Q rows past the length, may hold NaN.
+ * Arithmetic: Q K^T and P V on v_mfma_f32_16x16x4_f32, the softmax in fp32 with
+ * a running maximum (online softmax).  Always fp32, whatever
+ * asr_set_dense_arith says.  scale = 0 means 1 / sqrt(head_dim).
+ * Block grid: keys are walked in ascending blocks of ASR_ATTN_KEY_BLOCK frames
+ * aligned on absolute positions (block n = frames [64 n, 64 n + 64)); a block
+ * in which a query sees nothing leaves that query's state bit-unchanged.  So an
+ * output row's bits depend only on its own query, the keys and values it sees
+ * at their absolute positions, and the descriptor: never on Tq, Tk, B, the
+ * row's position in the buffer, q_pos0, k_pos0, other utterances, strides or
+ * pointer alignment (16-byte loads of aligned rows give the scalar path's
+ * bits).  A streaming caller that keeps a K/V cache of the last left*chunk
+ * frames and calls chunk by chunk (q_pos0 = first frame of the chunk, k_pos0 =
+ * first cached frame) gets the whole call's bits.
+ * One launch, asynchronous on s, no allocation, no host sync.  Checks, in this
+ * order, all before any HIP call — ASR_ERR_ARG: a NULL descriptor, d_q, d_k,
+ * d_v or d_out; non-positive Tq, Tk, B, heads, head_dim or chunk; left or
+ * right < -1; negative q_pos0 or k_pos0; a stride below heads*head_dim; a scale
+ * that is not finite or < 0.  ASR_ERR_UNSUPPORTED: head_dim % 4 != 0 or > 128;
+ * heads*head_dim > 4096; heads or B > 65535 (grid dimensions); q_pos0 + Tq or
+ * k_pos0 + Tk > INT_MAX - 64; Tq*B or Tk*B > INT_MAX.
+ * Not built: relative-position or rotary terms and additive score biases;
+ * the attention probabilities as an output; cross-attention with different
+ * batch sizes; a split-bf16 variant; training. */
+#define ASR_ATTN_KEY_BLOCK 64
+typedef struct asr_attn_desc {
+    int heads, head_dim;   /* head_dim % 4 == 0, 4 .. 128; heads*head_dim <= 4096 */
+    float scale;           /* 0 = 1/sqrt(head_dim); else finite, > 0 */
+    int chunk;             /* >= 1: mask granularity in frames (1 = per frame) */
+    int left, right;       /* chunks visible before / after the query's own; -1 = unlimited;
+                              right = 0 with chunk = 1: causal */
+} asr_attn_desc;
+int asr_attention_fwd(const asr_attn_desc* d, const float* d_q, long ldq, const float* d_k, long ldk,
+                      const float* d_v, long ldv, const int32_t* d_lengths, float* d_out, long ldo,
+                      int Tq, int q_pos0, int Tk, int k_pos0, int B, asr_stream_t s);
+
+/* LayerNorm over the N columns of each row of a time-major [T*B, N] buffer,
+ * with an optional fused residual (torch.nn.LayerNorm semantics):
+ *   v = x + res (x when d_res is NULL); mean = sum(v) / N;
+ *   var = sum((v - mean)^2) / N   (two-pass, biased, as torch; the fp32 mean is
+ *   refined once by the mean of the centred values, so a row far from zero
+ *   (1000 +- 1) is centred as accurately as one around zero);
+ *   out = ((v - mean) * (1 / sqrt(var + eps))) * gamma + beta,
+ * d_gamma / d_beta [N], NULL = 1 / 0.  Row strides ldx, ldr, ldo >= N; columns
+ * >= N of d_out are not touched.  Rows t >= len[b] are zeros whatever x holds
+ * (d_lengths device int32 [B], clamped to [0, T], NULL = all rows).  d_out may
+ * be exactly d_x or d_res (in place).  One wave per row; the sums are a fixed
+ * tree (a lane's columns l, l + 64, ... ascending, then the butterfly over the
+ * lanes, as asr_lm_score's), so a row's bits never depend on T, B or the
+ * row's position.  fp32 always.  GELU / Swish / GLU feed-forward activations
+ * are not built (asr_linear_fwd fuses ReLU).
+ * One launch, asynchronous on s.  Checks, in this order, before any HIP call —
+ * ASR_ERR_ARG: NULL d_x or d_out; non-positive T, B or N; a stride < N; eps not
+ * finite or < 0.  ASR_ERR_UNSUPPORTED: N > 4096; T*B > INT_MAX. */
+int asr_layernorm_fwd(const float* d_x, long ldx, const float* d_res, long ldr, const float* d_gamma,
+                      const float* d_beta, float eps, const int32_t* d_lengths, float* d_out, long ldo,
+                      int T, int B, int N, asr_stream_t s);
+
+/* Zero columns [0, N) of the rows t >= len[b] of a time-major [T*B, >= N]
+ * buffer in place (row stride ldx; d_lengths device int32 [B], clamped to
+ * [0, T]; NULL: nothing to do, no launch).  It gives the output of a
+ * projection with a bias (asr_linear_fwd after asr_attention_fwd, or the
+ * residual sum of a pre-norm Transformer layer) the zero-past-length
+ * convention of the other layers; the rows may hold NaN before.  One launch,
+ * asynchronous on s.  ASR_ERR_ARG: NULL d_x, non-positive T, B or N, ldx < N;
+ * ASR_ERR_UNSUPPORTED: T*B > INT_MAX. */
+int asr_mask_rows(float* d_x, long ldx, const int32_t* d_lengths, int T, int B, int N, asr_stream_t s);
+
 /* ---- CTC prefix beam search: replaces CTCBeamSearch (CTCBeamSearch.h:107-150,
  *      CTCBeamSearch.cu:220-312) with the semantics of the CPU decoder
  *      CTCBeamSearch.cpp:50-187 (fixes F1-F3, fp64 log domain). ---- */
