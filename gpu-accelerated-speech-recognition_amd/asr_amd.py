@@ -36,6 +36,10 @@ include/asr_amd.h — it contains no arithmetic of its own:
     NGramLM.from_arpa(path).score(token_lists) / CTCDecoder.lm_rescore(...)
                                           back-off n-gram LM scoring and n-best
                                           rescoring (asr_lm_*); no reference member
+    CTCLMDecoder(V, beam_width, lm, tok_of_label, alpha, beta).decode(emis)
+                                          beam search with the n-gram LM fused into
+                                          every prune (asr_ctc_lm_*); no reference
+                                          member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -86,6 +90,8 @@ EXPORTS = [
     "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
     "asr_lm_token_string", "asr_lm_score_host", "asr_lm_upload", "asr_lm_score",
     "asr_edit_distance", "asr_edit_distance_host", "asr_nbest_mbr", "asr_nbest_mbr_host",
+    "asr_ctc_lm_create", "asr_ctc_lm_destroy", "asr_ctc_lm_decode", "asr_ctc_lm_decode_host",
+    "asr_ctc_lm_get_beams", "asr_ctc_lm_get_best", "asr_ctc_lm_host_gaps",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -218,6 +224,13 @@ def lib() -> ctypes.CDLL:
                                    _vp],
         "asr_nbest_mbr": [_vp, ctypes.c_long, _vp, _i, _i, _vp, _i, _i, _vp, _vp, ctypes.c_long, _vp, _vp, _vp],
         "asr_nbest_mbr_host": [_vp, ctypes.c_long, _vp, _i, _i, _vp, _i, _i, _vp, _vp, ctypes.c_long, _vp, _vp],
+        "asr_ctc_lm_create": [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _i, _i, ctypes.POINTER(_vp)],
+        "asr_ctc_lm_destroy": [_vp],
+        "asr_ctc_lm_decode": [_vp, _vp, _i, _i, ctypes.c_long, ctypes.c_long, _vp, _i, _vp],
+        "asr_ctc_lm_decode_host": [_vp, _vp, _i, _i, ctypes.c_long, ctypes.c_long, _vp, _i],
+        "asr_ctc_lm_get_beams": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_ctc_lm_get_best": [_vp, _vp, _i, _vp, _vp],
+        "asr_ctc_lm_host_gaps": [_vp, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -1765,9 +1778,133 @@ class NGramLM:
                 return [lookup(w) for w in "".join(labels[c] for c in hyp).split(space) if w != ""]
         return mapper
 
+    def label_tokens(self, labels: Sequence[str]) -> np.ndarray:
+        """int32 [V]: every label's string looked up as a token of this model
+        (CTCLMDecoder's tok_of_label); the empty string or an absent token
+        gives -1 (an OOV)."""
+        return np.array([self.token_id(s) if s != "" else -1 for s in labels], dtype=np.int32)
+
     def close(self) -> None:
         if getattr(self, "h", None):
             lib().asr_lm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CTCLMDecoder:
+    """Handle over asr_ctc_lm_*: the beam search with the n-gram LM fused into
+    every prune (the semantics are in include/asr_amd.h).  lm is an NGramLM
+    that must outlive this decoder (upload() it before a device decode);
+    tok_of_label[V] is the LM token of every label (NGramLM.label_tokens).
+    No arithmetic here."""
+
+    def __init__(self, V: int, beam_width: int, lm: NGramLM, tok_of_label: Sequence[int], alpha: float, beta: float,
+                 blank_id: int = 0, bos: bool = True, eos: bool = False, top_n: int = 0, max_states: int = 0,
+                 codes: Optional[Sequence[int]] = None):
+        self.V, self.beam, self.blank = V, beam_width, blank_id
+        self.lm = lm   # keeps the LM handle alive
+        self.codes = None if codes is None else np.ascontiguousarray(codes, dtype=np.int32)
+        tok = np.ascontiguousarray(tok_of_label, dtype=np.int32)
+        if tok.shape != (V,):
+            raise ValueError(f"CTCLMDecoder: tok_of_label has shape {tok.shape}, not ({V},)")
+        flags = (ASR_LM_BOS if bos else 0) | (ASR_LM_EOS if eos else 0)
+        h = _vp()
+        check(lib().asr_ctc_lm_create(_ptr(self.codes) if self.codes is not None else None, V, beam_width, blank_id,
+                                      max_states, lm.h, _ptr(tok), alpha, beta, flags, top_n, ctypes.byref(h)),
+              "asr_ctc_lm_create")
+        self.h = h.value
+        self._emis: Optional[DeviceBytes] = None
+        self.T = self.B = 0
+
+    @staticmethod
+    def _lengths(lengths, B):
+        ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        if ln is not None:
+            assert ln.shape == (B,), (ln.shape, B)
+        return ln
+
+    def decode_device(self, d_emis: int, T: int, B: int, is_log: bool, stream: int = 0,
+                      lengths: Optional[Sequence[int]] = None, frame_stride: Optional[int] = None,
+                      utt_stride: Optional[int] = None) -> None:
+        """Decode device emissions: element (t, b, v) at d_emis[t*frame_stride +
+        b*utt_stride + v] (default time-major [T][B][V]); 1 <= lengths[b] <= T."""
+        fs = B * self.V if frame_stride is None else int(frame_stride)
+        us = self.V if utt_stride is None else int(utt_stride)
+        ln = self._lengths(lengths, B)
+        check(lib().asr_ctc_lm_decode(self.h, d_emis, T, B, fs, us, _ptr(ln) if ln is not None else None,
+                                      int(bool(is_log)), stream or None), "asr_ctc_lm_decode")
+        self.T, self.B = T, B
+
+    @staticmethod
+    def _shape(emis, batch_major):
+        if batch_major:
+            B, T, V = emis.shape
+            return T, B, V, V, T * V
+        T, B, V = emis.shape
+        return T, B, V, B * V, V
+
+    def decode(self, emis: np.ndarray, is_log: bool = False, stream: int = 0,
+               lengths: Optional[Sequence[int]] = None, batch_major: bool = False) -> None:
+        """Upload emissions (fp32 [T][B][V], or [B][T][V] with batch_major) and
+        enqueue the decode on the device."""
+        emis = np.ascontiguousarray(emis, dtype=np.float32)
+        T, B, V, fs, us = self._shape(emis, batch_major)
+        assert V == self.V, (V, self.V)
+        if self._emis is None or self._emis.nbytes < emis.nbytes:
+            self._emis = DeviceBytes(emis.nbytes)
+        check(lib().asr_memcpy_h2d(self._emis.ptr, _ptr(emis), emis.nbytes, stream), "asr_memcpy_h2d")
+        self.decode_device(self._emis.ptr, T, B, is_log, stream, lengths, fs, us)
+
+    def decode_host(self, emis: np.ndarray, is_log: bool = False, lengths: Optional[Sequence[int]] = None,
+                    batch_major: bool = False) -> None:
+        """The host twin (asr_ctc_lm_decode_host): one thread, no GPU."""
+        emis = np.ascontiguousarray(emis, dtype=np.float32)
+        T, B, V, fs, us = self._shape(emis, batch_major)
+        assert V == self.V, (V, self.V)
+        ln = self._lengths(lengths, B)
+        check(lib().asr_ctc_lm_decode_host(self.h, _ptr(emis), T, B, fs, us, _ptr(ln) if ln is not None else None,
+                                           int(bool(is_log))), "asr_ctc_lm_decode_host")
+        self.T, self.B = T, B
+
+    def beams(self, max_hyps: int) -> List[List[Tuple[List[int], float, float, float, int]]]:
+        """Ranked final beam (total desc, string asc) of every utterance of the
+        last decode: [(labels, total, ctc_logp, lm_log10, n_tokens)]."""
+        B, T = self.B, max(self.T, 1)
+        nh = np.zeros(max(B, 1), np.int32)
+        ln = np.zeros((B, max_hyps), np.int32)
+        lab = np.zeros((B, max_hyps, T), np.int32)
+        tot, ctc, lm = (np.zeros((B, max_hyps), np.float64) for _ in range(3))
+        nt = np.zeros((B, max_hyps), np.int32)
+        check(lib().asr_ctc_lm_get_beams(self.h, max_hyps, T, _ptr(nh), _ptr(ln), _ptr(lab), _ptr(tot), _ptr(ctc),
+                                         _ptr(lm), _ptr(nt)), "asr_ctc_lm_get_beams")
+        return [[(lab[b, k, :ln[b, k]].tolist(), float(tot[b, k]), float(ctc[b, k]), float(lm[b, k]), int(nt[b, k]))
+                 for k in range(min(nh[b], max_hyps))] for b in range(B)]
+
+    def host_gaps(self) -> np.ndarray:
+        """Per utterance of the last decode_host: the smallest relative gap
+        between two differing scores whose order decided something
+        (asr_ctc_lm_host_gaps)."""
+        g = np.zeros(max(self.B, 1), np.float64)
+        check(lib().asr_ctc_lm_host_gaps(self.h, _ptr(g)), "asr_ctc_lm_host_gaps")
+        return g[:self.B].copy()
+
+    def best(self) -> Tuple[List[List[int]], np.ndarray]:
+        """Best label sequence and total of every utterance."""
+        B, T = self.B, max(self.T, 1)
+        lab = np.zeros((max(B, 1), T), np.int32)
+        ln = np.zeros(max(B, 1), np.int32)
+        tot = np.zeros(max(B, 1), np.float64)
+        check(lib().asr_ctc_lm_get_best(self.h, _ptr(lab), T, _ptr(ln), _ptr(tot)), "asr_ctc_lm_get_best")
+        return [lab[b, :ln[b]].tolist() for b in range(B)], tot[:B].copy()
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib().asr_ctc_lm_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -2121,8 +2258,7 @@ class CTCBeamDecoder:
     num_processes=, log_probs_input=True).decode(probs[B,T,V], seq_lens)) on
     this library's decoder.  ctcdecode itself is not available here, so the
     search semantics are the reference C++ decoder's (CTCBeamSearch.cpp with
-    F1-F3), not ctcdecode's; no language model (model_path must
-    be None).  decode returns (beam_results [B, beam_width, T] int32 label
+    F1-F3), not ctcdecode's.  decode returns (beam_results [B, beam_width, T] int32 label
     ids, beam_scores [B, beam_width] float32 = -log p (lower is better),
     timesteps [B, beam_width, T] int32, out_lens [B, beam_width] int32);
     hypotheses beyond an utterance's final beam have length 0 and score +inf.
@@ -2134,17 +2270,43 @@ class CTCBeamDecoder:
     node table per decode, so it is on only with timesteps=True (the
     default, as ctcdecode always returns them); timesteps=False returns an
     all -1 array and decodes on the plain path.  probs may be a numpy array
-    or a torch tensor (a GPU tensor is decoded in place, no copy)."""
+    or a torch tensor (a GPU tensor is decoded in place, no copy).
+
+    With model_path (an ARPA file of a character, BPE or word-piece model whose
+    tokens are the label strings) the search is CTCLMDecoder's: the LM is fused
+    into every prune with alpha and beta, <s> as the first context and no
+    </s>, top_n = cutoff_top_n.  Every label is mapped to a token by
+    NGramLM.label_tokens; if no non-blank label is a token (a word-level
+    model) ValueError is raised: use CTCDecoder.lm_rescore with
+    NGramLM.label_mapper(labels, mode="word") instead.  beam_scores is then
+    -total (total = ctc + alpha ln10 lm_log10 + beta n_tokens) and timesteps is
+    all -1 (the fused search records none).  cutoff_prob other than 1.0 is not
+    implemented with a model (NotImplementedError).  Without model_path,
+    cutoff_top_n, cutoff_prob, alpha and beta are ignored, as before."""
 
     def __init__(self, labels: Sequence[str], model_path: Optional[str] = None, alpha: float = 0.0,
                  beta: float = 0.0, cutoff_top_n: int = 40, cutoff_prob: float = 1.0,
                  beam_width: int = 100, num_processes: int = 4, blank_id: int = 0,
                  log_probs_input: bool = False, timesteps: bool = True):
-        if model_path is not None:
-            raise NotImplementedError("language-model scoring is not supported")
         self.labels = list(labels)
         self.beam_width, self.blank_id, self.log_probs_input = beam_width, blank_id, log_probs_input
         self.track_timesteps = bool(timesteps)
+        self._lm: Optional[NGramLM] = None
+        self._fused: Optional[CTCLMDecoder] = None
+        self._dec: Optional[CTCDecoder] = None
+        if model_path is not None:
+            if cutoff_prob != 1.0:
+                raise NotImplementedError("cutoff_prob other than 1.0 is not implemented with a language model")
+            self._lm = NGramLM.from_arpa(model_path)
+            tok = self._lm.label_tokens(self.labels)
+            if not any(t >= 0 for v, t in enumerate(tok) if v != blank_id):
+                raise ValueError("no non-blank label is a token of the model (a word-level LM?): decode without "
+                                 "model_path and re-rank with CTCDecoder.lm_rescore(..., "
+                                 "lm.label_mapper(labels, mode=\"word\"))")
+            self._fused = CTCLMDecoder(len(self.labels), beam_width, self._lm, tok, alpha, beta, blank_id,
+                                       bos=self._lm.bos_id >= 0, eos=False, top_n=max(int(cutoff_top_n), 0))
+            self._uploaded = False
+            return
         self._dec = CTCDecoder(len(self.labels), beam_width, blank_id)
         self._dec.set_timesteps(self.track_timesteps)
 
@@ -2152,19 +2314,25 @@ class CTCBeamDecoder:
         B, T, V = (int(x) for x in probs.shape)
         lens = None if seq_lens is None else np.asarray(
             seq_lens.cpu().numpy() if hasattr(seq_lens, "cpu") else seq_lens, dtype=np.int32)
+        dec = self._fused if self._fused is not None else self._dec
+        if self._fused is not None and not self._uploaded:
+            self._lm.upload()
+            self._uploaded = True
         if hasattr(probs, "is_cuda") and probs.is_cuda:   # torch GPU tensor: zero-copy
             import torch
             p = probs if probs.dtype == torch.float32 else probs.float()
             if p.stride(2) != 1:   # the kernel reads a frame's V labels contiguously
                 p = p.contiguous()
-            self._dec.decode_device(p.data_ptr(), T, B, self.log_probs_input,
-                                    torch.cuda.current_stream().cuda_stream, lens,
-                                    p.stride(1), p.stride(0))
+            dec.decode_device(p.data_ptr(), T, B, self.log_probs_input,
+                              torch.cuda.current_stream().cuda_stream, lens,
+                              p.stride(1), p.stride(0))
         else:
             arr = probs.cpu().numpy() if hasattr(probs, "cpu") else np.asarray(probs)
-            self._dec.decode(arr, is_log=self.log_probs_input, lengths=lens, batch_major=True)
+            dec.decode(arr, is_log=self.log_probs_input, lengths=lens, batch_major=True)
         K = self.beam_width
-        if self.track_timesteps:
+        if self._fused is not None:
+            beams = [[(lab, total, None) for lab, total, _, _, _ in u] for u in self._fused.beams(256)]
+        elif self.track_timesteps:
             beams = self._dec.beams_ts(max_hyps=self._dec.config()[0])
         else:
             beams = [[(lab, lp, None) for lab, lp in u] for u in self._dec.beams(self._dec.config()[0])]

@@ -1061,6 +1061,123 @@ int asr_nbest_mbr_host(const int32_t* h_tokens, long ldt, const int32_t* h_lengt
                        const int32_t* h_group_start, int G, int max_hyps, const double* h_weight,
                        int32_t* h_dist, long ldm, double* h_risk, int32_t* h_best);
 
+/* ---- CTC beam search with n-gram LM shallow fusion ---------------------------
+ * No reference member is replaced (the reference decodes without a language
+ * model).  A decoder of its own (csrc/ctc_lm.hip): asr_ctc_* and
+ * its kernels are untouched.  Rescoring (CTCDecoder.lm_rescore) can only reorder
+ * what an acoustic-only beam kept; here the LM takes part in every prune.
+ *
+ * Search: the reference search of asr_ctc_* (states "q" / "q$",
+ * one initial state per symbol, extension and merge in the std::set fold order,
+ * fp64 lse, the final "q" / "q$" merge).  Only what the prune and the final
+ * ranking compare changes.
+ *
+ * Tokens: tok_of_label[V] maps every non-blank label to one LM token id (the
+ * blank's entry is ignored): character, BPE and word-piece models.  An id
+ * outside [0, vocab) is an OOV under asr_lm_*'s rule above (<unk> if present,
+ * else oov_log10, order 0, and it cuts the context).
+ *
+ * Per-prefix LM weight: aln10 = (double)alpha * 2.302585092994046, computed once
+ * on the host.  For a prefix q of labels c1..cn let v_i be the value of position
+ * i of the token row tok(c1)..tok(ci) under asr_lm_score's per-token rule, with
+ * ASR_LM_BOS as configured and ASR_LM_EOS off.  Then
+ *   W(empty) = 0.0    W(q+c) = W(q) + ((aln10 * v) + beta)
+ *   L(empty) = 0.0    L(q+c) = L(q) + v            n(q+c) = n(q) + 1
+ * every operation a rounded fp64 operation (no fma).  A prefix has one parent,
+ * so W, L and n depend on q only, never on the lineage that reached q.
+ *
+ * Prune: a state s is compared by fused(s) = pathScore(s) + W(prefix of s).
+ * Every state with fused >= the (beam_width+1)-th largest fused survives (ties
+ * at the cutoff all survive; all states survive when there are at most
+ * beam_width).  The merge of equal strings is unchanged: an lse fold of
+ * pathScore in the reference's set order.
+ *
+ * Label cutoff top_n (ctcdecode's cutoff_top_n): 0 or >= V-1 means every label.
+ * Otherwise C_t is the top_n non-blank labels with the largest emission (the
+ * fp32 values as given) at frame t of that utterance, the smaller label id
+ * first among equal values.  A non-blank label outside C_t takes part in no
+ * transition at t: neither the extension nor the repeat "qc"+c -> "qc".  Blank
+ * always takes part.  Frame 0's initial states are "$" and one per label of C_0.
+ *
+ * Final ranking: after the last prune and the "q" / "q$" merge,
+ * total(q) = ctc(q) + W(q); with ASR_LM_EOS, total(q) + (aln10 * v_eos) where
+ * v_eos is </s> scored after q (no beta for it, not counted in n, added into L).
+ * Ranked by (total descending, code string ascending); best is rank 0.  Per
+ * hypothesis: labels, total, ctc_logp, lm_log10 = L, n_tokens = n.  L is a
+ * left-to-right sum while asr_lm_score's total is a tree of 64 partial sums:
+ * the two agree to rounding only.
+ *
+ * With alpha = 0 and beta = 0, W is exactly 0.0 for every prefix and the search
+ * is asr_ctc_*'s.
+ *
+ * Limits: alpha >= 0 and finite, beta finite; V <= 4096; at most 255 candidate
+ * non-blank labels per frame (top_n ? min(top_n, V-1) : V-1); beam_width + 1 +
+ * ties <= 256, max_states as in asr_ctc_create (0 = automatic).  If the states
+ * that survive a prune exceed max_states, the fetch returns
+ * ASR_ERR_BEAM_OVERFLOW (the utterance then reports 0 hypotheses), for an
+ * automatic and an explicit capacity alike: there is no automatic re-decode.
+ * Per-utterance lengths are in [1, T].
+ *
+ * asr_ctc_lm_create: host only, no HIP call.  The LM handle must outlive the
+ * decoder handle.  Checks, in this order — ASR_ERR_ARG: out NULL; lm or
+ * tok_of_label NULL; V < 2, beam_width < 1, blank_id outside [0, V); alpha
+ * negative or not finite, beta not finite; lm_flags with other bits than
+ * ASR_LM_BOS | ASR_LM_EOS, top_n < 0, max_states < 0; a flag whose token the
+ * model lacks.  ASR_ERR_UNSUPPORTED: V > 4096.  ASR_ERR_ARG: two equal codes;
+ * 0 < max_states < beam_width + 1.  ASR_ERR_UNSUPPORTED: more than 255
+ * candidate labels; a capacity (rounded up to a multiple of 32) above 256.
+ *
+ * asr_ctc_lm_decode: device emissions, addressed as in asr_ctc_decode_ex
+ * (element (t, b, v) at d_emis[t*frame_stride + b*utt_stride + v]; h_lengths a
+ * host array, NULL = T for all).  Asynchronous on s: the label cutoff (one wave
+ * per frame and utterance, only with top_n) and the search (one workgroup per
+ * utterance).  The workspace is sized once per shape and reused while the next
+ * shape fits.  An utterance's results depend on its own frames only: never on
+ * its row, B, the strides or the other utterances.  d_emis must stay in place
+ * until the stream has run the decode.  A handle holds one decode at a time: the
+ * next decode (either kind) discards the results of the previous one, and waits
+ * for it first when it was queued on another stream.
+ * asr_ctc_lm_decode_host: the host twin — host emissions, plain C++ over
+ * std::map / std::set with the LM's host tables, one thread, no HIP call: the
+ * library's CPU path.  Labels, ranks and n_tokens equal the device's; scores
+ * differ only through exp / log / log1p.
+ * Checks of both, in this order, before any HIP call — ASR_ERR_ARG: h or the
+ * emissions NULL, T < 1, B < 1, a stride < 1, a length outside [1, T];
+ * ASR_ERR_STATE (asr_ctc_lm_decode only): the LM was not uploaded
+ * (asr_lm_upload).
+ *
+ * asr_ctc_lm_get_beams: the ranked final beam of every utterance of the last
+ * decode (either kind; waits for a device decode): h_n_hyps[B],
+ * h_lengths[B][max_hyps], h_labels[B][max_hyps][max_len], and, each may be
+ * NULL, h_total, h_ctc_logp, h_lm_log10 (fp64) and h_n_tokens [B][max_hyps].
+ * asr_ctc_lm_get_best: rank 0 only: h_labels[B][max_len], h_lengths[B],
+ * h_total[B] (may be NULL).  Checks, in this order — ASR_ERR_ARG: h NULL,
+ * max_hyps < 1, max_len < 1, h_n_hyps, h_lengths or h_labels NULL;
+ * ASR_ERR_STATE: no decode yet on this handle.  ASR_ERR_BEAM_OVERFLOW as above
+ * (the other utterances' results are written).
+ * asr_ctc_lm_host_gaps: h_gap[B], per utterance of the last HOST decode, the
+ * smallest relative distance |x - y| / max(1, |x|, |y|) it met between two
+ * finite scores that differ and whose order decides something: at every prune
+ * the cutoff against every other fused score, and adjacent final totals
+ * (+inf: none met).  A caller comparing two implementations learns from it
+ * whether a difference in ranks can be rounding.  ASR_ERR_ARG: h or h_gap NULL;
+ * ASR_ERR_STATE: the last decode on this handle was not a host decode.
+ * asr_ctc_lm_destroy: ASR_ERR_ARG for NULL. */
+typedef struct asr_ctc_lm asr_ctc_lm_t;
+int asr_ctc_lm_create(const int32_t* codes, int V, int beam_width, int blank_id, int max_states,
+                      const asr_lm_t* lm, const int32_t* tok_of_label, float alpha, float beta, int lm_flags,
+                      int top_n, asr_ctc_lm_t** out);
+int asr_ctc_lm_destroy(asr_ctc_lm_t* h);
+int asr_ctc_lm_decode(asr_ctc_lm_t* h, const float* d_emis, int T, int B, long frame_stride, long utt_stride,
+                      const int32_t* h_lengths, int is_log, asr_stream_t s);
+int asr_ctc_lm_decode_host(asr_ctc_lm_t* h, const float* h_emis, int T, int B, long frame_stride,
+                           long utt_stride, const int32_t* h_lengths, int is_log);
+int asr_ctc_lm_get_beams(asr_ctc_lm_t* h, int max_hyps, int max_len, int32_t* h_n_hyps, int32_t* h_lengths,
+                         int32_t* h_labels, double* h_total, double* h_ctc_logp, double* h_lm_log10,
+                         int32_t* h_n_tokens);
+int asr_ctc_lm_get_best(asr_ctc_lm_t* h, int32_t* h_labels, int max_len, int32_t* h_lengths, double* h_total);
+int asr_ctc_lm_host_gaps(asr_ctc_lm_t* h, double* h_gap);
+
 #ifdef __cplusplus
 }
 #endif
