@@ -23,12 +23,16 @@
 //     barriers compile away), from the floor G; when fewer than K keys reach
 //     G every label is visited and every column-1 fold done (exact, rare).
 // The kernel is small (no per-wave column groups, no staging arrays for other
-// waves): ~80 VGPRs and ~13 KB of LDS at beam <= 56, so a CU holds a dozen
+// waves): 128 VGPRs and 9.9 KB of LDS at beam <= 56, so a CU holds 16
 // utterances and keeps its SIMDs busy where the workgroup kernel leaves them
 // waiting on barriers and LDS round trips.
+//
+// The selection (wave_kth_select) and the argument why its passes on the
+// keys' high words are exact are in ctc_wave_select.h.
 // ============================================================================
 #pragma once
 #include "ctc_beam_kernel.inc"
+#include "ctc_wave_select.h"
 
 namespace asr {
 
@@ -137,7 +141,7 @@ struct WKeys {
             f(R.k1[k]);
 #pragma unroll
             for (int j = 0; j < WNL; j++)
-                if (j < nl) f(R.kx[k][j]);
+                f(R.kx[k][j]);   // j >= nl: key 0, in no range
         }
         for (uint64_t m = rest; m; m &= m - 1ull) {   // uniform loop
             const int c = __builtin_ctzll(m);
@@ -154,78 +158,6 @@ struct WKeys {
         return (!taken && base > -INFINITY) ? asr_d2key(base + ec) : 0ull;
     }
 };
-
-// The need-th largest key as a threshold tau (survivors: keys >= tau), one
-// wave: kth_select_all's 64-bin passes (keys in [lo, hi] counted per bin,
-// largest keys in lane 0; the bin holding the need-th key is split next)
-// over ONE histogram — the wave reads its 64 counts and zeroes them in
-// program order, so no rotation and no barrier.  Returns false when fewer
-// than need keys are >= lb.  ktop: top of the first pass's highest
-// non-empty bin (a bound of the best key).
-// h2 (ASR_CTC_HIST2): a second copy of the histogram for the odd lanes
-// (same-bin atomics of one instruction split over two words), bin b at word
-// (b + 16) & 63 so that the copies' words of one bin sit in different banks.
-template <class KS>
-__device__ __forceinline__ bool wave_kth_select(const KS& keys, int need, uint64_t lb, uint64_t kmax,
-                                                uint32_t* h, uint64_t& tau, uint64_t& ktop, int& err,
-                                                uint32_t* h2 = nullptr, uint64_t* npass = nullptr) {
-    const int lane = threadIdx.x & 63;
-    if (kmax < lb) return false;
-    uint64_t lo = lb, hi = kmax;   // inclusive range that holds the answer
-    uint32_t* const hs = (h2 && (lane & 1)) ? h2 : h;
-    const uint32_t rot = (h2 && (lane & 1)) ? 16u : 0u;
-    for (int pass = 0; pass < 12; pass++) {
-        const uint64_t span = hi - lo;
-        const int top = span ? 63 - __clzll((long long)span) : 0;
-        const int sh = top > 5 ? top - 5 : 0;   // span >> sh < 64
-        keys.each([&](uint64_t x) {
-            const uint64_t d = x - lo;   // x in [lo, hi] <=> x - lo <= span (unsigned)
-            if (d <= span) atomicAdd(&hs[(63u - (uint32_t)(d >> sh) + rot) & 63u], 1u);
-        });
-        uint32_t c = h[lane];
-        h[lane] = 0u;
-        if (h2) {
-            c += h2[(lane + 16) & 63];
-            h2[(lane + 16) & 63] = 0u;
-        }
-        const uint32_t S = wave_incl_scan(c);
-        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)S, 63);
-        if (npass) {   // diagnostic counters: passes, keys counted in the first pass
-            npass[0]++;
-            if (pass == 0) npass[1] += total;
-        }
-        if (pass == 0) {   // highest non-empty bin
-            const uint64_t nz = __ballot(c != 0u);
-            if (nz) {
-                const int Lz = __builtin_ctzll(nz);
-                const uint64_t t0 = lo + ((uint64_t)(64 - Lz) << sh) - 1ull;
-                ktop = (t0 > hi || t0 < lo) ? hi : t0;
-            }
-        }
-        if (total < (uint32_t)need) {
-            if (pass == 0) return false;   // fewer than need keys >= the floor
-            err = 1;
-            tau = lo;
-            return true;
-        }
-        const int L = __builtin_ctzll(__ballot(S >= (uint32_t)need));
-        const uint32_t cd = (uint32_t)__builtin_amdgcn_readlane((int)c, L);
-        const uint32_t SL = (uint32_t)__builtin_amdgcn_readlane((int)S, L);
-        const uint64_t b0 = lo + ((uint64_t)(63 - L) << sh);
-        uint64_t b1 = b0 + ((1ull << sh) - 1ull);
-        if (b1 > hi || b1 < b0) b1 = hi;
-        need -= (int)(SL - cd);
-        if ((int)cd == need || sh == 0 || b1 == b0) {   // the whole bin survives / one key value
-            tau = b0;
-            return true;
-        }
-        lo = b0;
-        hi = b1;
-    }
-    err = 1;
-    tau = lo;
-    return true;
-}
 
 // Child-mask bit of label `lab` set in a mask shared with other lanes (the
 // bits set into one mask are distinct: 32-bit adds, see set_label_bit).
@@ -408,12 +340,15 @@ void ctc_wave_kernel(CtcArgs a) {
         const double smaxS = asr_key2d(best_state);
         // the frame's largest log emission: a wave max over the label lanes
         const double smaxU = smaxS + asr_key2d(lds<uint64_t>(L::EMAX)[si]);
-        const uint64_t kmaxU = asr_d2key(smaxU + 1.1);
+        // (a bound rounded up to an all-ones low word: ctc_wave_select.h)
+        const uint64_t kmaxU = asr_d2key(smaxU + 1.1) | 0xFFFFFFFFull;
+        constexpr uint64_t FLOOR1 = 1ull << 32;   // floor "1": below every present key, zero low word
         // the selection floor guessed from the last frame's cutoff distance:
         // a pure speed knob (a guess above the cutoff falls back to the exact
         // floor-1 path; 1.1 / 0.35 measured best, profiles/r03)
         const double Gd = smaxU - (1.1 * gap + 0.35);
-        const uint64_t G = smaxU > -INFINITY ? asr_d2key(Gd) : 1ull;
+        // (rounded down to a zero low word: ctc_wave_select.h)
+        const uint64_t G = smaxU > -INFINITY ? asr_d2key(Gd) & ~0xFFFFFFFFull : FLOOR1;
         WRows<RPT> R;
         double rx[RPT], rsnb[RPT], rel[RPT];
         uint32_t pend = 0u;   // bit k: column 1 of row k has two sources (needs the exact fold)
@@ -444,8 +379,8 @@ void ctc_wave_kernel(CtcArgs a) {
                 R.k1[k] = asr_d2key(fmax(rx[k], y_) + rel[k]);
                 if (rx[k] > -INFINITY && y_ > -INFINITY) pend |= 1u << k;
             }
-            // the next frame's links and child masks (last read in frame t-1)
-            plN[r] = -1;
+            // the next frame's child masks (last read in frame t-1); its parent
+            // links are written by each slot's builder
             chN[r] = 0;
         }
         for (int i = lane; i < WOFW; i += 64) ofN[i] = 0u;
@@ -458,7 +393,10 @@ void ctc_wave_kernel(CtcArgs a) {
             const uint64_t x = R.l0[k] > -INFINITY ? asr_d2key(R.l0[k]) : 0ull;
             l0k = x > l0k ? x : l0k;
         }
-        l0k = wave_max_u64(l0k);
+        // the largest HIGH word with an all-ones low word: still an upper bound
+        // (2^-20 relative looser), from a 32-bit DPP maximum and one readlane
+        const uint32_t l0h = (uint32_t)__builtin_amdgcn_readlane((int)wave_max_u32_last((uint32_t)(l0k >> 32)), 63);
+        l0k = l0h ? ((uint64_t)l0h << 32) | 0xFFFFFFFFull : 0ull;
         const double maxL0 = l0k ? asr_key2d(l0k) : -INFINITY;
 
         // exact folds of column 1 where the upper bound max + ln 2 reaches FILT
@@ -482,7 +420,7 @@ void ctc_wave_kernel(CtcArgs a) {
         uint64_t rest = 0ull;
         int labs[WNL];
         for (int attempt = 0; attempt < 2; attempt++) {
-            const uint64_t floorG = attempt ? 1ull : G;
+            const uint64_t floorG = attempt ? FLOOR1 : G;
             uint64_t lm = __ballot(lane < V && lane != blank &&
                                    (attempt || asr_d2key(maxL0 + ev) >= G));
             nl = 0;
@@ -501,6 +439,9 @@ void ctc_wave_kernel(CtcArgs a) {
                         const double base = c == (int)(R.meta[k] & META_LAST) ? R.sb[k] : R.l0[k];
                         R.kx[k][j] = (!taken && base > -INFINITY) ? asr_d2key(base + ec) : 0ull;
                     }
+                } else {   // absent: key 0, counted by no pass and kept by no stage
+#pragma unroll
+                    for (int k = 0; k < RPT; k++) R.kx[k][j] = 0ull;
                 }
             }
             rest = lm;
@@ -538,15 +479,12 @@ void ctc_wave_kernel(CtcArgs a) {
         uint64_t smask[RPT];
         int spre[RPT];
         int nself = 0;
-        uint64_t kbest = 0ull;
 #pragma unroll
         for (int k = 0; k < RPT; k++) {
             const bool sb_ = R.kb[k] >= tau, snb_ = R.k1[k] >= tau;
             smask[k] = __ballot(sb_ || snb_);
             spre[k] = nself;
             nself += __popcll(smask[k]);
-            kbest = sb_ && R.kb[k] > kbest ? R.kb[k] : kbest;
-            kbest = snb_ && R.k1[k] > kbest ? R.k1[k] : kbest;
         }
         // the next slot of row r's own prefix (or -1)
         const auto newslot = [&](int r) -> int {
@@ -567,7 +505,7 @@ void ctc_wave_kernel(CtcArgs a) {
         int xtot = 0;
         {
             const auto stage = [&](uint64_t key, int r, int c) {
-                const bool s = key >= tau && key != 0ull;
+                const bool s = key >= tau;   // tau >= 1: an absent key (0) fails it
                 const uint64_t bal = __ballot(s);
                 if (s) {
                     const int i = nself + xtot + (int)mbcnt64(bal);
@@ -575,16 +513,14 @@ void ctc_wave_kernel(CtcArgs a) {
                         n_snb[i] = asr_key2d(key);
                         n_node[i] = r | (c << 16);
                     }
-                    kbest = key > kbest ? key : kbest;
                 }
                 xtot += __popcll(bal);
             };
 #pragma unroll
-            for (int j = 0; j < WNL; j++)
-                if (j < nl) {
+            for (int j = 0; j < WNL; j++) {   // j >= nl: key 0, nothing staged
 #pragma unroll
-                    for (int k = 0; k < RPT; k++) stage(R.kx[k][j], lane + 64 * k, labs[j]);
-                }
+                for (int k = 0; k < RPT; k++) stage(R.kx[k][j], lane + 64 * k, labs[j]);
+            }
             const WKeys<RPT> keys{R, nl, rest, ev};
             for (uint64_t m = rest; m; m &= m - 1ull) {
                 const int c = __builtin_ctzll(m);
@@ -596,8 +532,16 @@ void ctc_wave_kernel(CtcArgs a) {
         const int total = nself + xtot;
         if (total > kcap) overflow = 1;
         // best state (bounds every survivor): the top of the selection's
-        // highest bin, or (nothing pruned) the maximum survivor
-        best_state = prune ? ktop : wave_max_u64(kbest);
+        // highest bin, or (nothing pruned: tau = 1, every present key survives;
+        // uniform and rare) the maximum key
+        if (prune) {
+            best_state = ktop;
+        } else {
+            uint64_t kbest = 0ull;
+            const WKeys<RPT> keys{R, nl, rest, ev};
+            keys.each([&](uint64_t x) { kbest = x > kbest ? x : kbest; });
+            best_state = wave_max_u64(kbest);
+        }
 
         ASR_WCNT(11, xtot);
         ASR_WPH(5)   // survivors staged
@@ -627,8 +571,8 @@ void ctc_wave_kernel(CtcArgs a) {
             n_hp[i] = hp;
             const int pr = plC[r];
             const int y = pr >= 0 && pr < kcap ? newslot(pr) : -1;
+            plN[i] = y;   // (or -1) before any adoption below rewrites it
             if (y >= 0) {
-                plN[i] = y;
                 set_child_bit(&chN[y], lab);
             } else if (m0 & META_HAS_PAR) {
                 // an orphan next frame, unless an extension built now
@@ -667,8 +611,8 @@ void ctc_wave_kernel(CtcArgs a) {
             n_h[i] = h;
             n_hp[i] = hr;
             const int y = newslot(r);
+            plN[i] = y;
             if (y >= 0) {
-                plN[i] = y;
                 set_child_bit(&chN[y], lab);
             } else {
                 wofilt_insert(ofN, hr);
