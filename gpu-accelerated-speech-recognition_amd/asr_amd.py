@@ -40,6 +40,10 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           beam search with the n-gram LM fused into
                                           every prune (asr_ctc_lm_*); no reference
                                           member
+    CTCLMDecoder.word(V, beam_width, lm, Lexicon.from_lm(lm, labels), alpha, beta)
+                                          the same search with a word-level LM fused
+                                          through a lexicon trie (asr_lexicon_*,
+                                          asr_ctc_lm_create_word); no reference member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -92,6 +96,8 @@ EXPORTS = [
     "asr_edit_distance", "asr_edit_distance_host", "asr_nbest_mbr", "asr_nbest_mbr_host",
     "asr_ctc_lm_create", "asr_ctc_lm_destroy", "asr_ctc_lm_decode", "asr_ctc_lm_decode_host",
     "asr_ctc_lm_get_beams", "asr_ctc_lm_get_best", "asr_ctc_lm_host_gaps",
+    "asr_lexicon_create", "asr_lexicon_upload", "asr_lexicon_get_info", "asr_lexicon_destroy",
+    "asr_ctc_lm_create_word",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -231,6 +237,11 @@ def lib() -> ctypes.CDLL:
         "asr_ctc_lm_get_beams": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_ctc_lm_get_best": [_vp, _vp, _i, _vp, _vp],
         "asr_ctc_lm_host_gaps": [_vp, _vp],
+        "asr_lexicon_create": [_vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(_vp)],
+        "asr_lexicon_upload": [_vp],
+        "asr_lexicon_get_info": [_vp, _vp],
+        "asr_lexicon_destroy": [_vp],
+        "asr_ctc_lm_create_word": [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -1796,12 +1807,89 @@ class NGramLM:
             pass
 
 
+ASR_LEX_OPEN, ASR_LEX_CLOSED = 0, 1
+
+
+class LexiconInfo(ctypes.Structure):
+    """asr_lexicon_info (include/asr_amd.h)."""
+    _fields_ = [("words", ctypes.c_int32), ("nodes", ctypes.c_int32), ("max_children", ctypes.c_int32),
+                ("space_label", ctypes.c_int32), ("table_bytes", ctypes.c_int64)]
+
+
+class Lexicon:
+    """Handle over asr_lexicon_*: words spelled in label ids, each with one LM
+    token id, as a trie (include/asr_amd.h).  words is a list of label-id
+    lists, tokens their LM token ids, V the number of labels and space the
+    space label's id.  No arithmetic here."""
+
+    def __init__(self, words: Sequence[Sequence[int]], tokens: Sequence[int], V: int, space: int):
+        words = [list(w) for w in words]
+        if len(words) != len(tokens):
+            raise ValueError(f"Lexicon: {len(words)} words, {len(tokens)} tokens")
+        spell = np.ascontiguousarray([c for w in words for c in w] or [0], dtype=np.int32)
+        offsets = np.zeros(len(words) + 1, np.int64)
+        offsets[1:] = np.cumsum([len(w) for w in words])
+        tok = np.ascontiguousarray(list(tokens) or [0], dtype=np.int32)
+        h = _vp()
+        check(lib().asr_lexicon_create(_ptr(spell), _ptr(offsets), _ptr(tok), len(words), V, space, ctypes.byref(h)),
+              "asr_lexicon_create")
+        self.h = h.value
+        self.V, self.space, self.skipped = V, space, 0
+
+    @classmethod
+    def from_lm(cls, lm: "NGramLM", labels: Sequence[str], space: str = " ",
+                blank_id: Optional[int] = None) -> "Lexicon":
+        """Every token of lm except <s>, </s> and <unk>, spelled character by
+        character in labels.  A token with a character that is no label, or
+        with the space, is left out; `skipped` counts those.  blank_id names a
+        label whose string (ctcdecode's "_") spells nothing."""
+        labels = list(labels)
+        if space not in labels:
+            raise ValueError(f"Lexicon.from_lm: the space {space!r} is not a label")
+        label_of = {s: i for i, s in enumerate(labels) if len(s) == 1 and i != blank_id}
+        words, tokens, skipped = [], [], 0
+        for t in range(lm.vocab_size):
+            if t in (lm.bos_id, lm.eos_id, lm.unk_id):
+                continue
+            s = lm.token_string(t)
+            if s == "" or space in s or any(ch not in label_of for ch in s):
+                skipped += 1
+                continue
+            words.append([label_of[ch] for ch in s])
+            tokens.append(t)
+        lex = cls(words, tokens, len(labels), labels.index(space))
+        lex.skipped = skipped
+        return lex
+
+    def upload(self) -> None:
+        """Copy the trie to the current device (synchronous; once)."""
+        check(lib().asr_lexicon_upload(self.h), "asr_lexicon_upload")
+
+    def info(self) -> dict:
+        info = LexiconInfo()
+        check(lib().asr_lexicon_get_info(self.h, ctypes.byref(info)), "asr_lexicon_get_info")
+        return {"words": int(info.words), "nodes": int(info.nodes), "max_children": int(info.max_children),
+                "space_label": int(info.space_label), "table_bytes": int(info.table_bytes)}
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib().asr_lexicon_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CTCLMDecoder:
     """Handle over asr_ctc_lm_*: the beam search with the n-gram LM fused into
     every prune (the semantics are in include/asr_amd.h).  lm is an NGramLM
     that must outlive this decoder (upload() it before a device decode);
     tok_of_label[V] is the LM token of every label (NGramLM.label_tokens).
-    No arithmetic here."""
+    CTCLMDecoder.word(...) is the same handle in the word mode: a word-level
+    LM fused through a Lexicon.  No arithmetic here."""
 
     def __init__(self, V: int, beam_width: int, lm: NGramLM, tok_of_label: Sequence[int], alpha: float, beta: float,
                  blank_id: int = 0, bos: bool = True, eos: bool = False, top_n: int = 0, max_states: int = 0,
@@ -1818,8 +1906,33 @@ class CTCLMDecoder:
                                       max_states, lm.h, _ptr(tok), alpha, beta, flags, top_n, ctypes.byref(h)),
               "asr_ctc_lm_create")
         self.h = h.value
+        self.lexicon: Optional[Lexicon] = None
         self._emis: Optional[DeviceBytes] = None
         self.T = self.B = 0
+
+    @classmethod
+    def word(cls, V: int, beam_width: int, lm: NGramLM, lexicon: Lexicon, alpha: float, beta: float,
+             blank_id: int = 0, bos: bool = True, eos: bool = False, top_n: int = 0, closed: bool = False,
+             max_states: int = 0, codes: Optional[Sequence[int]] = None) -> "CTCLMDecoder":
+        """The word mode (asr_ctc_lm_create_word): lm is a word-level model and
+        lexicon spells its words; closed=True keeps the search inside the
+        lexicon.  beams() then reports words as n_tokens.  lm and lexicon must
+        outlive the decoder (upload() both before a device decode)."""
+        self = cls.__new__(cls)
+        self.V, self.beam, self.blank = V, beam_width, blank_id
+        self.lm, self.lexicon = lm, lexicon   # keeps both handles alive
+        self.codes = None if codes is None else np.ascontiguousarray(codes, dtype=np.int32)
+        flags = (ASR_LM_BOS if bos else 0) | (ASR_LM_EOS if eos else 0)
+        h = _vp()
+        self.h = None
+        check(lib().asr_ctc_lm_create_word(_ptr(self.codes) if self.codes is not None else None, V, beam_width,
+                                           blank_id, max_states, lm.h, lexicon.h, alpha, beta, flags, top_n,
+                                           ASR_LEX_CLOSED if closed else ASR_LEX_OPEN, ctypes.byref(h)),
+              "asr_ctc_lm_create_word")
+        self.h = h.value
+        self._emis = None
+        self.T = self.B = 0
+        return self
 
     @staticmethod
     def _lengths(lengths, B):
@@ -2282,22 +2395,45 @@ class CTCBeamDecoder:
     -total (total = ctc + alpha ln10 lm_log10 + beta n_tokens) and timesteps is
     all -1 (the fused search records none).  cutoff_prob other than 1.0 is not
     implemented with a model (NotImplementedError).  Without model_path,
-    cutoff_top_n, cutoff_prob, alpha and beta are ignored, as before."""
+    cutoff_top_n, cutoff_prob, alpha and beta are ignored, as before.
+
+    With lexicon="open" or "closed" model_path is a word-level model: its
+    tokens are spelled in the labels (Lexicon.from_lm, `space` the label that
+    separates words) and the search is CTCLMDecoder.word's, the LM term added
+    when a word ends; "closed" keeps the search inside the lexicon.  The same
+    outputs as with a label-level model.  ValueError if `space` is not a
+    label.  lexicon=None changes nothing."""
 
     def __init__(self, labels: Sequence[str], model_path: Optional[str] = None, alpha: float = 0.0,
                  beta: float = 0.0, cutoff_top_n: int = 40, cutoff_prob: float = 1.0,
                  beam_width: int = 100, num_processes: int = 4, blank_id: int = 0,
-                 log_probs_input: bool = False, timesteps: bool = True):
+                 log_probs_input: bool = False, timesteps: bool = True, lexicon: Optional[str] = None,
+                 space: str = " "):
         self.labels = list(labels)
         self.beam_width, self.blank_id, self.log_probs_input = beam_width, blank_id, log_probs_input
         self.track_timesteps = bool(timesteps)
         self._lm: Optional[NGramLM] = None
+        self._lex: Optional[Lexicon] = None
         self._fused: Optional[CTCLMDecoder] = None
         self._dec: Optional[CTCDecoder] = None
+        if lexicon is not None:
+            if lexicon not in ("open", "closed"):
+                raise ValueError(f"lexicon {lexicon!r}: None, \"open\" or \"closed\"")
+            if model_path is None:
+                raise ValueError("lexicon needs model_path, a word-level ARPA model")
+            if space not in self.labels:
+                raise ValueError(f"lexicon: the space {space!r} is not a label")
         if model_path is not None:
             if cutoff_prob != 1.0:
                 raise NotImplementedError("cutoff_prob other than 1.0 is not implemented with a language model")
             self._lm = NGramLM.from_arpa(model_path)
+            if lexicon is not None:
+                self._lex = Lexicon.from_lm(self._lm, self.labels, space, blank_id)
+                self._fused = CTCLMDecoder.word(len(self.labels), beam_width, self._lm, self._lex, alpha, beta,
+                                                blank_id, bos=self._lm.bos_id >= 0, eos=False,
+                                                top_n=max(int(cutoff_top_n), 0), closed=lexicon == "closed")
+                self._uploaded = False
+                return
             tok = self._lm.label_tokens(self.labels)
             if not any(t >= 0 for v, t in enumerate(tok) if v != blank_id):
                 raise ValueError("no non-blank label is a token of the model (a word-level LM?): decode without "
@@ -2317,6 +2453,8 @@ class CTCBeamDecoder:
         dec = self._fused if self._fused is not None else self._dec
         if self._fused is not None and not self._uploaded:
             self._lm.upload()
+            if self._lex is not None:
+                self._lex.upload()
             self._uploaded = True
         if hasattr(probs, "is_cuda") and probs.is_cuda:   # torch GPU tensor: zero-copy
             import torch

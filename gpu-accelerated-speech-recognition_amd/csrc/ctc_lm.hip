@@ -23,6 +23,12 @@
 //           of the new prefixes to HBM, the hash table rebuilt.
 // The host twin (asr_ctc_lm_decode_host) is the same rule set written over
 // std::map / std::set, one thread, no HIP call.
+//
+// Word mode (asr_ctc_lm_create_word): character labels and a
+// word-level LM.  A slot also carries its node in a lexicon trie (asr_lexicon_*:
+// three flat arrays in HBM, breadth-first) and its word count; W moves only when a
+// space ends a word, and the closed mode drops pairs the trie does not have.  The
+// frame loop is one template, instantiated once per mode.
 // ============================================================================
 #include "ctc_lse.h"
 #include "lm_tables.h"
@@ -67,6 +73,31 @@ struct ClmArgs {
     double* fin_lm;         // [B][kcap]
 };
 
+// The lexicon trie of the word mode, breadth-first: node 0 is the
+// root and the children of node i are the nodes first[i] .. first[i+1], their
+// labels ascending, so a child is found as lm_find finds a word.
+struct LexTables {
+    const uint32_t* first;   // [nodes + 1]
+    const int32_t* label;    // [nodes] the label on the edge into the node (root: -1)
+    const int32_t* tok;      // [nodes] LM token of the word that ends at the node, -1: none
+    int nodes, space, closed;
+};
+constexpr int LEX_OFF = -1;   // the partial word is no prefix of a lexicon word; never an index
+
+struct ClmWordArgs {
+    LexTables lex;
+    int32_t* fin_nw;   // [B][kcap] words scored
+};
+
+// Child of node z by label c, or LEX_OFF; the arrays are read for z >= 0 only.
+__host__ __device__ static inline int lex_child(const LexTables& t, int z, int c) {
+    if (z < 0) return LEX_OFF;
+    return (int)lm_find(t.label, t.first[z], t.first[z + 1], c);
+}
+
+// The token of the word that ends at z (z is not the root): -1, an OOV, unless z is terminal.
+__host__ __device__ static inline int32_t lex_word(const LexTables& t, int z) { return z > 0 ? t.tok[z] : -1; }
+
 __host__ __device__ static inline uint64_t clm_hash(uint64_t h, int c) {
     uint64_t x = (h ^ (uint64_t)(uint32_t)(c + 1)) * 0x9E3779B97F4A7C15ull;
     return x ^ (x >> 29);
@@ -95,14 +126,18 @@ __device__ __forceinline__ void clm_fold(double& acc, bool& have, double x, bool
     }
 }
 
-__host__ __device__ static inline size_t clm_lds_bytes(int kc) {
-    return (size_t)kc * 212 + 256 * 8 + 256 * 4 + CLM_HT * 4 + 256 * 4 + 16 * 4;
+// Word mode: two more ints per slot and buffer (the trie node and the word count).
+__host__ __device__ static inline size_t clm_lds_bytes(int kc, bool word = false) {
+    return (size_t)kc * (word ? 228 : 212) + 256 * 8 + 256 * 4 + CLM_HT * 4 + 256 * 4 + 16 * 4;
 }
 
 enum { M_NSTATE = 0, M_NNEW, M_NODES, M_BUCKET, M_KREM, M_ALL };
 
-__global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
-    extern __shared__ __align__(16) unsigned char smem[];
+// WORD: the word mode.  s_n stays the label count (the hash match
+// and the trace need it), s_nw counts the words scored, s_z is the trie node of the
+// partial word and s_ctx holds word tokens; W moves only when a space ends a word.
+template <bool WORD>
+__device__ __forceinline__ void clm_search(const ClmArgs& a, const ClmWordArgs& wa, unsigned char* smem) {
     const int KC = a.kcap, NC = a.nc;
     const int tid = threadIdx.x;
     const long ub = blockIdx.x;
@@ -128,6 +163,8 @@ __global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
     int* s_ht = s_clab + 256;                  // [CLM_HT] slot of a live prefix, -1: free
     unsigned* s_hist = (unsigned*)(s_ht + CLM_HT);   // [256]
     int* s_misc = (int*)(s_hist + 256);        // [16]
+    int* s_z = s_misc + 16;                    // [2][KC] word mode: trie node (0: root, LEX_OFF)
+    int* s_nw = s_z + 2 * KC;                  // [2][KC] word mode: words scored
 
     int len = a.lengths ? a.lengths[ub] : a.T;
     len = min(max(len, 1), a.T);
@@ -150,6 +187,10 @@ __global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
         s_last[0] = -1;
         s_fl[0] = 2;
         s_misc[M_NODES] = 0;
+        if constexpr (WORD) {
+            s_z[0] = 0;
+            s_nw[0] = 0;
+        }
     }
     for (int i = tid; i < CLM_HT; i += CLM_NT) s_ht[i] = -1;
     __syncthreads();
@@ -235,6 +276,25 @@ __global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
                 clm_fold(acc, have, viaBlank, pBlank);
                 if (!have) {
                     ckey[p] = 0;
+                } else if constexpr (WORD) {
+                    const int z = s_z[o + s];
+                    const bool sp = c == wa.lex.space;
+                    // closed: a letter needs a child in the trie, a space a finished word
+                    const bool ok =
+                        !wa.lex.closed || (sp ? (z > 0 && wa.lex.tok[z] >= 0) : lex_child(wa.lex, z, c) >= 0);
+                    if (!ok) {
+                        ckey[p] = 0;
+                    } else {
+                        double v = 0.0, Wn = s_W[o + s];
+                        if (sp && z != 0) {   // the space ends a word: the one LM lookup
+                            v = clm_value(a.lm, s_ctx + (o + s) * LM_CTX, min(s_nw[o + s], LM_CTX), lex_word(wa.lex, z),
+                                          false, a.flags);
+                            Wn = Wn + ((a.aln10 * v) + a.beta);
+                        }
+                        ckey[p] = asr_d2key(acc + Wn);
+                        cscore[p] = acc;
+                        cv[p] = v;
+                    }
                 } else {
                     const double v = clm_value(a.lm, s_ctx + (o + s) * LM_CTX, min(nq, LM_CTX), a.tok[c], false, a.flags);
                     const double Wn = s_W[o + s] + ((a.aln10 * v) + a.beta);
@@ -370,6 +430,10 @@ __global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
                 s_fl[d] = (sn ? 1 : 0) | (sb ? 2 : 0);
 #pragma unroll
                 for (int i = 0; i < LM_CTX; i++) s_ctx[d * LM_CTX + i] = s_ctx[(o + s) * LM_CTX + i];
+                if constexpr (WORD) {
+                    s_z[d] = s_z[o + s];
+                    s_nw[d] = s_nw[o + s];
+                }
             }
         }
         for (int p = tid; p < npairs; p += CLM_NT) {
@@ -380,25 +444,54 @@ __global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
                 const int d = o2 + atomicAdd(&s_misc[M_NNEW], 1);
                 const int nid = atomicAdd(&s_misc[M_NODES], 1);   // < T*KC: at most KC new prefixes per frame
                 nodes[nid] = make_int2(s_node[o + s], c);
-                s_nb[d] = cscore[p];
-                s_b[d] = 0.0;
-                s_W[d] = s_W[o + s] + ((a.aln10 * v) + a.beta);
-                s_L[d] = s_L[o + s] + v;
-                s_hash[d] = clm_hash(s_hash[o + s], c);
-                const int nq = s_n[o + s];
-                s_n[d] = nq + 1;
-                s_node[d] = nid;
-                s_pnode[d] = s_node[o + s];
-                s_last[d] = c;
-                s_fl[d] = 1;
-                const int m = min(nq, LM_CTX);
-                const int32_t tk = a.tok[c];
+                if constexpr (WORD) {
+                    const int z = s_z[o + s];
+                    const bool sp = c == wa.lex.space;
+                    const bool scored = sp && z != 0;   // the space ended a word: v is its value
+                    const int nw = s_nw[o + s];
+                    const int m = min(nw, LM_CTX);
+                    const int32_t tk = scored ? lex_word(wa.lex, z) : 0;
+                    s_nb[d] = cscore[p];
+                    s_b[d] = 0.0;
+                    s_W[d] = scored ? s_W[o + s] + ((a.aln10 * v) + a.beta) : s_W[o + s];
+                    s_L[d] = scored ? s_L[o + s] + v : s_L[o + s];
+                    s_hash[d] = clm_hash(s_hash[o + s], c);
+                    s_n[d] = s_n[o + s] + 1;
+                    s_node[d] = nid;
+                    s_pnode[d] = s_node[o + s];
+                    s_last[d] = c;
+                    s_fl[d] = 1;
+                    s_z[d] = sp ? 0 : lex_child(wa.lex, z, c);
+                    s_nw[d] = nw + (scored ? 1 : 0);
 #pragma unroll
-                for (int i = 0; i < LM_CTX; i++) {
-                    int x;
-                    if (m < LM_CTX) x = i < m ? s_ctx[(o + s) * LM_CTX + i] : (i == m ? tk : 0);
-                    else x = i < LM_CTX - 1 ? s_ctx[(o + s) * LM_CTX + i + 1] : tk;
-                    s_ctx[d * LM_CTX + i] = x;
+                    for (int i = 0; i < LM_CTX; i++) {
+                        int y;
+                        if (!scored) y = s_ctx[(o + s) * LM_CTX + i];
+                        else if (m < LM_CTX) y = i < m ? s_ctx[(o + s) * LM_CTX + i] : (i == m ? tk : 0);
+                        else y = i < LM_CTX - 1 ? s_ctx[(o + s) * LM_CTX + i + 1] : tk;
+                        s_ctx[d * LM_CTX + i] = y;
+                    }
+                } else {
+                    s_nb[d] = cscore[p];
+                    s_b[d] = 0.0;
+                    s_W[d] = s_W[o + s] + ((a.aln10 * v) + a.beta);
+                    s_L[d] = s_L[o + s] + v;
+                    s_hash[d] = clm_hash(s_hash[o + s], c);
+                    const int nq = s_n[o + s];
+                    s_n[d] = nq + 1;
+                    s_node[d] = nid;
+                    s_pnode[d] = s_node[o + s];
+                    s_last[d] = c;
+                    s_fl[d] = 1;
+                    const int m = min(nq, LM_CTX);
+                    const int32_t tk = a.tok[c];
+#pragma unroll
+                    for (int i = 0; i < LM_CTX; i++) {
+                        int x;
+                        if (m < LM_CTX) x = i < m ? s_ctx[(o + s) * LM_CTX + i] : (i == m ? tk : 0);
+                        else x = i < LM_CTX - 1 ? s_ctx[(o + s) * LM_CTX + i + 1] : tk;
+                        s_ctx[d * LM_CTX + i] = x;
+                    }
                 }
             }
         }
@@ -427,12 +520,43 @@ __global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
             bool have = false;
             clm_fold(acc, have, s_nb[o + s], (fl & 1) != 0);
             clm_fold(acc, have, s_b[o + s], (fl & 2) != 0);
-            double total = acc + s_W[o + s];
-            double L = s_L[o + s];
-            if (a.flags & ASR_LM_EOS) {
-                const double v = clm_value(a.lm, s_ctx + (o + s) * LM_CTX, min(s_n[o + s], LM_CTX), 0, true, a.flags);
-                total = total + (a.aln10 * v);
-                L = L + v;
+            double total, L;
+            if constexpr (WORD) {
+                int32_t ctx[LM_CTX];
+#pragma unroll
+                for (int i = 0; i < LM_CTX; i++) ctx[i] = s_ctx[(o + s) * LM_CTX + i];
+                double W = s_W[o + s];
+                L = s_L[o + s];
+                int nw = s_nw[o + s];
+                const int z = s_z[o + s];
+                if (z != 0) {   // the pending word, scored as a space would score it
+                    const int m = min(nw, LM_CTX);
+                    const int32_t tk = lex_word(wa.lex, z);
+                    const double v = clm_value(a.lm, ctx, m, tk, false, a.flags);
+                    W = W + ((a.aln10 * v) + a.beta);
+                    L = L + v;
+#pragma unroll
+                    for (int i = 0; i < LM_CTX; i++) {
+                        if (m < LM_CTX) ctx[i] = i == m ? tk : ctx[i];
+                        else ctx[i] = i < LM_CTX - 1 ? ctx[i + 1] : tk;
+                    }
+                    nw++;
+                }
+                total = acc + W;
+                if (a.flags & ASR_LM_EOS) {
+                    const double v = clm_value(a.lm, ctx, min(nw, LM_CTX), 0, true, a.flags);
+                    total = total + (a.aln10 * v);
+                    L = L + v;
+                }
+                wa.fin_nw[ub * KC + s] = nw;
+            } else {
+                total = acc + s_W[o + s];
+                L = s_L[o + s];
+                if (a.flags & ASR_LM_EOS) {
+                    const double v = clm_value(a.lm, s_ctx + (o + s) * LM_CTX, min(s_n[o + s], LM_CTX), 0, true, a.flags);
+                    total = total + (a.aln10 * v);
+                    L = L + v;
+                }
             }
             const long d = ub * KC + s;
             a.fin_node[d] = s_node[o + s];
@@ -446,6 +570,16 @@ __global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
             a.status[ub] = 0;
         }
     }
+}
+
+__global__ __launch_bounds__(CLM_NT) void ctc_lm_kernel(const ClmArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    clm_search<false>(a, ClmWordArgs{}, smem);
+}
+
+__global__ __launch_bounds__(CLM_NT) void ctc_wordlm_kernel(const ClmArgs a, const ClmWordArgs wa) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    clm_search<true>(a, wa, smem);
 }
 
 // The label cutoff: one wave per (frame, utterance) ranks the non-blank labels by
@@ -505,7 +639,8 @@ static inline double clm_lse_host(double x, double y) {
 
 struct ClmPrefix {
     double W = 0.0, L = 0.0;
-    int n = 0;
+    int n = 0;    // tokens scored (word mode: words)
+    int z = 0;    // word mode: trie node of the partial word (0: root, LEX_OFF)
     int32_t ctx[LM_CTX] = {};
 };
 
@@ -518,10 +653,34 @@ struct ClmHyp {
 
 }  // namespace asr
 
+struct asr_lexicon {
+    int V = 0, space = 0, words = 0, max_children = 0;
+    std::vector<uint32_t> first;
+    std::vector<int32_t> label, tok;
+    std::vector<char> used;   // [V] the label occurs in a spelling
+    void* d_blob = nullptr;
+    const uint32_t* d_first = nullptr;
+    const int32_t *d_label = nullptr, *d_tok = nullptr;
+
+    asr::LexTables tables(bool dev, int closed) const {
+        asr::LexTables t;
+        t.first = dev ? d_first : first.data();
+        t.label = dev ? d_label : label.data();
+        t.tok = dev ? d_tok : tok.data();
+        t.nodes = (int)label.size();
+        t.space = space;
+        t.closed = closed;
+        return t;
+    }
+};
+
 struct asr_ctc_lm {
     int V = 0, beam = 0, blank = 0, kcap = 0, nc = 0, top_n = 0, flags = 0;
     double aln10 = 0.0, beta = 0.0;
     const asr_lm* lm = nullptr;
+    const asr_lexicon* lex = nullptr;   // word mode
+    int closed = 0;
+    int32_t* d_fin_nw = nullptr;
     std::vector<int32_t> codes, tok;
     // results of the last decode
     int state = 0;   // 0: none, 1: a device decode is queued, 2: hyps hold the results
@@ -556,6 +715,8 @@ static void clm_free_work(asr_ctc_lm* h) {
                  h->d_fin_node, h->d_fin_len, h->d_fin_total, h->d_fin_ctc, h->d_fin_lm};
     for (void* q : p)
         if (q) (void)hipFree(q);
+    if (h->d_fin_nw) (void)hipFree(h->d_fin_nw);
+    h->d_fin_nw = nullptr;
     if (h->p_lengths) (void)hipHostFree(h->p_lengths);
     h->p_lengths = nullptr;
     h->len_queued = false;
@@ -598,6 +759,7 @@ static int clm_reserve(asr_ctc_lm* h, int T, int B) {
     ASR_HIP_TRY(hipMalloc(&h->d_fin_total, 8 * nb * kc));
     ASR_HIP_TRY(hipMalloc(&h->d_fin_ctc, 8 * nb * kc));
     ASR_HIP_TRY(hipMalloc(&h->d_fin_lm, 8 * nb * kc));
+    if (h->lex) ASR_HIP_TRY(hipMalloc(&h->d_fin_nw, 4 * nb * kc));
     h->capT = T;
     h->capB = B;
     return ASR_OK;
@@ -641,10 +803,12 @@ static bool clm_decode_one(const asr_ctc_lm* h, const LmTables& lm, const float*
         if (!p.empty() && p.back() == bcode) p.pop_back();
         return p;
     };
-    auto child = [&](const ClmPrefix& q, int label) {
+    const bool word = h->lex != nullptr;
+    const LexTables lex = word ? h->lex->tables(false, h->closed) : LexTables{};
+    // the token `tk` scored after q's context and appended to it
+    auto scored = [&](const ClmPrefix& q, int32_t tk) {
         ClmPrefix c = q;
         const int m = std::min(q.n, LM_CTX);
-        const int32_t tk = h->tok[label];
         const double v = clm_value(lm, q.ctx, m, tk, false, h->flags);
         c.W = q.W + ((h->aln10 * v) + h->beta);
         c.L = q.L + v;
@@ -655,6 +819,29 @@ static bool clm_decode_one(const asr_ctc_lm* h, const LmTables& lm, const float*
             c.ctx[LM_CTX - 1] = tk;
         }
         return c;
+    };
+    // word mode: q with its pending word (q.z is not the root) scored, back at the root
+    auto word_end = [&](const ClmPrefix& q) {
+        ClmPrefix c = scored(q, lex_word(lex, q.z));
+        c.z = 0;
+        return c;
+    };
+    // closed mode: does the transition q -> q + label exist?
+    auto allowed = [&](const ClmPrefix& q, int label) {
+        if (!word || !lex.closed) return true;
+        if (label == lex.space) return q.z > 0 && lex.tok[q.z] >= 0;
+        return lex_child(lex, q.z, label) >= 0;
+    };
+    auto child = [&](const ClmPrefix& q, int label) {
+        if (word) {
+            if (label != lex.space) {
+                ClmPrefix c = q;
+                c.z = lex_child(lex, q.z, label);
+                return c;
+            }
+            return q.z == 0 ? q : word_end(q);   // an empty word is not a word
+        }
+        return scored(q, h->tok[label]);
     };
     std::vector<double> le(V);
     std::vector<char> inC(V);
@@ -706,7 +893,7 @@ static bool clm_decode_one(const asr_ctc_lm* h, const LmTables& lm, const float*
     {
         const ClmPrefix root;
         for (int i = 0; i < V; i++) {
-            if (!inC[i]) continue;
+            if (!inC[i] || (i != blank && !allowed(root, i))) continue;
             const ClmStr s(1, h->codes[i]);
             path.insert(s);
             score[s] = le[i];
@@ -728,14 +915,13 @@ static bool clm_decode_one(const asr_ctc_lm* h, const LmTables& lm, const float*
                 if (i == blank) {
                     ns = s;
                     if (s.back() != bcode) ns.push_back(bcode);
-                } else if (s.back() == bcode) {
-                    ns = s;
-                    ns.back() = h->codes[i];
                 } else if (s.back() == h->codes[i]) {
-                    ns = s;
+                    ns = s;   // the repeat "qc" + c -> "qc": always exists
                 } else {
+                    if (!allowed(info.at(ps), i)) continue;   // closed mode: no such extension
                     ns = s;
-                    ns.push_back(h->codes[i]);
+                    if (s.back() == bcode) ns.back() = h->codes[i];
+                    else ns.push_back(h->codes[i]);
                 }
                 const double x = sc + le[i];
                 auto f = uscore.find(ns);
@@ -768,7 +954,8 @@ static bool clm_decode_one(const asr_ctc_lm* h, const LmTables& lm, const float*
     }
     out.clear();
     for (const auto& kv : fin) {
-        const ClmPrefix& q = info.at(kv.first);
+        const ClmPrefix& q0 = info.at(kv.first);
+        const ClmPrefix q = word && q0.z != 0 ? word_end(q0) : q0;   // the pending word
         ClmHyp hy;
         hy.str = kv.first;
         for (int32_t c : kv.first) hy.labels.push_back(label_of[c]);
@@ -804,7 +991,8 @@ static int clm_fetch(asr_ctc_lm* h) {
     ctc_lm_trace_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream>>>(
         h->d_nodes, (long)T * kc, h->d_fin_n, h->d_fin_node, h->d_fin_len, kc, T, B, h->d_lab);
     ASR_LAUNCH_TRY();
-    std::vector<int32_t> fin_n(B), status(B), fin_len((size_t)n);
+    std::vector<int32_t> fin_n(B), status(B), fin_len((size_t)n), fin_nw(h->lex ? (size_t)n : 0);
+    if (h->lex) ASR_HIP_TRY(hipMemcpyAsync(fin_nw.data(), h->d_fin_nw, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     std::vector<double> total((size_t)n), ctc((size_t)n), lmv((size_t)n);
     std::vector<uint16_t> lab(need);
     ASR_HIP_TRY(hipMemcpyAsync(fin_n.data(), h->d_fin_n, 4 * (size_t)B, hipMemcpyDeviceToHost, h->stream));
@@ -840,7 +1028,7 @@ static int clm_fetch(asr_ctc_lm* h) {
             hy.total = total[i];
             hy.ctc = ctc[i];
             hy.lm = lmv[i];
-            hy.n = fin_len[i];
+            hy.n = h->lex ? fin_nw[i] : fin_len[i];
         }
         clm_rank(v);
     }
@@ -848,22 +1036,23 @@ static int clm_fetch(asr_ctc_lm* h) {
     return ASR_OK;
 }
 
-}  // namespace asr
-
-extern "C" {
-
-int asr_ctc_lm_create(const int32_t* codes, int V, int beam_width, int blank_id, int max_states, const asr_lm_t* lm,
-                      const int32_t* tok_of_label, float alpha, float beta, int lm_flags, int top_n,
-                      asr_ctc_lm_t** out) {
+// Both creates: tok_of_label (token mode) or lex and lex_mode (word mode).
+static int clm_create(const int32_t* codes, int V, int beam_width, int blank_id, int max_states, const asr_lm_t* lm,
+                      const int32_t* tok_of_label, const asr_lexicon* lex, int lex_mode, bool word, float alpha,
+                      float beta, int lm_flags, int top_n, asr_ctc_lm_t** out) {
     if (!out) return ASR_ERR_ARG;
     *out = nullptr;
-    if (!lm || !tok_of_label) return ASR_ERR_ARG;
+    if (!lm || (word ? !lex : !tok_of_label)) return ASR_ERR_ARG;
     if (V < 2 || beam_width < 1 || blank_id < 0 || blank_id >= V) return ASR_ERR_ARG;
     if (!std::isfinite(alpha) || alpha < 0.0f || !std::isfinite(beta)) return ASR_ERR_ARG;
     if ((lm_flags & ~(ASR_LM_BOS | ASR_LM_EOS)) || top_n < 0 || max_states < 0) return ASR_ERR_ARG;
     const asr::LmTables *host, *dev;
     (void)asr_internal_lm_tables(lm, &host, &dev);
     if (((lm_flags & ASR_LM_BOS) && host->bos < 0) || ((lm_flags & ASR_LM_EOS) && host->eos < 0)) return ASR_ERR_ARG;
+    if (word) {
+        if (lex->V != V || lex->used[blank_id] || lex->space == blank_id) return ASR_ERR_ARG;
+        if (lex_mode != ASR_LEX_OPEN && lex_mode != ASR_LEX_CLOSED) return ASR_ERR_ARG;
+    }
     if (V > asr::CLM_VMAX) return ASR_ERR_UNSUPPORTED;
     if (codes)
         for (int v = 0; v < V; v++)
@@ -880,7 +1069,8 @@ int asr_ctc_lm_create(const int32_t* codes, int V, int beam_width, int blank_id,
     try {
         h = new asr_ctc_lm();
         h->codes.resize(V);
-        h->tok.assign(tok_of_label, tok_of_label + V);
+        if (word) h->tok.assign(V, -1);   // unused: words carry the tokens
+        else h->tok.assign(tok_of_label, tok_of_label + V);
         for (int v = 0; v < V; v++) h->codes[v] = codes ? codes[v] : v;
     } catch (const std::bad_alloc&) {
         delete h;
@@ -896,7 +1086,141 @@ int asr_ctc_lm_create(const int32_t* codes, int V, int beam_width, int blank_id,
     h->aln10 = (double)alpha * 2.302585092994046;
     h->beta = (double)beta;
     h->lm = lm;
+    h->lex = word ? lex : nullptr;
+    h->closed = word && lex_mode == ASR_LEX_CLOSED ? 1 : 0;
     *out = h;
+    return ASR_OK;
+}
+
+}  // namespace asr
+
+extern "C" {
+
+int asr_ctc_lm_create(const int32_t* codes, int V, int beam_width, int blank_id, int max_states, const asr_lm_t* lm,
+                      const int32_t* tok_of_label, float alpha, float beta, int lm_flags, int top_n,
+                      asr_ctc_lm_t** out) {
+    return asr::clm_create(codes, V, beam_width, blank_id, max_states, lm, tok_of_label, nullptr, 0, false, alpha, beta,
+                           lm_flags, top_n, out);
+}
+
+int asr_ctc_lm_create_word(const int32_t* codes, int V, int beam_width, int blank_id, int max_states,
+                           const asr_lm_t* lm, const asr_lexicon_t* lex, float alpha, float beta, int lm_flags,
+                           int top_n, int lex_mode, asr_ctc_lm_t** out) {
+    return asr::clm_create(codes, V, beam_width, blank_id, max_states, lm, nullptr, lex, lex_mode, true, alpha, beta,
+                           lm_flags, top_n, out);
+}
+
+int asr_lexicon_create(const int32_t* spell, const int64_t* offsets, const int32_t* tok, int n_words, int V,
+                       int space_label, asr_lexicon_t** out) {
+    if (!out) return ASR_ERR_ARG;
+    *out = nullptr;
+    if (!spell || !offsets || !tok) return ASR_ERR_ARG;
+    if (V < 2 || n_words < 1 || space_label < 0 || space_label >= V) return ASR_ERR_ARG;
+    if (offsets[0] != 0) return ASR_ERR_ARG;
+    for (int w = 0; w < n_words; w++)
+        if (offsets[w + 1] < offsets[w]) return ASR_ERR_ARG;
+    for (int64_t i = 0; i < offsets[n_words]; i++)
+        if (spell[i] < 0 || spell[i] >= V || spell[i] == space_label) return ASR_ERR_ARG;
+    for (int w = 0; w < n_words; w++)
+        if (offsets[w + 1] == offsets[w]) return ASR_ERR_ARG;
+    for (int w = 0; w < n_words; w++)
+        if (tok[w] < 0) return ASR_ERR_ARG;
+    asr_lexicon* h = nullptr;
+    try {
+        // the trie in insertion order, then renumbered breadth-first
+        std::vector<std::map<int32_t, int64_t>> kids(1);
+        std::vector<int32_t> wtok(1, -1);
+        int words = 0;
+        for (int w = 0; w < n_words; w++) {
+            int64_t z = 0;
+            for (int64_t i = offsets[w]; i < offsets[w + 1]; i++) {
+                auto f = kids[(size_t)z].find(spell[i]);
+                if (f != kids[(size_t)z].end()) {
+                    z = f->second;
+                } else {
+                    if (kids.size() >= ((size_t)1 << 31) - 1) return ASR_ERR_UNSUPPORTED;   // 2^31 or more nodes
+                    const int64_t nz = (int64_t)kids.size();
+                    kids[(size_t)z][spell[i]] = nz;
+                    kids.emplace_back();
+                    wtok.push_back(-1);
+                    z = nz;
+                }
+            }
+            if (wtok[(size_t)z] >= 0) {
+                if (wtok[(size_t)z] != tok[w]) return ASR_ERR_ARG;   // one spelling, two tokens
+            } else {
+                wtok[(size_t)z] = tok[w];
+                words++;
+            }
+        }
+        h = new asr_lexicon();
+        const size_t N = kids.size();
+        h->first.resize(N + 1);
+        h->label.resize(N);
+        h->tok.resize(N);
+        h->used.assign((size_t)V, 0);
+        std::vector<int64_t> order(1, 0);   // order[new id] = old id
+        order.reserve(N);
+        h->label[0] = -1;
+        for (size_t i = 0; i < N; i++) {
+            const int64_t old = order[i];
+            h->first[i] = (uint32_t)order.size();
+            h->tok[i] = wtok[(size_t)old];
+            h->max_children = std::max(h->max_children, (int)kids[(size_t)old].size());
+            for (const auto& kv : kids[(size_t)old]) {   // ascending labels
+                h->label[order.size()] = kv.first;
+                h->used[(size_t)kv.first] = 1;
+                order.push_back(kv.second);
+            }
+        }
+        h->first[N] = (uint32_t)N;
+        h->V = V;
+        h->space = space_label;
+        h->words = words;
+    } catch (const std::bad_alloc&) {
+        delete h;
+        return ASR_ERR_OOM;
+    }
+    *out = h;
+    return ASR_OK;
+}
+
+int asr_lexicon_upload(asr_lexicon_t* h) {
+    if (!h) return ASR_ERR_ARG;
+    if (h->d_blob) return ASR_OK;
+    const size_t N = h->label.size();
+    const size_t b_first = ((N + 1) * 4 + 15) & ~(size_t)15, b_node = (N * 4 + 15) & ~(size_t)15;
+    void* d = nullptr;
+    ASR_HIP_TRY(hipMalloc(&d, b_first + 2 * b_node));
+    hipError_t e = hipMemcpy(d, h->first.data(), (N + 1) * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char*)d + b_first, h->label.data(), N * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char*)d + b_first + b_node, h->tok.data(), N * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        asr_internal_set_error("hipMemcpy (lexicon tables)", hipGetErrorString(e), __FILE__, __LINE__);
+        (void)hipFree(d);
+        return ASR_ERR_HIP;
+    }
+    h->d_first = (const uint32_t*)d;
+    h->d_label = (const int32_t*)((char*)d + b_first);
+    h->d_tok = (const int32_t*)((char*)d + b_first + b_node);
+    h->d_blob = d;
+    return ASR_OK;
+}
+
+int asr_lexicon_get_info(const asr_lexicon_t* h, asr_lexicon_info* info) {
+    if (!h || !info) return ASR_ERR_ARG;
+    info->words = h->words;
+    info->nodes = (int32_t)h->label.size();
+    info->max_children = h->max_children;
+    info->space_label = h->space;
+    info->table_bytes = (int64_t)(h->first.size() + h->label.size() + h->tok.size()) * 4;
+    return ASR_OK;
+}
+
+int asr_lexicon_destroy(asr_lexicon_t* h) {
+    if (!h) return ASR_ERR_ARG;
+    if (h->d_blob) (void)hipFree(h->d_blob);
+    delete h;
     return ASR_OK;
 }
 
@@ -920,6 +1244,7 @@ int asr_ctc_lm_decode(asr_ctc_lm_t* h, const float* d_emis, int T, int B, long f
     if (rc != ASR_OK) return rc;
     const asr::LmTables *host, *dev;
     if (!asr_internal_lm_tables(h->lm, &host, &dev)) return ASR_ERR_STATE;
+    if (h->lex && !h->lex->d_blob) return ASR_ERR_STATE;
     hipStream_t st = asr_stream(s);
     // one decode at a time per handle: a queued one on another stream ends before its workspace is reused
     if (h->state == 1 && h->stream != st) ASR_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -968,7 +1293,14 @@ int asr_ctc_lm_decode(asr_ctc_lm_t* h, const float* d_emis, int T, int B, long f
     a.fin_total = h->d_fin_total;
     a.fin_ctc = h->d_fin_ctc;
     a.fin_lm = h->d_fin_lm;
-    asr::ctc_lm_kernel<<<dim3((unsigned)B), dim3(asr::CLM_NT), asr::clm_lds_bytes(h->kcap), st>>>(a);
+    if (h->lex) {
+        asr::ClmWordArgs wa;
+        wa.lex = h->lex->tables(true, h->closed);
+        wa.fin_nw = h->d_fin_nw;
+        asr::ctc_wordlm_kernel<<<dim3((unsigned)B), dim3(asr::CLM_NT), asr::clm_lds_bytes(h->kcap, true), st>>>(a, wa);
+    } else {
+        asr::ctc_lm_kernel<<<dim3((unsigned)B), dim3(asr::CLM_NT), asr::clm_lds_bytes(h->kcap), st>>>(a);
+    }
     ASR_LAUNCH_TRY();
     h->stream = st;
     h->lastT = T;

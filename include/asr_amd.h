@@ -1178,6 +1178,86 @@ int asr_ctc_lm_get_beams(asr_ctc_lm_t* h, int max_hyps, int max_len, int32_t* h_
 int asr_ctc_lm_get_best(asr_ctc_lm_t* h, int32_t* h_labels, int max_len, int32_t* h_lengths, double* h_total);
 int asr_ctc_lm_host_gaps(asr_ctc_lm_t* h, double* h_gap);
 
+/* ---- Word-level LM fused through a lexicon trie ----------------
+ * Character labels, a word-level n-gram model: the search is the fused search
+ * above, unchanged (states, fold order, fp64 lse, fused(s) = pathScore(s) +
+ * W(prefix of s), the prune with ties kept, top_n, the final merge, the ranking).
+ * Only what a prefix carries, and when W moves, changes.  One non-blank label is
+ * the space label sp.
+ *
+ * Lexicon: a set of words, each a non-empty sequence of non-blank, non-space
+ * labels with one LM token id, kept as a trie.  An id outside the model's
+ * [0, vocab) is an OOV under asr_lm_*'s rule.
+ *
+ * Every prefix q carries z(q), a trie node: the root (the partial word is empty),
+ * a node, or OFF (the partial word is no prefix of a lexicon word); n(q), the
+ * words scored; the last min(n, 7) word tokens; W and L.  All depend on the
+ * string q only.
+ *   q + c, c != sp:  z = child(z(q), c), OFF if there is none or z(q) is OFF;
+ *                    W, L, n and the context are unchanged.
+ *   q + sp, the partial word empty (q empty or ending in sp): nothing changes
+ *                    (an empty word is not a word).
+ *   q + sp otherwise: w = the word token of z(q) if z(q) is terminal, else -1 (an
+ *                    OOV); v = the per-token value of w after the word context,
+ *                    ASR_LM_BOS as configured, ASR_LM_EOS off;
+ *                    W = W(q) + ((aln10 * v) + beta), L = L(q) + v,
+ *                    n = n(q) + 1, z = the root.
+ * every operation a rounded fp64 operation.  Final: a hypothesis whose partial
+ * word is not empty gets that word scored by the same rule (with beta, counted in
+ * n) before the totals; then ASR_LM_EOS applies as above.
+ *
+ * lex_mode ASR_LEX_OPEN: every transition of the plain search exists; words
+ * outside the lexicon cost the OOV value.  ASR_LEX_CLOSED: a transition q -> q+c,
+ * c != sp, exists only if z(q+c) is not OFF, and q -> q+sp only if z(q) is
+ * terminal (so no leading or doubled space and no unfinished word before a
+ * space).  A removed transition takes part in nothing at that frame, like a label
+ * outside C_t.  Blank and the repeat "qc"+c -> "qc" always exist.  At the final a
+ * partial word that is not terminal is still scored as an OOV: closed mode
+ * constrains transitions, not final states.
+ *
+ * With alpha = 0 and beta = 0 in open mode W is exactly 0.0 and the search is
+ * asr_ctc_*'s.  The limits are those above.
+ *
+ * asr_lexicon_create: host only.  spell holds the words' label ids one after
+ * another, offsets[n_words + 1] delimits them (offsets[0] = 0), tok[n_words] are
+ * their LM token ids.  Checks, in this order — ASR_ERR_ARG: out NULL; spell,
+ * offsets or tok NULL; V < 2, n_words < 1, space_label outside [0, V);
+ * offsets[0] != 0 or decreasing offsets; a label outside [0, V) or equal to
+ * space_label; an empty word; a negative token; one spelling with two different
+ * tokens (the same spelling with the same token counts once).
+ * ASR_ERR_UNSUPPORTED: 2^31 or more trie nodes.
+ * asr_lexicon_upload: copies the trie to the current device (synchronous; a
+ * second call does nothing).  asr_lexicon_get_info: words, nodes (the root
+ * included), the largest child count, bytes of the three tables.
+ * asr_lexicon_destroy: ASR_ERR_ARG for NULL.
+ *
+ * asr_ctc_lm_create_word: an asr_ctc_lm_t on which asr_ctc_lm_decode,
+ * _decode_host, _get_beams, _get_best, _host_gaps and _destroy work as above;
+ * n_tokens is then n (words), lm_log10 is L, lengths stay label counts.  The
+ * lexicon and the LM must outlive the handle.  Checks: asr_ctc_lm_create's, with
+ * lex in the place of tok_of_label, and, after "a flag whose token the model
+ * lacks" — ASR_ERR_ARG: the lexicon's V differs from V; a spelling uses
+ * blank_id; space_label == blank_id; lex_mode neither ASR_LEX_OPEN nor
+ * ASR_LEX_CLOSED.  asr_ctc_lm_decode returns ASR_ERR_STATE until both
+ * asr_lm_upload and asr_lexicon_upload have run. */
+enum { ASR_LEX_OPEN = 0, ASR_LEX_CLOSED = 1 };
+typedef struct asr_lexicon asr_lexicon_t;
+typedef struct asr_lexicon_info {
+    int32_t words;         /* distinct spellings */
+    int32_t nodes;         /* trie nodes, the root included */
+    int32_t max_children;  /* the widest sibling run */
+    int32_t space_label;
+    int64_t table_bytes;
+} asr_lexicon_info;
+int asr_lexicon_create(const int32_t* spell, const int64_t* offsets, const int32_t* tok, int n_words, int V,
+                       int space_label, asr_lexicon_t** out);
+int asr_lexicon_upload(asr_lexicon_t* h);
+int asr_lexicon_get_info(const asr_lexicon_t* h, asr_lexicon_info* info);
+int asr_lexicon_destroy(asr_lexicon_t* h);
+int asr_ctc_lm_create_word(const int32_t* codes, int V, int beam_width, int blank_id, int max_states,
+                           const asr_lm_t* lm, const asr_lexicon_t* lex, float alpha, float beta, int lm_flags,
+                           int top_n, int lex_mode, asr_ctc_lm_t** out);
+
 #ifdef __cplusplus
 }
 #endif
