@@ -44,6 +44,10 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           the same search with a word-level LM fused
                                           through a lexicon trie (asr_lexicon_*,
                                           asr_ctc_lm_create_word); no reference member
+    TransducerDecoder.from_torch(embedding, lstm, enc_proj, pred_proj, out_proj, blank).decode(enc)
+                                          RNN-T greedy decoding, the whole (t, u)
+                                          walk in one launch (asr_rnnt_*); no
+                                          reference member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -98,6 +102,8 @@ EXPORTS = [
     "asr_ctc_lm_get_beams", "asr_ctc_lm_get_best", "asr_ctc_lm_host_gaps",
     "asr_lexicon_create", "asr_lexicon_upload", "asr_lexicon_get_info", "asr_lexicon_destroy",
     "asr_ctc_lm_create_word",
+    "asr_rnnt_create", "asr_rnnt_upload", "asr_rnnt_get_info", "asr_rnnt_destroy", "asr_rnnt_workspace_bytes",
+    "asr_rnnt_greedy", "asr_rnnt_greedy_host",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -242,6 +248,12 @@ def lib() -> ctypes.CDLL:
         "asr_lexicon_get_info": [_vp, _vp],
         "asr_lexicon_destroy": [_vp],
         "asr_ctc_lm_create_word": [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _i, _i, _i, ctypes.POINTER(_vp)],
+        "asr_rnnt_create": [_vp, _vp, ctypes.POINTER(_vp)],
+        "asr_rnnt_upload": [_vp],
+        "asr_rnnt_get_info": [_vp, _vp],
+        "asr_rnnt_destroy": [_vp],
+        "asr_rnnt_greedy": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_greedy_host": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -274,6 +286,8 @@ def lib() -> ctypes.CDLL:
     L.asr_fbank_workspace_bytes.restype = _sz
     L.asr_ctc_align_workspace_bytes.argtypes = [_i, _i, _i]
     L.asr_ctc_align_workspace_bytes.restype = _sz
+    L.asr_rnnt_workspace_bytes.argtypes = [_vp, _i, _i]
+    L.asr_rnnt_workspace_bytes.restype = _sz
     _lib = L
     return L
 
@@ -2019,6 +2033,230 @@ class CTCLMDecoder:
         if getattr(self, "h", None):
             lib().asr_ctc_lm_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------ RNN-T (transducer)
+RNNT_ACT_RELU, RNNT_ACT_TANH = 0, 1    # ASR_RNNT_ACT_*
+RNNT_ACTS = {"relu": RNNT_ACT_RELU, "tanh": RNNT_ACT_TANH}
+ASR_RNNT_MAX_LAYERS = 2
+
+
+class RnntDesc(ctypes.Structure):
+    """asr_rnnt_desc (include/asr_amd.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("V", "blank", "E", "D", "Hp", "L", "J", "act", "max_symbols")]
+
+
+class RnntWeights(ctypes.Structure):
+    """asr_rnnt_weights: host pointers."""
+    _fields_ = [("emb", _vp), ("w_ih", _vp * ASR_RNNT_MAX_LAYERS), ("w_hh", _vp * ASR_RNNT_MAX_LAYERS),
+                ("b_ih", _vp * ASR_RNNT_MAX_LAYERS), ("b_hh", _vp * ASR_RNNT_MAX_LAYERS), ("w_enc", _vp),
+                ("b_enc", _vp), ("w_pred", _vp), ("b_pred", _vp), ("w_out", _vp), ("b_out", _vp)]
+
+
+class RnntInfo(ctypes.Structure):
+    """asr_rnnt_info."""
+    _fields_ = [("desc", RnntDesc), ("uploaded", ctypes.c_int32), ("lds_bytes", ctypes.c_int32),
+                ("weight_bytes", ctypes.c_int64)]
+
+
+def rnnt_desc(V: int, blank: int, E: int, D: int, Hp: int, L: int, J: int, act="relu",
+              max_symbols: int = 10) -> RnntDesc:
+    return RnntDesc(V, blank, E, D, Hp, L, J, RNNT_ACTS[act] if isinstance(act, str) else int(act), max_symbols)
+
+
+class TransducerDecoder:
+    """RNN-T greedy decoding (asr_rnnt_*; the walk is defined in
+    include/asr_amd.h): an embedding, an LSTM prediction network of one or two
+    layers and a joint network, decoded frame by frame in one launch
+    (decode / decode_device) or by the fp64 host twin (decode_host).  No
+    arithmetic here.
+
+    weights: a dict of fp32 arrays in the library's [in][out] layout: emb
+    [V, D]; w_ih, w_hh, b_ih, b_hh: lists of L arrays ([in, 4Hp], [Hp, 4Hp],
+    [4Hp]); w_enc [E, J], b_enc; w_pred [Hp, J], b_pred; w_out [J, V], b_out."""
+
+    def __init__(self, desc: RnntDesc, weights: dict):
+        self.desc = desc
+        self.h = None
+        d = desc
+        L = max(0, min(int(d.L), ASR_RNNT_MAX_LAYERS))
+        H4 = 4 * d.Hp
+        shapes = {"emb": (d.V, d.D), "w_enc": (d.E, d.J), "b_enc": (d.J,), "w_pred": (d.Hp, d.J), "b_pred": (d.J,),
+                  "w_out": (d.J, d.V), "b_out": (d.V,)}
+        keep = {}
+        w = RnntWeights()
+        for name, shape in shapes.items():
+            a = np.ascontiguousarray(weights[name], dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{name}: shape {a.shape}, expected {shape}")
+            keep[name] = a
+            setattr(w, name, _ptr(a))
+        for name in ("w_ih", "w_hh", "b_ih", "b_hh"):
+            if len(weights[name]) != d.L:
+                raise ValueError(f"{name}: {len(weights[name])} layers, expected {d.L}")
+            for l in range(L):
+                a = np.ascontiguousarray(weights[name][l], dtype=np.float32)
+                shape = {"w_ih": (d.Hp if l else d.D, H4), "w_hh": (d.Hp, H4)}.get(name, (H4,))
+                if a.shape != shape:
+                    raise ValueError(f"{name}[{l}]: shape {a.shape}, expected {shape}")
+                keep[name, l] = a
+                getattr(w, name)[l] = _ptr(a)
+        self.weights = keep            # the fp32 arrays the handle was made from
+        h = _vp()
+        check(lib().asr_rnnt_create(ctypes.byref(desc), ctypes.byref(w), ctypes.byref(h)), "asr_rnnt_create")
+        self.h = h.value
+        self._work = None
+        self._uploaded = False
+
+    @classmethod
+    def from_torch(cls, embedding, lstm, enc_proj, pred_proj, out_proj, blank: int, activation: str = "relu",
+                   max_symbols: int = 10) -> "TransducerDecoder":
+        """From torch.nn.Embedding, torch.nn.LSTM (unidirectional, with bias, no
+        projection) and three torch.nn.Linear, transposed into [in][out]."""
+        if lstm.bidirectional or not lstm.bias or getattr(lstm, "proj_size", 0):
+            raise ValueError("the predictor is a unidirectional LSTM with bias and no projection")
+
+        def arr(t):
+            return t.detach().cpu().numpy().astype(np.float32)
+
+        def lin(m):
+            b = arr(m.bias) if m.bias is not None else np.zeros(m.out_features, np.float32)
+            return np.ascontiguousarray(arr(m.weight).T), b
+
+        L = lstm.num_layers
+        wt = {"emb": arr(embedding.weight),
+              "w_ih": [np.ascontiguousarray(arr(getattr(lstm, f"weight_ih_l{l}")).T) for l in range(L)],
+              "w_hh": [np.ascontiguousarray(arr(getattr(lstm, f"weight_hh_l{l}")).T) for l in range(L)],
+              "b_ih": [arr(getattr(lstm, f"bias_ih_l{l}")) for l in range(L)],
+              "b_hh": [arr(getattr(lstm, f"bias_hh_l{l}")) for l in range(L)]}
+        wt["w_enc"], wt["b_enc"] = lin(enc_proj)
+        wt["w_pred"], wt["b_pred"] = lin(pred_proj)
+        wt["w_out"], wt["b_out"] = lin(out_proj)
+        d = rnnt_desc(embedding.num_embeddings, blank, enc_proj.in_features, embedding.embedding_dim,
+                      lstm.hidden_size, L, enc_proj.out_features, activation, max_symbols)
+        if lstm.input_size != d.D or pred_proj.in_features != d.Hp or pred_proj.out_features != d.J or \
+                out_proj.in_features != d.J or out_proj.out_features != d.V:
+            raise ValueError("the modules' sizes do not chain")
+        return cls(d, wt)
+
+    def info(self) -> dict:
+        info = RnntInfo()
+        check(lib().asr_rnnt_get_info(self.h, ctypes.byref(info)), "asr_rnnt_get_info")
+        return {**{n: int(getattr(info.desc, n)) for n, _t in RnntDesc._fields_}, "uploaded": bool(info.uploaded),
+                "lds_bytes": int(info.lds_bytes), "weight_bytes": int(info.weight_bytes)}
+
+    def upload(self) -> None:
+        """Copy the weights to the current device (synchronous; once)."""
+        check(lib().asr_rnnt_upload(self.h), "asr_rnnt_upload")
+        self._uploaded = True
+
+    def workspace_bytes(self, T: int, B: int) -> int:
+        return int(lib().asr_rnnt_workspace_bytes(self.h, T, B))
+
+    def state_shape(self, B: int) -> tuple:
+        """(2, L, B, Hp): h of every layer, then c."""
+        return (2, int(self.desc.L), int(B), int(self.desc.Hp))
+
+    def decode_device(self, d_enc: int, T: int, B: int, max_out: int, d_tokens: int, d_timesteps: int, d_logp: int,
+                      d_count: int, d_total: int, d_work: int, d_lengths: int = 0, d_state_in: int = 0,
+                      d_state_out: int = 0, stream: int = 0) -> None:
+        """asr_rnnt_greedy on device pointers: asynchronous on stream."""
+        check(lib().asr_rnnt_greedy(self.h, d_enc or None, d_lengths or None, T, B, max_out, d_state_in or None,
+                                    d_state_out or None, d_tokens or None, d_timesteps or None, d_logp or None,
+                                    d_count or None, d_total or None, d_work or None, stream or None),
+              "asr_rnnt_greedy")
+
+    @staticmethod
+    def _unpack(B, max_out, tok, ts, lp, cnt, total):
+        out = []
+        for b in range(B):
+            n = min(int(cnt[b]), max_out)
+            out.append((tok[b, :n].tolist(), ts[b, :n].tolist(), lp[b, :n].copy(), float(total[b])))
+        return out
+
+    def _prepare(self, enc, lengths, max_out):
+        enc = np.ascontiguousarray(enc, dtype=np.float32)
+        if enc.ndim != 3 or enc.shape[2] != self.desc.E:
+            raise ValueError(f"enc: shape {enc.shape}, expected (T, B, {self.desc.E})")
+        T, B = enc.shape[0], enc.shape[1]
+        if max_out is None:
+            max_out = T * int(self.desc.max_symbols)
+        ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        if ln is not None and ln.shape != (B,):
+            raise ValueError(f"lengths: shape {ln.shape}, expected ({B},)")
+        return enc, ln, T, B, int(max_out)
+
+    def decode(self, enc, lengths=None, state=None, max_out=None, stream: int = 0):
+        """enc [T, B, E] time-major.  Returns (results, state, counts): per
+        utterance (tokens, timesteps, logps float64, total), the new state
+        [2, L, B, Hp] float32 (pass it to the next chunk's decode and add the
+        frame offset to the timesteps), and the emission counts int32 [B],
+        which exceed max_out where records were dropped.  max_out defaults to
+        T * max_symbols, the most a walk can emit."""
+        enc, ln, T, B, max_out = self._prepare(enc, lengths, max_out)
+        if not self._uploaded:
+            self.upload()
+        d_enc = _upload(enc, stream)
+        d_len = _upload(ln, stream) if ln is not None else None
+        shape = self.state_shape(B)
+        nstate = int(np.prod(shape))
+        d_sin = None
+        if state is not None:
+            st = np.ascontiguousarray(state, dtype=np.float32)
+            if st.shape != shape:
+                raise ValueError(f"state: shape {st.shape}, expected {shape}")
+            d_sin = _upload(st, stream)
+        d_sout = DeviceBytes(4 * nstate)
+        mo = max(max_out, 1)
+        d_tok, d_ts, d_lp = DeviceBytes(4 * B * mo), DeviceBytes(4 * B * mo), DeviceBytes(8 * B * mo)
+        d_cnt, d_tot = DeviceBytes(max(4 * B, 16)), DeviceBytes(max(8 * B, 16))
+        need = self.workspace_bytes(T, B)
+        if self._work is None or self._work.nbytes < need:
+            self._work = DeviceBytes(need)
+        self.decode_device(d_enc.ptr, T, B, max_out, d_tok.ptr, d_ts.ptr, d_lp.ptr, d_cnt.ptr, d_tot.ptr,
+                           self._work.ptr, d_len.ptr if d_len else 0, d_sin.ptr if d_sin else 0, d_sout.ptr, stream)
+        check(lib().asr_stream_sync(stream or None), "asr_stream_sync")
+        cnt = _download(d_cnt, (B,), np.int32, stream)
+        total = _download(d_tot, (B,), np.float64, stream)
+        tok = _download(d_tok, (B, mo), np.int32, stream)
+        ts = _download(d_ts, (B, mo), np.int32, stream)
+        lp = _download(d_lp, (B, mo), np.float64, stream)
+        new_state = _download(d_sout, shape, np.float32, stream)
+        return self._unpack(B, max_out, tok, ts, lp, cnt, total), new_state, cnt
+
+    def decode_host(self, enc, lengths=None, state=None, max_out=None, gaps: bool = False):
+        """The same through asr_rnnt_greedy_host (one thread, fp64): the state is
+        float64; with gaps also the smallest top-2 logit gap of each
+        utterance's walk."""
+        enc, ln, T, B, max_out = self._prepare(enc, lengths, max_out)
+        shape = self.state_shape(B)
+        sin = None
+        if state is not None:
+            sin = np.ascontiguousarray(state, dtype=np.float64)
+            if sin.shape != shape:
+                raise ValueError(f"state: shape {sin.shape}, expected {shape}")
+        sout = np.zeros(shape, np.float64)
+        mo = max(max_out, 1)
+        tok, ts, lp = np.zeros((B, mo), np.int32), np.zeros((B, mo), np.int32), np.zeros((B, mo), np.float64)
+        cnt, total, gap = np.zeros(B, np.int32), np.zeros(B, np.float64), np.zeros(B, np.float64)
+        check(lib().asr_rnnt_greedy_host(self.h, _ptr(enc), _ptr(ln) if ln is not None else None, T, B, max_out,
+                                         _ptr(sin) if sin is not None else None, _ptr(sout), _ptr(tok), _ptr(ts),
+                                         _ptr(lp), _ptr(cnt), _ptr(total), _ptr(gap) if gaps else None),
+              "asr_rnnt_greedy_host")
+        res = self._unpack(B, max_out, tok, ts, lp, cnt, total), sout, cnt
+        return res + (gap,) if gaps else res
+
+    def close(self) -> None:
+        if self.h:
+            lib().asr_rnnt_destroy(self.h)
+            self.h = None
+        self._work = None
 
     def __del__(self):
         try:

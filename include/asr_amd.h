@@ -1258,6 +1258,110 @@ int asr_ctc_lm_create_word(const int32_t* codes, int V, int beam_width, int blan
                            const asr_lm_t* lm, const asr_lexicon_t* lex, float alpha, float beta, int lm_flags,
                            int top_n, int lex_mode, asr_ctc_lm_t** out);
 
+/* ---- RNN-T (transducer) greedy decoding on the device ----------
+ * The model: an embedding Emb [V][D]; L (1 or 2) LSTM layers of asr_lstm_fwd's
+ * cell (W_ih [in][4Hp], W_hh [Hp][4Hp], b_ih, b_hh [4Hp]; gates i, f, g, o;
+ * (x.W_ih + h.W_hh) + (b_ih + b_hh)); and the joint
+ *   f_t = enc_t.W_enc + b_enc      W_enc [E][J]
+ *   g   = h_top.W_pred + b_pred    W_pred [Hp][J]
+ *   z   = act(f_t + g)             ReLU or tanh
+ *   logit = z.W_out + b_out        W_out [J][V]
+ * all weights in this library's [in][out] layout.  k = argmax logit, the lowest
+ * index among equal maxima (a NaN never wins); logp = logit[k] -
+ * logsumexp(logit).
+ *
+ * The greedy walk of utterance b (length len_b, clamped to [0, T]): with no
+ * state given h = c = 0 and the predictor takes one step on Emb[blank] (NeMo's
+ * blank_as_pad start is the case of a zero row there); with a state given,
+ * (h, c) is used as it stands.  t = 0, n = 0; while t < len_b the joint is
+ * evaluated: k != blank records (k, t, logp), steps the predictor on Emb[k] and
+ * counts n += 1, and at n == max_symbols moves on (t += 1, n = 0) without
+ * another evaluation; k == blank adds its logp to the total only, t += 1,
+ * n = 0.  max_symbols >= 1 is required: there is no unbounded mode.
+ *
+ * Outputs per utterance: tokens, timesteps (frames of this call, from 0) and
+ * token log-probs, rows of max_out; the count of emissions, which keeps
+ * counting past max_out (records beyond max_out are dropped while the walk and
+ * the state go on); the total log-prob (emissions and blanks); the state after
+ * the last frame.  A state is [2][L][B][Hp]: h of every layer, then c.
+ * Streaming: a call ends at a frame boundary (n = 0), so passing a call's
+ * state to the next and adding the frame offset to its timesteps reproduces a
+ * whole decode bit for bit.
+ *
+ * asr_rnnt_create takes host pointers and keeps a host copy (for
+ * asr_rnnt_greedy_host).  Checks, in this order — ASR_ERR_ARG: a NULL
+ * argument; V < 2; blank outside [0, V); a non-positive E, D, Hp, J;
+ * L < 1; max_symbols < 1; act neither ASR_RNNT_ACT_RELU nor _TANH.
+ * ASR_ERR_UNSUPPORTED: L > 2; D, Hp or J not a multiple of 16; the limit of the
+ * decode kernel, whose rows live in LDS:
+ *     64 * (2 * L * (Hp + 4) + (J + 4)) + 4096 <= 160 KiB
+ * (L = 1: up to Hp = J = 816, or e.g. 1024 / 432; L = 2: up to
+ * Hp = J = 480).  Then ASR_ERR_ARG: a NULL weight of a layer in use.
+ * asr_rnnt_upload copies the weights to the current device and computes
+ * Emb.W_ih of layer 0 there (one GEMM under the asr_set_dense_arith setting of
+ * that moment; synchronous; a second call does nothing).
+ * asr_rnnt_workspace_bytes(h, T, B): f [T*B][J] and 16 * (L * Hp + J) floats
+ * per 16 utterances; 0 for a NULL handle, a non-positive size or T*B > INT_MAX.
+ *
+ * asr_rnnt_greedy: device pointers.  d_enc [T*B][E] time-major; d_lengths
+ * int32 [B] or NULL (= T); d_state_in NULL or a state; d_state_out NULL or a
+ * state (may be d_state_in); d_tokens, d_timesteps int32 [B][max_out], d_logp
+ * double [B][max_out] (entries at and beyond the count are not written; the
+ * three may be NULL when max_out = 0); d_count int32 [B]; d_total double [B];
+ * d_work of asr_rnnt_workspace_bytes(h, T, B) bytes, 16-byte aligned.  f for
+ * all T is one GEMM that follows asr_set_dense_arith (bias fused); the walk is
+ * one launch, 16 utterances per workgroup, at most T * (max_symbols + 1) joint
+ * evaluations per utterance by a bound the host sets.  Asynchronous on s, no
+ * allocation, no host synchronisation.  An utterance's bits depend on the
+ * model's shape only, never on B or on the utterances beside it.
+ * asr_rnnt_greedy_host: the same on host memory, one thread, fp64 accumulation
+ * from the fp32 weights; its states and every floating-point output are double
+ * (so that a chunked host decode equals a whole one); h_gap (optional,
+ * double [B]): the smallest gap between the best and the second-best logit met
+ * on the utterance's walk (HUGE_VAL when it evaluated nothing).
+ * Checks of both, in this order, before any HIP call — ASR_ERR_ARG: h, the
+ * encoder output, the count or the total NULL; non-positive T or B;
+ * max_out < 0; max_out > 0 with a NULL token, timestep or log-prob array.
+ * ASR_ERR_UNSUPPORTED: T*B > INT_MAX; T * (max_symbols + 1) >= INT_MAX.
+ * asr_rnnt_greedy only, then: ASR_ERR_ARG for a NULL d_work; ASR_ERR_STATE
+ * when the weights were not uploaded. */
+enum { ASR_RNNT_ACT_RELU = 0, ASR_RNNT_ACT_TANH = 1 };
+#define ASR_RNNT_MAX_LAYERS 2
+typedef struct asr_rnnt asr_rnnt_t;
+typedef struct asr_rnnt_desc {
+    int32_t V, blank, E, D, Hp, L, J, act, max_symbols;
+} asr_rnnt_desc;
+typedef struct asr_rnnt_weights {
+    const float* emb;                          /* [V][D] */
+    const float* w_ih[ASR_RNNT_MAX_LAYERS];    /* [D or Hp][4Hp] */
+    const float* w_hh[ASR_RNNT_MAX_LAYERS];    /* [Hp][4Hp] */
+    const float* b_ih[ASR_RNNT_MAX_LAYERS];    /* [4Hp] */
+    const float* b_hh[ASR_RNNT_MAX_LAYERS];
+    const float* w_enc;                        /* [E][J] */
+    const float* b_enc;
+    const float* w_pred;                       /* [Hp][J] */
+    const float* b_pred;
+    const float* w_out;                        /* [J][V] */
+    const float* b_out;
+} asr_rnnt_weights;
+typedef struct asr_rnnt_info {
+    asr_rnnt_desc desc;
+    int32_t uploaded;      /* 1 after asr_rnnt_upload */
+    int32_t lds_bytes;     /* of the decode kernel */
+    int64_t weight_bytes;  /* of the host copy */
+} asr_rnnt_info;
+int asr_rnnt_create(const asr_rnnt_desc* desc, const asr_rnnt_weights* weights, asr_rnnt_t** out);
+int asr_rnnt_upload(asr_rnnt_t* h);
+int asr_rnnt_get_info(const asr_rnnt_t* h, asr_rnnt_info* info);
+int asr_rnnt_destroy(asr_rnnt_t* h);
+size_t asr_rnnt_workspace_bytes(const asr_rnnt_t* h, int T, int B);
+int asr_rnnt_greedy(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_lengths, int T, int B, int max_out,
+                    const float* d_state_in, float* d_state_out, int32_t* d_tokens, int32_t* d_timesteps,
+                    double* d_logp, int32_t* d_count, double* d_total, void* d_work, asr_stream_t s);
+int asr_rnnt_greedy_host(const asr_rnnt_t* h, const float* h_enc, const int32_t* h_lengths, int T, int B, int max_out,
+                         const double* h_state_in, double* h_state_out, int32_t* h_tokens, int32_t* h_timesteps,
+                         double* h_logp, int32_t* h_count, double* h_total, double* h_gap);
+
 #ifdef __cplusplus
 }
 #endif
