@@ -48,6 +48,10 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           RNN-T greedy decoding, the whole (t, u)
                                           walk in one launch (asr_rnnt_*); no
                                           reference member
+    TransducerDecoder.beam_search(enc, beam=4)
+                                          RNN-T beam search, one symbol per frame,
+                                          the n-best in one launch (asr_rnnt_beam*);
+                                          no reference member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -104,6 +108,7 @@ EXPORTS = [
     "asr_ctc_lm_create_word",
     "asr_rnnt_create", "asr_rnnt_upload", "asr_rnnt_get_info", "asr_rnnt_destroy", "asr_rnnt_workspace_bytes",
     "asr_rnnt_greedy", "asr_rnnt_greedy_host",
+    "asr_rnnt_beam_workspace_bytes", "asr_rnnt_beam", "asr_rnnt_beam_host",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -254,6 +259,8 @@ def lib() -> ctypes.CDLL:
         "asr_rnnt_destroy": [_vp],
         "asr_rnnt_greedy": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_greedy_host": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_beam": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_beam_host": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -288,6 +295,8 @@ def lib() -> ctypes.CDLL:
     L.asr_ctc_align_workspace_bytes.restype = _sz
     L.asr_rnnt_workspace_bytes.argtypes = [_vp, _i, _i]
     L.asr_rnnt_workspace_bytes.restype = _sz
+    L.asr_rnnt_beam_workspace_bytes.argtypes = [_vp, _i, _i, _i]
+    L.asr_rnnt_beam_workspace_bytes.restype = _sz
     _lib = L
     return L
 
@@ -2074,8 +2083,9 @@ class TransducerDecoder:
     """RNN-T greedy decoding (asr_rnnt_*; the walk is defined in
     include/asr_amd.h): an embedding, an LSTM prediction network of one or two
     layers and a joint network, decoded frame by frame in one launch
-    (decode / decode_device) or by the fp64 host twin (decode_host).  No
-    arithmetic here.
+    (decode / decode_device) or by the fp64 host twin (decode_host); and the
+    one-symbol-per-frame beam search on the same handle (beam_search /
+    beam_search_device / beam_search_host).  No arithmetic here.
 
     weights: a dict of fp32 arrays in the library's [in][out] layout: emb
     [V, D]; w_ih, w_hh, b_ih, b_hh: lists of L arrays ([in, 4Hp], [Hp, 4Hp],
@@ -2251,6 +2261,78 @@ class TransducerDecoder:
               "asr_rnnt_greedy_host")
         res = self._unpack(B, max_out, tok, ts, lp, cnt, total), sout, cnt
         return res + (gap,) if gaps else res
+
+    # ---- beam search (asr_rnnt_beam*; the search is defined in include/asr_amd.h)
+    def beam_workspace_bytes(self, T: int, B: int, beam: int) -> int:
+        return int(lib().asr_rnnt_beam_workspace_bytes(self.h, T, B, beam))
+
+    def _beam_prepare(self, enc, lengths, beam, nbest, max_out):
+        enc, ln, T, B, _mo = self._prepare(enc, lengths, 0)
+        nbest = int(beam) if nbest is None else int(nbest)
+        max_out = T if max_out is None else int(max_out)    # one symbol per frame: at most T tokens
+        return enc, ln, T, B, int(beam), nbest, max_out
+
+    @staticmethod
+    def _beam_unpack(B, max_out, tok, ts, ln, score, nhyp):
+        out = []
+        for b in range(B):
+            hyps = []
+            for j in range(int(nhyp[b])):
+                n = min(int(ln[b, j]), max_out)
+                hyps.append((tok[b, j, :n].tolist(), ts[b, j, :n].tolist(), float(score[b, j])))
+            out.append(hyps)
+        return out
+
+    def beam_search_device(self, d_enc: int, T: int, B: int, beam: int, nbest: int, max_out: int, d_tokens: int,
+                           d_timesteps: int, d_len: int, d_score: int, d_nhyp: int, d_work: int, d_lengths: int = 0,
+                           stream: int = 0) -> None:
+        """asr_rnnt_beam on device pointers: asynchronous on stream."""
+        check(lib().asr_rnnt_beam(self.h, d_enc or None, d_lengths or None, T, B, beam, nbest, max_out,
+                                  d_tokens or None, d_timesteps or None, d_len or None, d_score or None,
+                                  d_nhyp or None, d_work or None, stream or None), "asr_rnnt_beam")
+
+    def beam_search(self, enc, lengths=None, beam: int = 4, nbest=None, max_out=None, stream: int = 0):
+        """One-symbol-per-frame beam search of width `beam` (1..16), one launch.
+        enc [T, B, E] time-major.  Returns per utterance a list of (tokens,
+        timesteps, score), best first, at most nbest (default: beam) of them;
+        tokens and timesteps are cut at max_out (default T, the most a search
+        can emit).  The token lists go into nbest_mbr and edit_distance as they
+        are.  desc.max_symbols plays no part."""
+        enc, ln, T, B, beam, nbest, max_out = self._beam_prepare(enc, lengths, beam, nbest, max_out)
+        if not self._uploaded:
+            self.upload()
+        d_enc = _upload(enc, stream)
+        d_lens = _upload(ln, stream) if ln is not None else None
+        mo, nb = max(max_out, 1), max(nbest, 1)
+        d_tok, d_ts = DeviceBytes(4 * B * nb * mo), DeviceBytes(4 * B * nb * mo)
+        d_len, d_sc, d_nh = DeviceBytes(max(4 * B * nb, 16)), DeviceBytes(max(8 * B * nb, 16)), DeviceBytes(max(4 * B, 16))
+        need = self.beam_workspace_bytes(T, B, beam)
+        if need and (self._work is None or self._work.nbytes < need):
+            self._work = DeviceBytes(need)
+        self.beam_search_device(d_enc.ptr, T, B, beam, nbest, max_out, d_tok.ptr, d_ts.ptr, d_len.ptr, d_sc.ptr,
+                                d_nh.ptr, self._work.ptr if self._work else 0, d_lens.ptr if d_lens else 0, stream)
+        check(lib().asr_stream_sync(stream or None), "asr_stream_sync")
+        nhyp = _download(d_nh, (B,), np.int32, stream)
+        hl = _download(d_len, (B, nb), np.int32, stream)
+        sc = _download(d_sc, (B, nb), np.float64, stream)
+        tok = _download(d_tok, (B, nb, mo), np.int32, stream)
+        ts = _download(d_ts, (B, nb, mo), np.int32, stream)
+        return self._beam_unpack(B, max_out, tok, ts, hl, sc, nhyp)
+
+    def beam_search_host(self, enc, lengths=None, beam: int = 4, nbest=None, max_out=None, margins: bool = False):
+        """The same through asr_rnnt_beam_host (one thread, fp64); with margins
+        also the smallest decision margin of each utterance's search (float64
+        [B]; include/asr_amd.h says what counts)."""
+        enc, ln, T, B, beam, nbest, max_out = self._beam_prepare(enc, lengths, beam, nbest, max_out)
+        mo, nb = max(max_out, 1), max(nbest, 1)
+        tok, ts = np.zeros((B, nb, mo), np.int32), np.zeros((B, nb, mo), np.int32)
+        hl, sc, nhyp = np.zeros((B, nb), np.int32), np.zeros((B, nb), np.float64), np.zeros(B, np.int32)
+        margin = np.zeros(B, np.float64)
+        check(lib().asr_rnnt_beam_host(self.h, _ptr(enc), _ptr(ln) if ln is not None else None, T, B, beam, nbest,
+                                       max_out, _ptr(tok), _ptr(ts), _ptr(hl), _ptr(sc), _ptr(nhyp),
+                                       _ptr(margin) if margins else None), "asr_rnnt_beam_host")
+        res = self._beam_unpack(B, max_out, tok, ts, hl, sc, nhyp)
+        return (res, margin) if margins else res
 
     def close(self) -> None:
         if self.h:

@@ -1362,6 +1362,70 @@ int asr_rnnt_greedy_host(const asr_rnnt_t* h, const float* h_enc, const int32_t*
                          const double* h_state_in, double* h_state_out, int32_t* h_tokens, int32_t* h_timesteps,
                          double* h_logp, int32_t* h_count, double* h_total, double* h_gap);
 
+/* RNN-T beam search, one symbol per frame (the "modified beam search" of k2 /
+ * icefall), on an asr_rnnt handle.  The model and the start are the greedy
+ * walk's (h = c = 0, then one predictor step on Emb[blank]); desc.max_symbols
+ * plays no part.
+ *
+ * Utterance b has beam width K, 1 <= K <= 16, and length len_b clamped to
+ * [0, T].  A hypothesis is its tokens ys, one timestep per token, a score (a
+ * log-probability, double) and the predictor state after ys.  The beam A is
+ * ordered by rank and starts as one hypothesis: empty ys, score 0.  Each frame
+ * t < len_b: (1) for every hypothesis i in rank order logit_i = joint(f_t,
+ * h_top_i) and lp_i[v] = logit_i[v] - logsumexp(logit_i); (2) candidate (i, v)
+ * has score s_i + lp_i[v]; (3) the best min(K, |A| V) candidates are kept, in
+ * the order score descending, then i ascending, then v ascending, a NaN score
+ * after every number; (4) a kept (i, blank) is hypothesis i unchanged but for
+ * its score; (5) a kept (i, v != blank) is ys_i + [v] with timestep t and the
+ * state of i stepped on Emb[v]; (6) kept candidates with equal token sequences
+ * merge: the score is logaddexp of the two in double, the timesteps are those
+ * of the constituent with the higher score (the earlier in candidate order on
+ * equal scores); at most two candidates can share a sequence (A + blank and
+ * B + v); sequences are compared as sequences, not by parentage, so a prefix
+ * that was pruned and created again still merges; (7) the new A is the merged
+ * set by score descending, ties by the position of the earlier constituent in
+ * candidate order; it may hold fewer than K hypotheses.  The result is the
+ * final A, best first.  K = 1 is the greedy walk with max_symbols = 1.
+ *
+ * asr_rnnt_beam_workspace_bytes(h, T, B, K): f [T*B][J]; per workgroup of
+ * 16 / R utterances (R the smallest power of two >= K) 16 * (2 * L * Hp + J + V)
+ * floats; per utterance T*K + 1 node records of 16 bytes.  0 for a NULL handle,
+ * a non-positive size, K outside [1, 16], T*B > INT_MAX or T*K + 1 > INT_MAX.
+ *
+ * asr_rnnt_beam: device pointers.  d_enc [T*B][E] time-major; d_lengths int32
+ * [B] or NULL (= T); d_tokens, d_timesteps int32 [B][nbest][max_out] (may be
+ * NULL when max_out = 0; a hypothesis longer than max_out is cut there);
+ * d_len int32 [B][nbest], the uncut lengths; d_score double [B][nbest]; d_nhyp
+ * int32 [B], min(|A|, nbest); entries of hypotheses at and beyond d_nhyp[b] and
+ * tokens at and beyond a length are not written.  len_b = 0 gives one empty
+ * hypothesis with score 0.  d_work of asr_rnnt_beam_workspace_bytes bytes,
+ * 16-byte aligned.  f for all T is one GEMM that follows asr_set_dense_arith;
+ * the search is one launch.  Asynchronous on s, no allocation, no host
+ * synchronisation.  An utterance's bits depend on the model's shape and on K
+ * only, never on B or on the utterances beside it.
+ * asr_rnnt_beam_host: the same on host memory, one thread, fp64 from the fp32
+ * weights, sequences compared as such.  h_margin (optional, double [B]): the
+ * smallest over the utterance's search of (a) the score of the last kept
+ * candidate minus that of the best rejected one, (b) the absolute score
+ * difference of the two constituents of a merge, (c) the gaps between
+ * neighbouring final scores; HUGE_VAL when none occurred.
+ * Checks of both, in this order, before any HIP call — ASR_ERR_ARG: h, the
+ * encoder output, the lengths, scores or counts NULL, or non-positive T or B;
+ * K outside [1, 16]; nbest outside [1, K]; max_out < 0; max_out > 0 with a
+ * NULL token or timestep array.  ASR_ERR_UNSUPPORTED: T*B > INT_MAX or
+ * T*K + 1 > INT_MAX.  asr_rnnt_beam only, then: ASR_ERR_ARG for a NULL d_work;
+ * ASR_ERR_UNSUPPORTED when the search kernel's rows do not fit in LDS,
+ *     64 * (2 * L * (Hp + 4) + (J + 4)) + 8192 <= 160 KiB
+ * (the greedy limit with 8192 in place of 4096, for any K; L = 1: up to
+ * Hp = J = 800); ASR_ERR_STATE when the weights were not uploaded. */
+size_t asr_rnnt_beam_workspace_bytes(const asr_rnnt_t* h, int T, int B, int K);
+int asr_rnnt_beam(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_lengths, int T, int B, int K, int nbest,
+                  int max_out, int32_t* d_tokens, int32_t* d_timesteps, int32_t* d_len, double* d_score,
+                  int32_t* d_nhyp, void* d_work, asr_stream_t s);
+int asr_rnnt_beam_host(const asr_rnnt_t* h, const float* h_enc, const int32_t* h_lengths, int T, int B, int K,
+                       int nbest, int max_out, int32_t* h_tokens, int32_t* h_timesteps, int32_t* h_len,
+                       double* h_score, int32_t* h_nhyp, double* h_margin);
+
 #ifdef __cplusplus
 }
 #endif
