@@ -52,6 +52,10 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           RNN-T beam search, one symbol per frame,
                                           the n-best in one launch (asr_rnnt_beam*);
                                           no reference member
+    TransducerDecoder.beam_search(enc, beam=4, lm=NGramLM, alpha=.., beta=.., tok_of_label=..)
+                                          the same search with the n-gram LM fused
+                                          into every prune (asr_rnnt_lm_*,
+                                          asr_rnnt_beam_lm*); no reference member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -109,6 +113,8 @@ EXPORTS = [
     "asr_rnnt_create", "asr_rnnt_upload", "asr_rnnt_get_info", "asr_rnnt_destroy", "asr_rnnt_workspace_bytes",
     "asr_rnnt_greedy", "asr_rnnt_greedy_host",
     "asr_rnnt_beam_workspace_bytes", "asr_rnnt_beam", "asr_rnnt_beam_host",
+    "asr_rnnt_lm_create", "asr_rnnt_lm_destroy", "asr_rnnt_beam_lm_workspace_bytes", "asr_rnnt_beam_lm",
+    "asr_rnnt_beam_lm_host",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -261,6 +267,10 @@ def lib() -> ctypes.CDLL:
         "asr_rnnt_greedy_host": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_beam": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_beam_host": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_lm_create": [_vp, _vp, _vp, _f, _f, _i, ctypes.POINTER(_vp)],
+        "asr_rnnt_lm_destroy": [_vp],
+        "asr_rnnt_beam_lm": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_beam_lm_host": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -297,6 +307,8 @@ def lib() -> ctypes.CDLL:
     L.asr_rnnt_workspace_bytes.restype = _sz
     L.asr_rnnt_beam_workspace_bytes.argtypes = [_vp, _i, _i, _i]
     L.asr_rnnt_beam_workspace_bytes.restype = _sz
+    L.asr_rnnt_beam_lm_workspace_bytes.argtypes = [_vp, _i, _i, _i]
+    L.asr_rnnt_beam_lm_workspace_bytes.restype = _sz
     _lib = L
     return L
 
@@ -2085,15 +2097,20 @@ class TransducerDecoder:
     layers and a joint network, decoded frame by frame in one launch
     (decode / decode_device) or by the fp64 host twin (decode_host); and the
     one-symbol-per-frame beam search on the same handle (beam_search /
-    beam_search_device / beam_search_host).  No arithmetic here.
+    beam_search_device / beam_search_host), with an NGramLM optionally fused
+    into every prune (the lm keywords; asr_rnnt_lm_*).  No arithmetic here.
 
     weights: a dict of fp32 arrays in the library's [in][out] layout: emb
     [V, D]; w_ih, w_hh, b_ih, b_hh: lists of L arrays ([in, 4Hp], [Hp, 4Hp],
-    [4Hp]); w_enc [E, J], b_enc; w_pred [Hp, J], b_pred; w_out [J, V], b_out."""
+    [4Hp]); w_enc [E, J], b_enc; w_pred [Hp, J], b_pred; w_out [J, V], b_out.
+    labels (optional): label i's string, by which the LM keywords find the LM
+    token of a label when no tok_of_label is given."""
 
-    def __init__(self, desc: RnntDesc, weights: dict):
+    def __init__(self, desc: RnntDesc, weights: dict, labels: Optional[Sequence[str]] = None):
         self.desc = desc
         self.h = None
+        self.labels = list(labels) if labels is not None else None
+        self._fuse = {}
         d = desc
         L = max(0, min(int(d.L), ASR_RNNT_MAX_LAYERS))
         H4 = 4 * d.Hp
@@ -2291,14 +2308,128 @@ class TransducerDecoder:
                                   d_tokens or None, d_timesteps or None, d_len or None, d_score or None,
                                   d_nhyp or None, d_work or None, stream or None), "asr_rnnt_beam")
 
-    def beam_search(self, enc, lengths=None, beam: int = 4, nbest=None, max_out=None, stream: int = 0):
+    # ---- LM fusion (asr_rnnt_lm_* / asr_rnnt_beam_lm*)
+    def lm_tokens(self, lm: "NGramLM", tok_of_label=None) -> np.ndarray:
+        """tok_of_label as int32 [V]; None: every label's string (self.labels)
+        looked up in the model by name, -1 (an OOV) where it has none."""
+        V = int(self.desc.V)
+        if tok_of_label is None:
+            if self.labels is None:
+                raise ValueError("tok_of_label is required: the decoder has no labels")
+            if len(self.labels) != V:
+                raise ValueError(f"labels: {len(self.labels)} strings, expected {V}")
+            tok_of_label = [-1 if v == self.desc.blank else lm.token_id(s) for v, s in enumerate(self.labels)]
+        tok = np.ascontiguousarray(tok_of_label, dtype=np.int32)
+        if tok.shape != (V,):
+            raise ValueError(f"tok_of_label: shape {tok.shape}, expected ({V},)")
+        return tok
+
+    def _lm_handle(self, lm, alpha, beta, tok_of_label, bos, eos) -> int:
+        """The fusion handle of (lm, weights, mapping, flags), made once and kept
+        (with the LM) until close()."""
+        tok = self.lm_tokens(lm, tok_of_label)
+        flags = (ASR_LM_BOS if bos else 0) | (ASR_LM_EOS if eos else 0)
+        key = (lm.h, float(np.float32(alpha)), float(np.float32(beta)), flags, tok.tobytes())
+        if key not in self._fuse:
+            z = _vp()
+            check(lib().asr_rnnt_lm_create(self.h, lm.h, _ptr(tok), float(alpha), float(beta), flags, ctypes.byref(z)),
+                  "asr_rnnt_lm_create")
+            self._fuse[key] = (z.value, lm)
+        return self._fuse[key][0]
+
+    def beam_lm_workspace_bytes(self, fuse: int, T: int, B: int, beam: int) -> int:
+        return int(lib().asr_rnnt_beam_lm_workspace_bytes(fuse, T, B, beam))
+
+    @staticmethod
+    def _beam_lm_unpack(B, max_out, tok, ts, ln, total, am, lml, ntok, nhyp):
+        out = []
+        for b in range(B):
+            hyps = []
+            for j in range(int(nhyp[b])):
+                n = min(int(ln[b, j]), max_out)
+                hyps.append((tok[b, j, :n].tolist(), ts[b, j, :n].tolist(), float(total[b, j]), float(am[b, j]),
+                             float(lml[b, j]), int(ntok[b, j])))
+            out.append(hyps)
+        return out
+
+    def beam_search_lm_device(self, fuse: int, d_enc: int, T: int, B: int, beam: int, nbest: int, max_out: int,
+                              d_tokens: int, d_timesteps: int, d_len: int, d_total: int, d_nhyp: int, d_work: int,
+                              d_am: int = 0, d_lm_log10: int = 0, d_ntok: int = 0, d_lengths: int = 0,
+                              stream: int = 0) -> None:
+        """asr_rnnt_beam_lm on device pointers: asynchronous on stream."""
+        check(lib().asr_rnnt_beam_lm(fuse, d_enc or None, d_lengths or None, T, B, beam, nbest, max_out,
+                                     d_tokens or None, d_timesteps or None, d_len or None, d_total or None,
+                                     d_am or None, d_lm_log10 or None, d_ntok or None, d_nhyp or None,
+                                     d_work or None, stream or None), "asr_rnnt_beam_lm")
+
+    def _beam_search_lm(self, fuse, lm, enc, ln, T, B, beam, nbest, max_out, stream):
+        if not self._uploaded:
+            self.upload()
+        lm.upload()
+        d_enc = _upload(enc, stream)
+        d_lens = _upload(ln, stream) if ln is not None else None
+        mo, nb = max(max_out, 1), max(nbest, 1)
+        d_tok, d_ts = DeviceBytes(4 * B * nb * mo), DeviceBytes(4 * B * nb * mo)
+        d_len, d_nt, d_nh = DeviceBytes(max(4 * B * nb, 16)), DeviceBytes(max(4 * B * nb, 16)), DeviceBytes(max(4 * B, 16))
+        d_tot, d_am, d_lml = (DeviceBytes(max(8 * B * nb, 16)) for _ in range(3))
+        need = self.beam_lm_workspace_bytes(fuse, T, B, beam)
+        if need and (self._work is None or self._work.nbytes < need):
+            self._work = DeviceBytes(need)
+        self.beam_search_lm_device(fuse, d_enc.ptr, T, B, beam, nbest, max_out, d_tok.ptr, d_ts.ptr, d_len.ptr,
+                                   d_tot.ptr, d_nh.ptr, self._work.ptr if self._work else 0, d_am.ptr, d_lml.ptr,
+                                   d_nt.ptr, d_lens.ptr if d_lens else 0, stream)
+        check(lib().asr_stream_sync(stream or None), "asr_stream_sync")
+        nhyp = _download(d_nh, (B,), np.int32, stream)
+        hl = _download(d_len, (B, nb), np.int32, stream)
+        nt = _download(d_nt, (B, nb), np.int32, stream)
+        tot, am, lml = (_download(d, (B, nb), np.float64, stream) for d in (d_tot, d_am, d_lml))
+        tok = _download(d_tok, (B, nb, mo), np.int32, stream)
+        ts = _download(d_ts, (B, nb, mo), np.int32, stream)
+        return self._beam_lm_unpack(B, max_out, tok, ts, hl, tot, am, lml, nt, nhyp)
+
+    def lm_rescore(self, nbest, lm: "NGramLM", alpha: float, beta: float, tok_of_label=None, bos: bool = True,
+                   eos: bool = False, host: bool = False, stream: int = 0):
+        """An n-best of beam_search (without lm) re-ranked after the fact, as
+        CTCDecoder.lm_rescore does: per utterance [(tokens, timesteps, total, am,
+        lm_log10, n_tokens)], total descending (equal totals keep their order),
+            total = am + alpha * ln(10) * lm_log10 + beta * n_tokens,
+        am the hypothesis's score, lm_log10 asr_lm_score's value of its tokens
+        (one launch for the whole batch; host=True: asr_lm_score_host)."""
+        tok = self.lm_tokens(lm, tok_of_label)
+        rows = [[int(tok[y]) for y in h[0]] for u in nbest for h in u]
+        if not rows:
+            return [[] for _ in nbest]
+        if not host:
+            lm.upload()
+        lm_log10, counts = lm.score(rows, bos=bos, eos=eos, host=host, stream=stream)
+        out, k = [], 0
+        for u in nbest:
+            res = []
+            for h in u:
+                n = int(counts[k, 0]) - (1 if eos else 0)
+                res.append((h[0], h[1], lm_total(float(h[2]), float(lm_log10[k]), n, alpha, beta), float(h[2]),
+                            float(lm_log10[k]), n))
+                k += 1
+            out.append(sorted(res, key=lambda r: -r[2]))
+        return out
+
+    def beam_search(self, enc, lengths=None, beam: int = 4, nbest=None, max_out=None, stream: int = 0, lm=None,
+                    alpha: float = 0.0, beta: float = 0.0, tok_of_label=None, bos: bool = True, eos: bool = False):
         """One-symbol-per-frame beam search of width `beam` (1..16), one launch.
         enc [T, B, E] time-major.  Returns per utterance a list of (tokens,
         timesteps, score), best first, at most nbest (default: beam) of them;
         tokens and timesteps are cut at max_out (default T, the most a search
         can emit).  The token lists go into nbest_mbr and edit_distance as they
-        are.  desc.max_symbols plays no part."""
+        are.  desc.max_symbols plays no part.
+        With lm (an NGramLM) the model takes part in every prune with the
+        weights alpha and beta (include/asr_amd.h has the definition) and a
+        hypothesis is (tokens, timesteps, total, am, lm_log10, n_tokens);
+        tok_of_label [V] maps labels to LM tokens (None: by the decoder's label
+        strings), bos / eos are ASR_LM_BOS / ASR_LM_EOS."""
         enc, ln, T, B, beam, nbest, max_out = self._beam_prepare(enc, lengths, beam, nbest, max_out)
+        if lm is not None:
+            fuse = self._lm_handle(lm, alpha, beta, tok_of_label, bos, eos)
+            return self._beam_search_lm(fuse, lm, enc, ln, T, B, beam, nbest, max_out, stream)
         if not self._uploaded:
             self.upload()
         d_enc = _upload(enc, stream)
@@ -2319,15 +2450,27 @@ class TransducerDecoder:
         ts = _download(d_ts, (B, nb, mo), np.int32, stream)
         return self._beam_unpack(B, max_out, tok, ts, hl, sc, nhyp)
 
-    def beam_search_host(self, enc, lengths=None, beam: int = 4, nbest=None, max_out=None, margins: bool = False):
+    def beam_search_host(self, enc, lengths=None, beam: int = 4, nbest=None, max_out=None, margins: bool = False,
+                         lm=None, alpha: float = 0.0, beta: float = 0.0, tok_of_label=None, bos: bool = True,
+                         eos: bool = False):
         """The same through asr_rnnt_beam_host (one thread, fp64); with margins
         also the smallest decision margin of each utterance's search (float64
-        [B]; include/asr_amd.h says what counts)."""
+        [B]; include/asr_amd.h says what counts).  With lm: asr_rnnt_beam_lm_host,
+        the keywords and the hypotheses as in beam_search."""
         enc, ln, T, B, beam, nbest, max_out = self._beam_prepare(enc, lengths, beam, nbest, max_out)
         mo, nb = max(max_out, 1), max(nbest, 1)
         tok, ts = np.zeros((B, nb, mo), np.int32), np.zeros((B, nb, mo), np.int32)
         hl, sc, nhyp = np.zeros((B, nb), np.int32), np.zeros((B, nb), np.float64), np.zeros(B, np.int32)
         margin = np.zeros(B, np.float64)
+        if lm is not None:
+            fuse = self._lm_handle(lm, alpha, beta, tok_of_label, bos, eos)
+            am, lml, nt = np.zeros((B, nb), np.float64), np.zeros((B, nb), np.float64), np.zeros((B, nb), np.int32)
+            check(lib().asr_rnnt_beam_lm_host(fuse, _ptr(enc), _ptr(ln) if ln is not None else None, T, B, beam, nbest,
+                                              max_out, _ptr(tok), _ptr(ts), _ptr(hl), _ptr(sc), _ptr(am), _ptr(lml),
+                                              _ptr(nt), _ptr(nhyp), _ptr(margin) if margins else None),
+                  "asr_rnnt_beam_lm_host")
+            res = self._beam_lm_unpack(B, max_out, tok, ts, hl, sc, am, lml, nt, nhyp)
+            return (res, margin) if margins else res
         check(lib().asr_rnnt_beam_host(self.h, _ptr(enc), _ptr(ln) if ln is not None else None, T, B, beam, nbest,
                                        max_out, _ptr(tok), _ptr(ts), _ptr(hl), _ptr(sc), _ptr(nhyp),
                                        _ptr(margin) if margins else None), "asr_rnnt_beam_host")
@@ -2335,6 +2478,9 @@ class TransducerDecoder:
         return (res, margin) if margins else res
 
     def close(self) -> None:
+        for z, _lm in getattr(self, "_fuse", {}).values():
+            lib().asr_rnnt_lm_destroy(z)
+        self._fuse = {}
         if self.h:
             lib().asr_rnnt_destroy(self.h)
             self.h = None

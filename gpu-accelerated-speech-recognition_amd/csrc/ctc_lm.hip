@@ -103,19 +103,6 @@ __host__ __device__ static inline uint64_t clm_hash(uint64_t h, int c) {
     return x ^ (x >> 29);
 }
 
-// The LM value of token `w` after a prefix whose last m = min(n, 7) tokens are
-// ctx[0..m): exactly lm_position() at position n of the prefix's token row (a
-// context never reaches further back than 7 tokens; <s> is in reach iff n < 7).
-__host__ __device__ static inline double clm_value(const LmTables& t, const int32_t* ctx, int m, int32_t w,
-                                                   bool eos, int flags) {
-    int32_t tk[LM_CTX + 1];
-#pragma unroll
-    for (int j = 0; j < LM_CTX; j++) tk[j] = j < m ? ctx[j] : 0;
-    tk[LM_CTX] = 0;
-    if (!eos) tk[m] = w;
-    return lm_position(t, tk, eos ? m : m + 1, m, flags & ASR_LM_BOS).v;
-}
-
 __device__ __forceinline__ void clm_fold(double& acc, bool& have, double x, bool px) {
     if (!px) return;
     if (!have) {
@@ -287,7 +274,7 @@ __device__ __forceinline__ void clm_search(const ClmArgs& a, const ClmWordArgs& 
                     } else {
                         double v = 0.0, Wn = s_W[o + s];
                         if (sp && z != 0) {   // the space ends a word: the one LM lookup
-                            v = clm_value(a.lm, s_ctx + (o + s) * LM_CTX, min(s_nw[o + s], LM_CTX), lex_word(wa.lex, z),
+                            v = lm_value_after(a.lm, s_ctx + (o + s) * LM_CTX, min(s_nw[o + s], LM_CTX), lex_word(wa.lex, z),
                                           false, a.flags);
                             Wn = Wn + ((a.aln10 * v) + a.beta);
                         }
@@ -296,7 +283,7 @@ __device__ __forceinline__ void clm_search(const ClmArgs& a, const ClmWordArgs& 
                         cv[p] = v;
                     }
                 } else {
-                    const double v = clm_value(a.lm, s_ctx + (o + s) * LM_CTX, min(nq, LM_CTX), a.tok[c], false, a.flags);
+                    const double v = lm_value_after(a.lm, s_ctx + (o + s) * LM_CTX, min(nq, LM_CTX), a.tok[c], false, a.flags);
                     const double Wn = s_W[o + s] + ((a.aln10 * v) + a.beta);
                     ckey[p] = asr_d2key(acc + Wn);
                     cscore[p] = acc;
@@ -532,7 +519,7 @@ __device__ __forceinline__ void clm_search(const ClmArgs& a, const ClmWordArgs& 
                 if (z != 0) {   // the pending word, scored as a space would score it
                     const int m = min(nw, LM_CTX);
                     const int32_t tk = lex_word(wa.lex, z);
-                    const double v = clm_value(a.lm, ctx, m, tk, false, a.flags);
+                    const double v = lm_value_after(a.lm, ctx, m, tk, false, a.flags);
                     W = W + ((a.aln10 * v) + a.beta);
                     L = L + v;
 #pragma unroll
@@ -544,7 +531,7 @@ __device__ __forceinline__ void clm_search(const ClmArgs& a, const ClmWordArgs& 
                 }
                 total = acc + W;
                 if (a.flags & ASR_LM_EOS) {
-                    const double v = clm_value(a.lm, ctx, min(nw, LM_CTX), 0, true, a.flags);
+                    const double v = lm_value_after(a.lm, ctx, min(nw, LM_CTX), 0, true, a.flags);
                     total = total + (a.aln10 * v);
                     L = L + v;
                 }
@@ -553,7 +540,7 @@ __device__ __forceinline__ void clm_search(const ClmArgs& a, const ClmWordArgs& 
                 total = acc + s_W[o + s];
                 L = s_L[o + s];
                 if (a.flags & ASR_LM_EOS) {
-                    const double v = clm_value(a.lm, s_ctx + (o + s) * LM_CTX, min(s_n[o + s], LM_CTX), 0, true, a.flags);
+                    const double v = lm_value_after(a.lm, s_ctx + (o + s) * LM_CTX, min(s_n[o + s], LM_CTX), 0, true, a.flags);
                     total = total + (a.aln10 * v);
                     L = L + v;
                 }
@@ -809,7 +796,7 @@ static bool clm_decode_one(const asr_ctc_lm* h, const LmTables& lm, const float*
     auto scored = [&](const ClmPrefix& q, int32_t tk) {
         ClmPrefix c = q;
         const int m = std::min(q.n, LM_CTX);
-        const double v = clm_value(lm, q.ctx, m, tk, false, h->flags);
+        const double v = lm_value_after(lm, q.ctx, m, tk, false, h->flags);
         c.W = q.W + ((h->aln10 * v) + h->beta);
         c.L = q.L + v;
         c.n = q.n + 1;
@@ -964,7 +951,7 @@ static bool clm_decode_one(const asr_ctc_lm* h, const LmTables& lm, const float*
         hy.lm = q.L;
         hy.n = q.n;
         if (h->flags & ASR_LM_EOS) {
-            const double v = clm_value(lm, q.ctx, std::min(q.n, LM_CTX), 0, true, h->flags);
+            const double v = lm_value_after(lm, q.ctx, std::min(q.n, LM_CTX), 0, true, h->flags);
             hy.total = hy.total + (h->aln10 * v);
             hy.lm = hy.lm + v;
         }

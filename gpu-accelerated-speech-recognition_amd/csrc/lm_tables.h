@@ -1,6 +1,6 @@
 // The back-off n-gram model's tables and the per-token lookup, shared by the
-// scorer (lm.hip) and the LM-fused beam search (ctc_lm.hip).  The layout and the
-// two walks are described at the head of lm.hip.
+// scorer (lm.hip) and the LM-fused beam searches (ctc_lm.hip, rnnt_beam.hip).
+// The layout and the two walks are described at the head of lm.hip.
 #pragma once
 #include "asr_internal.h"
 
@@ -139,6 +139,19 @@ __host__ __device__ static inline LmTok lm_position(const LmTables& t, const int
     r.v = v;
     r.order = q;
     return r;
+}
+
+// The LM value of token `w` after a prefix whose last m = min(n, 7) tokens are
+// ctx[0..m): exactly lm_position() at position n of the prefix's token row (a
+// context never reaches further back than 7 tokens; <s> is in reach iff n < 7).
+__host__ __device__ static inline double lm_value_after(const LmTables& t, const int32_t* ctx, int m, int32_t w,
+                                                        bool eos, int flags) {
+    int32_t tk[LM_CTX + 1];
+#pragma unroll
+    for (int j = 0; j < LM_CTX; j++) tk[j] = j < m ? ctx[j] : 0;
+    tk[LM_CTX] = 0;
+    if (!eos) tk[m] = w;
+    return lm_position(t, tk, eos ? m : m + 1, m, flags & ASR_LM_BOS).v;
 }
 
 }  // namespace asr

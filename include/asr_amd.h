@@ -1426,6 +1426,85 @@ int asr_rnnt_beam_host(const asr_rnnt_t* h, const float* h_enc, const int32_t* h
                        int nbest, int max_out, int32_t* h_tokens, int32_t* h_timesteps, int32_t* h_len,
                        double* h_score, int32_t* h_nhyp, double* h_margin);
 
+/* RNN-T beam search with n-gram LM shallow fusion: the LM takes part in every
+ * per-frame prune.  The search is the one above, steps (1) to
+ * (7); only what the prune and the rankings compare changes, by the conventions
+ * of asr_ctc_lm_*.
+ *
+ * Tokens.  tok_of_label[V] maps every non-blank label to one LM token id; the
+ * blank's entry is ignored.  An id outside [0, vocab) is an OOV under
+ * asr_lm_score's rule: it scores as <unk> if the model has one, else as
+ * oov_log10 at order 0, and it cuts the context.
+ *
+ * LM weight of a hypothesis.  aln10 = (double)alpha * 2.302585092994046, once
+ * on the host.  For tokens ys = y1..yn let v_i be the per-token value of
+ * asr_lm_score at position i of the row tok(y1)..tok(yi), ASR_LM_BOS as
+ * configured and ASR_LM_EOS off.  Then
+ *     W(empty) = 0.0,  W(ys + [y]) = W(ys) + ((aln10 * v) + beta),
+ *     L(empty) = 0.0,  L(ys + [y]) = L(ys) + v,  n = len(ys),
+ * every operation a rounded fp64 operation, no fma.  W, L and n depend on the
+ * sequence only, so the two constituents of a merge carry equal W and L bit for
+ * bit.
+ *
+ * A hypothesis carries its acoustic score s (the score of the search above), W
+ * and L; its fused score is s + W.  Candidate (i, blank) has acoustic
+ * s_i + lp_i[blank] and weight W_i; candidate (i, v) has acoustic s_i + lp_i[v]
+ * and weight W(ys_i + [v]).  Candidates are kept and ordered by fused =
+ * acoustic + weight, ties as above (i ascending, then v ascending, a NaN last).
+ * A merge takes logaddexp of the two acoustic scores in double; the timesteps
+ * are those of the constituent with the higher fused score (the earlier on
+ * equal ones).  The new A is ordered by fused score, ties by the earlier
+ * constituent.
+ *
+ * Result.  total = s + W; with ASR_LM_EOS total = (s + W) + (aln10 * v_eos),
+ * v_eos the value of </s> after ys: no beta, not counted in n, added into L.
+ * The final A is ranked again by total descending, ties by rank in A, and cut
+ * at nbest.  Each hypothesis returns tokens, timesteps, length, total, am = s,
+ * lm_log10 = L and n_tokens = n.  len_b = 0 gives one empty hypothesis with
+ * am = 0 and total 0 or the </s> term.  With alpha = beta = 0 and no
+ * ASR_LM_EOS every W is exactly 0.0 and the search is asr_rnnt_beam's: equal
+ * bytes in tokens, timesteps, lengths, counts and scores.
+ *
+ * asr_rnnt_lm_create: host only, no HIP call; the model and the LM must outlive
+ * the handle; tok_of_label (V entries) is copied.  Checks, in this order —
+ * ASR_ERR_ARG: out NULL; the model, the LM or tok_of_label NULL; alpha negative
+ * or not finite, beta not finite; a flag other than ASR_LM_BOS | ASR_LM_EOS; a
+ * flag whose token (<s>, </s>) the model does not have.
+ *
+ * asr_rnnt_beam_lm_workspace_bytes(z, T, B, K): asr_rnnt_beam_workspace_bytes
+ * plus, per workgroup, 16 LM rows of V doubles; 0 in the same cases and for a
+ * NULL handle.
+ *
+ * asr_rnnt_beam_lm: device pointers, as asr_rnnt_beam with d_total in place of
+ * d_score; d_am, d_lm_log10 (double [B][nbest]) and d_ntok (int32 [B][nbest])
+ * may each be NULL.  One GEMM and one launch, asynchronous on s, no host
+ * synchronisation; the first call on a handle copies tok_of_label to the
+ * device (one allocation, synchronous), every later call allocates nothing.
+ * An utterance's bits depend on the model's shape, K, the LM and the weights
+ * only, never on B or on the utterances beside it.
+ * asr_rnnt_beam_lm_host: the same on host memory over the LM's host tables, one
+ * thread, fp64.  h_margin (optional, double [B]) is asr_rnnt_beam_host's over
+ * fused scores: (a) the last kept candidate against the best rejected one,
+ * (b) the difference of a merge's constituents, (c) the gaps between
+ * neighbouring final totals.
+ * Checks of both, in this order, before any HIP call — ASR_ERR_ARG for a NULL
+ * handle; then asr_rnnt_beam's checks with the totals in the scores' place.
+ * asr_rnnt_beam_lm only, then: ASR_ERR_ARG for a NULL d_work;
+ * ASR_ERR_UNSUPPORTED beyond asr_rnnt_beam's LDS limit; ASR_ERR_STATE when the
+ * weights (asr_rnnt_upload) or the LM (asr_lm_upload) were not uploaded. */
+typedef struct asr_rnnt_lm asr_rnnt_lm_t;
+int asr_rnnt_lm_create(const asr_rnnt_t* model, const asr_lm_t* lm, const int32_t* tok_of_label, float alpha,
+                       float beta, int lm_flags, asr_rnnt_lm_t** out);
+int asr_rnnt_lm_destroy(asr_rnnt_lm_t* z);
+size_t asr_rnnt_beam_lm_workspace_bytes(const asr_rnnt_lm_t* z, int T, int B, int K);
+int asr_rnnt_beam_lm(asr_rnnt_lm_t* z, const float* d_enc, const int32_t* d_lengths, int T, int B, int K, int nbest,
+                     int max_out, int32_t* d_tokens, int32_t* d_timesteps, int32_t* d_len, double* d_total,
+                     double* d_am, double* d_lm_log10, int32_t* d_ntok, int32_t* d_nhyp, void* d_work, asr_stream_t s);
+int asr_rnnt_beam_lm_host(const asr_rnnt_lm_t* z, const float* h_enc, const int32_t* h_lengths, int T, int B, int K,
+                          int nbest, int max_out, int32_t* h_tokens, int32_t* h_timesteps, int32_t* h_len,
+                          double* h_total, double* h_am, double* h_lm_log10, int32_t* h_ntok, int32_t* h_nhyp,
+                          double* h_margin);
+
 #ifdef __cplusplus
 }
 #endif

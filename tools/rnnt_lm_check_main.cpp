@@ -1,0 +1,502 @@
+// The host code of the LM-fused transducer beam search as a stand-alone program
+// for a sanitizer build on the CPU (`make -C gpu-accelerated-speech-recognition_amd
+// rnntlmcheck` compiles csrc/rnnt_beam.hip, csrc/rnnt.hip, csrc/lm.hip and this
+// file with -fsanitize=address,undefined and runs the result).  It runs random
+// small models with random ARPA models of order 1 to 4 through
+// asr_rnnt_beam_lm_host in heap buffers of the exact size against a restatement
+// written here (column-wise dot products in another summation order, candidates
+// merged by comparing whole token sequences, the per-token LM values taken from
+// asr_lm_score_host), alpha = beta = 0 against asr_rnnt_beam_host, K = 1, and
+// every refusal of the asr_rnnt_lm_* / asr_rnnt_beam_lm* entry points.  No HIP
+// call is made; no GPU is needed or used.
+#include "asr_amd.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <random>
+#include <string>
+#include <vector>
+
+static int failures = 0;
+#define EXPECT(expr, want)                                                              \
+    do {                                                                                \
+        const long got_ = (long)(expr);                                                 \
+        if (got_ != (long)(want)) {                                                     \
+            std::printf("FAIL %s:%d %s: got %ld, want %ld\n", __FILE__, __LINE__, #expr, got_, (long)(want)); \
+            failures++;                                                                 \
+        }                                                                               \
+    } while (0)
+#define EXPECT_TRUE(expr) EXPECT(!!(expr), 1)
+
+struct Model {
+    asr_rnnt_desc d;
+    std::vector<float> emb, wih[2], whh[2], bih[2], bhh[2], wenc, benc, wpred, bpred, wout, bout;
+    asr_rnnt_weights ptrs() const {
+        asr_rnnt_weights w{};
+        w.emb = emb.data();
+        for (int l = 0; l < d.L && l < 2; l++) {
+            w.w_ih[l] = wih[l].data();
+            w.w_hh[l] = whh[l].data();
+            w.b_ih[l] = bih[l].data();
+            w.b_hh[l] = bhh[l].data();
+        }
+        w.w_enc = wenc.data(); w.b_enc = benc.data();
+        w.w_pred = wpred.data(); w.b_pred = bpred.data();
+        w.w_out = wout.data(); w.b_out = bout.data();
+        return w;
+    }
+};
+
+static std::mt19937 rng(4321);
+static void fill(std::vector<float>& v, size_t n, float bound) {
+    std::uniform_real_distribution<float> u(-bound, bound);
+    v.resize(n);
+    for (float& x : v) x = u(rng);
+}
+
+static Model make_model(int V, int blank, int E, int D, int Hp, int L, int J, int act) {
+    Model m;
+    m.d = asr_rnnt_desc{V, blank, E, D, Hp, L, J, act, 1};
+    const float k = 1.0f / std::sqrt((float)Hp);
+    fill(m.emb, (size_t)V * D, 1.0f);
+    for (int l = 0; l < L && l < 2; l++) {
+        fill(m.wih[l], (size_t)(l ? Hp : D) * 4 * Hp, k);
+        fill(m.whh[l], (size_t)Hp * 4 * Hp, k);
+        fill(m.bih[l], 4 * (size_t)Hp, k);
+        fill(m.bhh[l], 4 * (size_t)Hp, k);
+    }
+    fill(m.wenc, (size_t)E * J, std::sqrt(3.0f / E));
+    fill(m.benc, J, 0.1f);
+    fill(m.wpred, (size_t)Hp * J, 4.0f * std::sqrt(3.0f / Hp));
+    fill(m.bpred, J, 0.1f);
+    fill(m.wout, (size_t)J * V, 4.0f * std::sqrt(3.0f / J));
+    fill(m.bout, V, 0.1f);
+    m.bout[blank] = 2.0f;
+    return m;
+}
+
+// ---- a restatement of the search: dot products column by column, long double sums
+static double dotcol(const std::vector<double>& x, const float* W, int K, int N, int n) {
+    long double s = 0;
+    for (int k = K - 1; k >= 0; k--) s += (long double)x[k] * (long double)W[(size_t)k * N + n];
+    return (double)s;
+}
+static double sigm(double v) { return 1.0 / (1.0 + std::exp(-v)); }
+static void ref_step(const Model& m, int tok, std::vector<double>& h, std::vector<double>& c) {
+    const int Hp = m.d.Hp;
+    std::vector<double> x(m.emb.begin() + (size_t)tok * m.d.D, m.emb.begin() + (size_t)(tok + 1) * m.d.D);
+    for (int l = 0; l < m.d.L; l++) {
+        std::vector<double> hl(h.begin() + (size_t)l * Hp, h.begin() + (size_t)(l + 1) * Hp), z(4 * Hp);
+        for (int n = 0; n < 4 * Hp; n++)
+            z[n] = (dotcol(x, m.wih[l].data(), (int)x.size(), 4 * Hp, n) + dotcol(hl, m.whh[l].data(), Hp, 4 * Hp, n)) +
+                   ((double)m.bih[l][n] + (double)m.bhh[l][n]);
+        x.resize(Hp);
+        for (int n = 0; n < Hp; n++) {
+            const double cn = sigm(z[Hp + n]) * c[(size_t)l * Hp + n] + sigm(z[n]) * std::tanh(z[2 * Hp + n]);
+            c[(size_t)l * Hp + n] = cn;
+            x[n] = h[(size_t)l * Hp + n] = sigm(z[3 * Hp + n]) * std::tanh(cn);
+        }
+    }
+}
+
+struct Hyp {
+    std::vector<int> ys, ts;
+    double score = 0, W = 0, Lg = 0;
+    std::vector<double> h, c;
+};
+struct Cand {
+    double fused, ac, w, val;
+    int i, v;
+};
+static bool before(double sa, long ia, double sb, long ib) {
+    if (sa > sb) return true;
+    if (sa < sb) return false;
+    const bool na = sa != sa, nb = sb != sb;
+    if (na != nb) return nb;
+    return ia < ib;
+}
+
+struct Fuse {
+    const asr_lm_t* lm;
+    std::vector<int32_t> tok;
+    double aln10, beta;
+    int flags;
+};
+// asr_lm_score_host's value of the last token of tok(ys) + [tok(v)] (v < 0: of </s> after ys)
+static double lm_value(const Fuse& z, const std::vector<int>& ys, int v) {
+    std::vector<int32_t> row;
+    for (int y : ys) row.push_back(z.tok[(size_t)y]);
+    if (v >= 0) row.push_back(z.tok[(size_t)v]);
+    const int32_t len = (int32_t)row.size();
+    const long ld = len + 1;
+    std::vector<int32_t> pad(row);
+    pad.resize((size_t)ld, 0);
+    std::vector<double> tl((size_t)ld);
+    std::vector<int32_t> to((size_t)ld);
+    double logp;
+    int32_t counts[2];
+    const int flags = (z.flags & ASR_LM_BOS) | (v < 0 ? ASR_LM_EOS : 0);
+    EXPECT(asr_lm_score_host(z.lm, pad.data(), ld, &len, 1, len, flags, &logp, counts, tl.data(), to.data(), ld), ASR_OK);
+    return tl[(size_t)(v < 0 ? len : len - 1)];
+}
+static double weight(double W, double aln10, double v, double beta) {
+    volatile double x = aln10 * v;
+    volatile double y = x + beta;
+    return W + y;
+}
+
+struct Final {
+    Hyp h;
+    double total;
+};
+// The final ranking of utterance b; *margin as asr_rnnt_beam_lm_host's h_margin.
+static std::vector<Final> ref_search(const Model& m, const Fuse& z, const float* enc, int T, int B, int b, int len, int K,
+                                     double* margin) {
+    const asr_rnnt_desc& d = m.d;
+    std::vector<Hyp> A(1);
+    A[0].h.assign((size_t)d.L * d.Hp, 0.0);
+    A[0].c.assign((size_t)d.L * d.Hp, 0.0);
+    ref_step(m, d.blank, A[0].h, A[0].c);
+    len = len < 0 ? 0 : (len > T ? T : len);
+    *margin = HUGE_VAL;
+    for (int t = 0; t < len; t++) {
+        std::vector<double> e(enc + ((size_t)t * B + b) * d.E, enc + ((size_t)t * B + b + 1) * d.E), f(d.J);
+        for (int j = 0; j < d.J; j++) f[j] = dotcol(e, m.wenc.data(), d.E, d.J, j) + (double)m.benc[j];
+        std::vector<Cand> cands;
+        for (int i = 0; i < (int)A.size(); i++) {
+            std::vector<double> ht(A[i].h.begin() + (size_t)(d.L - 1) * d.Hp, A[i].h.end()), zz(d.J), logit(d.V);
+            for (int j = 0; j < d.J; j++) {
+                const double v = f[j] + (dotcol(ht, m.wpred.data(), d.Hp, d.J, j) + (double)m.bpred[j]);
+                zz[j] = d.act == ASR_RNNT_ACT_TANH ? std::tanh(v) : (v > 0 ? v : 0);
+            }
+            double top = -HUGE_VAL, se = 0;
+            for (int v = 0; v < d.V; v++) {
+                logit[v] = dotcol(zz, m.wout.data(), d.J, d.V, v) + (double)m.bout[v];
+                top = std::max(top, logit[v]);
+            }
+            for (int v = 0; v < d.V; v++) se += std::exp(logit[v] - top);
+            for (int v = 0; v < d.V; v++) {
+                const double ac = A[i].score + (logit[v] - (top + std::log(se)));
+                const double val = v == d.blank ? 0.0 : lm_value(z, A[i].ys, v);
+                const double w = v == d.blank ? A[i].W : weight(A[i].W, z.aln10, val, z.beta);
+                cands.push_back(Cand{ac + w, ac, w, val, i, v});
+            }
+        }
+        const long V = d.V;
+        std::sort(cands.begin(), cands.end(),
+                  [V](const Cand& x, const Cand& y) { return before(x.fused, x.i * V + x.v, y.fused, y.i * V + y.v); });
+        const size_t nk = std::min((size_t)K, cands.size());
+        if (cands.size() > nk) *margin = std::min(*margin, cands[nk - 1].fused - cands[nk].fused);
+        // whole sequences, merged with whatever earlier entry holds the same one
+        std::vector<Hyp> N;
+        std::vector<int> step_tok;      // the token the entry still has to step on, -1: none
+        for (size_t j = 0; j < nk; j++) {
+            Hyp x = A[cands[j].i];
+            x.score = cands[j].ac;
+            x.W = cands[j].w;
+            int tok = -1;
+            if (cands[j].v != d.blank) {
+                x.ys.push_back(cands[j].v);
+                x.ts.push_back(t);
+                x.Lg = x.Lg + cands[j].val;
+                tok = cands[j].v;
+            }
+            size_t q = 0;
+            while (q < N.size() && N[q].ys != x.ys) q++;
+            if (q == N.size()) {
+                N.push_back(x);
+                step_tok.push_back(tok);
+                continue;
+            }
+            EXPECT_TRUE(N[q].W == x.W && N[q].Lg == x.Lg);   // functions of the sequence alone
+            const double fq = N[q].score + N[q].W, fx = x.score + x.W;
+            *margin = std::min(*margin, std::fabs(fq - fx));
+            const double hi = std::max(N[q].score, x.score), lo = std::min(N[q].score, x.score);
+            if (fx > fq) N[q].ts = x.ts;
+            if (step_tok[q] >= 0 && tok < 0) {   // take the state that is already the sequence's
+                N[q].h = x.h;
+                N[q].c = x.c;
+                step_tok[q] = -1;
+            }
+            N[q].score = hi + std::log1p(std::exp(lo - hi));
+        }
+        for (size_t q = 0; q < N.size(); q++)
+            if (step_tok[q] >= 0) ref_step(m, step_tok[q], N[q].h, N[q].c);
+        std::stable_sort(N.begin(), N.end(),
+                         [](const Hyp& x, const Hyp& y) { return before(x.score + x.W, 0, y.score + y.W, 0); });
+        A.swap(N);
+    }
+    std::vector<Final> out;
+    for (const Hyp& a : A) {
+        Final f{a, a.score + a.W};
+        if (z.flags & ASR_LM_EOS) {
+            const double ve = lm_value(z, a.ys, -1);
+            volatile double term = z.aln10 * ve;
+            f.total = f.total + term;
+            f.h.Lg = f.h.Lg + ve;
+        }
+        out.push_back(f);
+    }
+    std::stable_sort(out.begin(), out.end(), [](const Final& x, const Final& y) { return before(x.total, 0, y.total, 0); });
+    for (size_t j = 0; j + 1 < out.size(); j++) *margin = std::min(*margin, out[j].total - out[j + 1].total);
+    return out;
+}
+
+static bool close(double a, double b) { return std::fabs(a - b) <= 1e-9 * (1.0 + std::fabs(b)); }
+
+// A random ARPA text over w0 .. w(n-1), <s>, </s> and optionally <unk>: prefix-closed, not suffix-closed.
+static std::string random_arpa(int n, int order, bool unk) {
+    std::vector<std::string> names;
+    for (int i = 0; i < n; i++) names.push_back("w" + std::to_string(i));
+    names.push_back("<s>");
+    names.push_back("</s>");
+    if (unk) names.push_back("<unk>");
+    const int V = (int)names.size(), bos = n, eos = n + 1;
+    std::uniform_real_distribution<float> up(-4.f, 0.f), ub(-2.f, 0.5f);
+    std::vector<std::vector<std::vector<int>>> levels(1);
+    for (int i = 0; i < V; i++) levels[0].push_back({i});
+    for (int k = 2; k <= order; k++) {
+        std::vector<std::vector<int>> got;
+        for (int tries = 0; tries < 12 * n; tries++) {
+            std::vector<int> g = levels.back()[rng() % levels.back().size()];
+            const int w = (int)(rng() % V);
+            if (g.back() == eos || w == bos) continue;
+            g.push_back(w);
+            if (std::find(got.begin(), got.end(), g) == got.end()) got.push_back(g);
+        }
+        if (got.empty()) break;
+        levels.push_back(got);
+    }
+    std::string s = "\n\\data\\\n";
+    for (size_t k = 0; k < levels.size(); k++) s += "ngram " + std::to_string(k + 1) + "=" + std::to_string(levels[k].size()) + "\n";
+    char buf[64];
+    for (size_t k = 0; k < levels.size(); k++) {
+        s += "\n\\" + std::to_string(k + 1) + "-grams:\n";
+        for (const auto& g : levels[k]) {
+            std::snprintf(buf, sizeof buf, "%.9g\t", up(rng));
+            s += buf;
+            for (size_t x = 0; x < g.size(); x++) s += (x ? " " : "") + names[(size_t)g[x]];
+            if (k + 1 < levels.size() && rng() % 5) {
+                std::snprintf(buf, sizeof buf, "\t%.9g", ub(rng));
+                s += buf;
+            }
+            s += "\n";
+        }
+    }
+    return s + "\n\\end\\\n";
+}
+
+struct Out {
+    std::vector<int32_t> tok, ts, len, nhyp, ntok;
+    std::vector<double> total, am, lml, margin;
+    Out(int B, int nbest, int max_out)
+        : tok((size_t)B * nbest * max_out), ts((size_t)B * nbest * max_out), len((size_t)B * nbest), nhyp(B),
+          ntok((size_t)B * nbest), total((size_t)B * nbest), am((size_t)B * nbest), lml((size_t)B * nbest), margin(B) {}
+};
+
+static void random_searches() {
+    std::uniform_real_distribution<float> u(-1.f, 1.f);
+    int compared = 0, skipped = 0, short_seen = 0;
+    for (int trial = 0; trial < 80; trial++) {
+        const int L = 1 + trial % 2, act = (trial / 2) % 2, V = 3 + (int)(rng() % 6), K = 1 + (int)(rng() % 6);
+        const int T = 1 + (int)(rng() % 5), B = 1 + (int)(rng() % 3), blank = (int)(rng() % V);
+        const int order = 1 + trial % 4;
+        const bool unk = (trial / 4) % 2;
+        const Model m = make_model(V, blank, 8, 16, 16, L, 16, act);
+        asr_rnnt_weights w = m.ptrs();
+        asr_rnnt_t* h = nullptr;
+        EXPECT(asr_rnnt_create(&m.d, &w, &h), ASR_OK);
+        const std::string text = random_arpa(V - 1, order, unk);
+        asr_lm_t* lm = nullptr;
+        EXPECT(asr_lm_create_arpa_mem(text.data(), text.size(), -3.0f, &lm), ASR_OK);
+        if (!h || !lm) return;
+        Fuse z;
+        z.lm = lm;
+        z.tok.assign((size_t)V, -1);
+        for (int v = 0, k = 0; v < V; v++) {
+            if (v == blank) continue;
+            const std::string name = "w" + std::to_string(k++);
+            EXPECT(asr_lm_token_id(lm, name.c_str(), &z.tok[(size_t)v]), ASR_OK);
+            if (rng() % 7 == 0) z.tok[(size_t)v] = (rng() % 2) ? -1 : 1000;   // an OOV
+        }
+        const float alpha = 0.1f * (float)(rng() % 12), beta = 0.25f * (float)(rng() % 5) - 0.5f;
+        z.aln10 = (double)alpha * 2.302585092994046;
+        z.beta = (double)beta;
+        z.flags = (int)(rng() % 4);
+        asr_rnnt_lm_t* fz = nullptr;
+        EXPECT(asr_rnnt_lm_create(h, lm, z.tok.data(), alpha, beta, z.flags, &fz), ASR_OK);
+        if (!fz) return;
+        std::vector<float> enc((size_t)T * B * m.d.E);
+        for (float& x : enc) x = u(rng);
+        std::vector<int32_t> lens(B);
+        for (int b = 0; b < B; b++) lens[b] = (int)(rng() % (T + 3)) - 1;   // -1 .. T + 1: clamped
+        const int nbest = 1 + (int)(rng() % K), max_out = (int)(rng() % (T + 1));
+        Out full(B, K, T), cut(B, nbest, max_out);
+        EXPECT(asr_rnnt_beam_lm_host(fz, enc.data(), lens.data(), T, B, K, K, T, full.tok.data(), full.ts.data(),
+                                     full.len.data(), full.total.data(), full.am.data(), full.lml.data(), full.ntok.data(),
+                                     full.nhyp.data(), full.margin.data()), ASR_OK);
+        EXPECT(asr_rnnt_beam_lm_host(fz, enc.data(), lens.data(), T, B, K, nbest, max_out, max_out ? cut.tok.data() : nullptr,
+                                     max_out ? cut.ts.data() : nullptr, cut.len.data(), cut.total.data(), nullptr, nullptr,
+                                     nullptr, cut.nhyp.data(), nullptr), ASR_OK);
+        for (int b = 0; b < B; b++) {
+            const int nh = full.nhyp[b];
+            EXPECT(cut.nhyp[b], std::min(nh, nbest));
+            for (int j = 0; j < cut.nhyp[b]; j++) {
+                EXPECT(cut.len[(size_t)b * nbest + j], full.len[(size_t)b * K + j]);
+                EXPECT_TRUE(cut.total[(size_t)b * nbest + j] == full.total[(size_t)b * K + j]);
+                for (int x = 0; x < std::min(max_out, (int)full.len[(size_t)b * K + j]); x++) {
+                    EXPECT(cut.tok[((size_t)b * nbest + j) * max_out + x], full.tok[((size_t)b * K + j) * T + x]);
+                    EXPECT(cut.ts[((size_t)b * nbest + j) * max_out + x], full.ts[((size_t)b * K + j) * T + x]);
+                }
+            }
+            double margin;
+            const std::vector<Final> ref = ref_search(m, z, enc.data(), T, B, b, lens[b], K, &margin);
+            if (margin < 1e-6 || full.margin[b] < 1e-6) {   // a near-tie: the two summation orders may part
+                skipped++;
+                continue;
+            }
+            compared++;
+            EXPECT(nh, ref.size());
+            EXPECT_TRUE(close(full.margin[b], margin) || (std::isinf(margin) && std::isinf(full.margin[b])));
+            if (lens[b] >= 1 && nh < std::min(K, V)) short_seen++;
+            for (int j = 0; j < nh && j < (int)ref.size(); j++) {
+                const size_t o = (size_t)b * K + j;
+                EXPECT(full.len[o], ref[j].h.ys.size());
+                EXPECT(full.ntok[o], ref[j].h.ys.size());
+                EXPECT_TRUE(close(full.am[o], ref[j].h.score));
+                EXPECT_TRUE(close(full.total[o], ref[j].total));
+                EXPECT_TRUE(full.lml[o] == ref[j].h.Lg);
+                for (int x = 0; x < full.len[o] && x < (int)ref[j].h.ys.size(); x++) {
+                    EXPECT(full.tok[o * T + x], ref[j].h.ys[x]);
+                    EXPECT(full.ts[o * T + x], ref[j].h.ts[x]);
+                }
+            }
+        }
+        // alpha = beta = 0 without </s>: asr_rnnt_beam_host in every array; at K = 1 too
+        asr_rnnt_lm_t* zero = nullptr;
+        EXPECT(asr_rnnt_lm_create(h, lm, z.tok.data(), 0.f, 0.f, z.flags & ASR_LM_BOS, &zero), ASR_OK);
+        if (!zero) return;
+        for (int k : {K, 1}) {
+            Out a(B, k, T), p(B, k, T);
+            EXPECT(asr_rnnt_beam_lm_host(zero, enc.data(), lens.data(), T, B, k, k, T, a.tok.data(), a.ts.data(), a.len.data(),
+                                         a.total.data(), a.am.data(), a.lml.data(), a.ntok.data(), a.nhyp.data(),
+                                         a.margin.data()), ASR_OK);
+            EXPECT(asr_rnnt_beam_host(h, enc.data(), lens.data(), T, B, k, k, T, p.tok.data(), p.ts.data(), p.len.data(),
+                                      p.total.data(), p.nhyp.data(), p.margin.data()), ASR_OK);
+            EXPECT_TRUE(a.tok == p.tok && a.ts == p.ts && a.len == p.len && a.nhyp == p.nhyp);
+            for (int b = 0; b < B; b++) {
+                EXPECT_TRUE(a.margin[b] == p.margin[b]);
+                for (int j = 0; j < a.nhyp[b]; j++) {
+                    EXPECT_TRUE(a.total[(size_t)b * k + j] == p.total[(size_t)b * k + j]);
+                    EXPECT_TRUE(a.am[(size_t)b * k + j] == p.total[(size_t)b * k + j]);
+                    EXPECT(a.ntok[(size_t)b * k + j], a.len[(size_t)b * k + j]);
+                }
+            }
+        }
+        EXPECT(asr_rnnt_lm_destroy(zero), ASR_OK);
+        EXPECT(asr_rnnt_lm_destroy(fz), ASR_OK);
+        EXPECT(asr_lm_destroy(lm), ASR_OK);
+        EXPECT(asr_rnnt_destroy(h), ASR_OK);
+    }
+    std::printf("random searches: %d utterances compared, %d skipped at a near-tie, %d ended short of K\n", compared,
+                skipped, short_seen);
+    EXPECT_TRUE(compared > 60 && short_seen > 0);
+}
+
+static void refusals() {
+    const Model m = make_model(5, 0, 8, 16, 16, 1, 16, ASR_RNNT_ACT_RELU);
+    asr_rnnt_weights w = m.ptrs();
+    asr_rnnt_t* h = nullptr;
+    EXPECT(asr_rnnt_create(&m.d, &w, &h), ASR_OK);
+    const std::string text = random_arpa(4, 2, false);
+    const std::string bare = "\\data\\\nngram 1=1\n\n\\1-grams:\n-1.0\ta\n\n\\end\\\n";   // no <s>, no </s>
+    asr_lm_t *lm = nullptr, *lm0 = nullptr;
+    EXPECT(asr_lm_create_arpa_mem(text.data(), text.size(), -3.0f, &lm), ASR_OK);
+    EXPECT(asr_lm_create_arpa_mem(bare.data(), bare.size(), -3.0f, &lm0), ASR_OK);
+    if (!h || !lm || !lm0) return;
+    const int32_t map[5] = {-1, 0, 1, 2, 3};
+    asr_rnnt_lm_t* z = nullptr;
+    EXPECT(asr_rnnt_lm_create(h, lm, map, 0.5f, 0.5f, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(nullptr, lm, map, 0.5f, 0.5f, 0, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, nullptr, map, 0.5f, 0.5f, 0, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm, nullptr, 0.5f, 0.5f, 0, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm, map, -0.5f, 0.5f, 0, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm, map, INFINITY, 0.5f, 0, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm, map, NAN, 0.5f, 0, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm, map, 0.5f, NAN, 0, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm, map, 0.5f, 0.5f, 4, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm0, map, 0.5f, 0.5f, ASR_LM_BOS, &z), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm0, map, 0.5f, 0.5f, ASR_LM_EOS, &z), ASR_ERR_ARG);
+    EXPECT_TRUE(z == nullptr);
+    EXPECT(asr_rnnt_lm_destroy(nullptr), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_lm_create(h, lm, map, 0.5f, 0.5f, ASR_LM_BOS | ASR_LM_EOS, &z), ASR_OK);
+    if (!z) return;
+    const int T = 2, B = 2, K = 4, nbest = 2, mo = 3;
+    std::vector<float> enc((size_t)T * B * m.d.E, 0.25f);
+    Out o(B, nbest, mo);
+    double work[2] = {0, 0};
+    auto host = [&](asr_rnnt_lm_t* zz, const float* e, int t, int b, int k, int nb, int m_out, int32_t* tok, int32_t* ts,
+                    int32_t* len, double* tot, int32_t* nh) {
+        const int a = asr_rnnt_beam_lm_host(zz, e, nullptr, t, b, k, nb, m_out, tok, ts, len, tot, nullptr, nullptr, nullptr,
+                                            nh, nullptr);
+        const int d = asr_rnnt_beam_lm(zz, e, nullptr, t, b, k, nb, m_out, tok, ts, len, tot, nullptr, nullptr, nullptr, nh,
+                                       work, nullptr);
+        // the device entry refuses the same way before any HIP call; what the host accepts ends at "not uploaded"
+        EXPECT(d, a == ASR_OK ? ASR_ERR_STATE : a);
+        return a;
+    };
+    int32_t *tok = o.tok.data(), *ts = o.ts.data(), *len = o.len.data(), *nh = o.nhyp.data();
+    double* sc = o.total.data();
+    EXPECT(host(z, enc.data(), T, B, K, nbest, mo, tok, ts, len, sc, nh), ASR_OK);
+    EXPECT(host(nullptr, enc.data(), T, B, K, nbest, mo, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, nullptr, T, B, K, nbest, mo, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, nbest, mo, nullptr, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, nbest, mo, tok, nullptr, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, nbest, mo, tok, ts, nullptr, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, nbest, mo, tok, ts, len, nullptr, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, nbest, mo, tok, ts, len, sc, nullptr), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), 0, B, K, nbest, mo, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, 0, K, nbest, mo, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, 0, nbest, mo, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, 17, nbest, mo, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, 0, mo, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, K + 1, mo, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, nbest, -1, tok, ts, len, sc, nh), ASR_ERR_ARG);
+    EXPECT(host(z, enc.data(), T, B, K, nbest, 0, nullptr, nullptr, len, sc, nh), ASR_OK);
+    EXPECT(host(z, enc.data(), 1 << 30, B, K, nbest, mo, tok, ts, len, sc, nh), ASR_ERR_UNSUPPORTED);   // T * B
+    EXPECT(host(z, enc.data(), 1 << 30, 1, 16, nbest, mo, tok, ts, len, sc, nh), ASR_ERR_UNSUPPORTED);  // T * K + 1
+    EXPECT(asr_rnnt_beam_lm(z, enc.data(), nullptr, T, B, K, nbest, mo, tok, ts, len, sc, nullptr, nullptr, nullptr, nh,
+                            nullptr, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_beam_lm_workspace_bytes(nullptr, T, B, K), 0);
+    EXPECT(asr_rnnt_beam_lm_workspace_bytes(z, 0, B, K), 0);
+    EXPECT(asr_rnnt_beam_lm_workspace_bytes(z, T, B, 17), 0);
+    EXPECT(asr_rnnt_beam_lm_workspace_bytes(z, T, B, K), asr_rnnt_beam_workspace_bytes(h, T, B, K) + 16 * 5 * 8);
+    EXPECT(asr_rnnt_lm_destroy(z), ASR_OK);
+    EXPECT(asr_rnnt_destroy(h), ASR_OK);
+    // the search kernel's LDS limit is the device call's to refuse
+    const Model big = make_model(5, 0, 8, 16, 816, 1, 816, ASR_RNNT_ACT_RELU);
+    asr_rnnt_weights bw = big.ptrs();
+    EXPECT(asr_rnnt_create(&big.d, &bw, &h), ASR_OK);
+    if (!h) return;
+    EXPECT(asr_rnnt_lm_create(h, lm, map, 0.5f, 0.5f, 0, &z), ASR_OK);
+    if (!z) return;
+    EXPECT(asr_rnnt_beam_lm(z, enc.data(), nullptr, 1, 1, 1, 1, mo, tok, ts, len, sc, nullptr, nullptr, nullptr, nh, work,
+                            nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_rnnt_lm_destroy(z), ASR_OK);
+    EXPECT(asr_rnnt_destroy(h), ASR_OK);
+    EXPECT(asr_lm_destroy(lm), ASR_OK);
+    EXPECT(asr_lm_destroy(lm0), ASR_OK);
+}
+
+int main() {
+    random_searches();
+    refusals();
+    if (failures) {
+        std::printf("rnnt_lm_check: %d failure(s)\n", failures);
+        return 1;
+    }
+    std::printf("rnnt_lm_check: ok\n");
+    return 0;
+}
