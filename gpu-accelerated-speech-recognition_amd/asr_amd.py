@@ -556,10 +556,15 @@ class RNN:
         return self.hiddens[-1]
 
 
-# ---------------------------------------------------------------------- LSTM
+# ---------------------------------------------------------------- LSTM / GRU
 def lstm_workspace_bytes(T: int, B: int, H: int) -> int:
     """asr_lstm_workspace_bytes: 0 for a shape the LSTM kernels do not take."""
     return int(lib().asr_lstm_workspace_bytes(T, B, H))
+
+
+def gru_workspace_bytes(T: int, B: int, H: int) -> int:
+    """asr_gru_workspace_bytes: 0 for a shape the GRU kernels do not take."""
+    return int(lib().asr_gru_workspace_bytes(T, B, H))
 
 
 def device_lengths(lengths: Sequence[int]) -> DeviceBytes:
@@ -570,15 +575,19 @@ def device_lengths(lengths: Sequence[int]) -> DeviceBytes:
     return d
 
 
-def _lstm_tail(hid: DeviceMatrix, col: int, H: int, hT, cT, lengths, work, need_work: bool, T: int, B: int):
-    """Arguments shared by lstm_fwd / lstm_recur_fwd: the output pointer of the
-    direction that writes columns [col, col + H) of hid's rows, and the rest."""
+def _gated_tail(kind: str, hid: DeviceMatrix, col: int, H: int, T: int, B: int, work, need_work: bool, *optional):
+    """Arguments shared by lstm_fwd / lstm_recur_fwd / gru_fwd / gru_recur_fwd
+    (kind "LSTM" or "GRU"): the output pointer of the direction that writes
+    columns [col, col + H) of hid's rows, its row stride, and the pointers of
+    the optional buffers (None stays None).  need_work: the call needs the
+    whole asr_<kind>_workspace_bytes in work."""
     assert hid.rows == T * B and 0 <= col and col + H <= hid.cols, (hid.rows, hid.cols, col, H)
-    need = lstm_workspace_bytes(T, B, H)
-    if need_work and need and (work is None or work.nbytes < need):
-        raise ValueError(f"LSTM workspace of {need} bytes needed (asr_lstm_workspace_bytes)")
-    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
-    return hid.ptr + 4 * col, hid.cols, opt(hT), opt(cT), opt(lengths), opt(work)
+    if need_work:
+        name = f"asr_{kind.lower()}_workspace_bytes"
+        need = int(getattr(lib(), name)(T, B, H))
+        if need and (work is None or work.nbytes < need):
+            raise ValueError(f"{kind} workspace of {need} bytes needed ({name})")
+    return (hid.ptr + 4 * col, hid.cols) + tuple(m.ptr if m is not None else None for m in optional)
 
 
 def lstm_fwd(x: DeviceMatrix, W_ih: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh: DeviceMatrix,
@@ -591,7 +600,7 @@ def lstm_fwd(x: DeviceMatrix, W_ih: DeviceMatrix, W_hh: DeviceMatrix, b_ih: Devi
     (the row stride is hid.cols); lengths from device_lengths()."""
     inp, H = W_ih.rows, W_hh.rows
     assert x.rows == T * B and x.cols == inp and W_ih.cols == 4 * H and W_hh.cols == 4 * H
-    out, ldh, pht, pct, pln, pwk = _lstm_tail(hid, col, H, hT, cT, lengths, work, True, T, B)
+    out, ldh, pht, pct, pln, pwk = _gated_tail("LSTM", hid, col, H, T, B, work, True, hT, cT, lengths, work)
     check(lib().asr_lstm_fwd(x.ptr, h0.ptr if h0 else None, c0.ptr if c0 else None, W_ih.ptr, W_hh.ptr,
                              b_ih.ptr, b_hh.ptr, out, ldh, pht, pct, pln, pwk, T, B, inp, H,
                              int(bool(reverse)), stream), "asr_lstm_fwd")
@@ -608,105 +617,11 @@ def lstm_recur_fwd(P: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh
     (read only); work is needed for H > 128."""
     H = W_hh.rows
     assert P.rows == T * B and P.cols == 4 * H and W_hh.cols == 4 * H
-    out, ldh, pht, pct, pln, pwk = _lstm_tail(hid, col, H, hT, cT, lengths, work, H > 128, T, B)
+    out, ldh, pht, pct, pln, pwk = _gated_tail("LSTM", hid, col, H, T, B, work, H > 128, hT, cT, lengths, work)
     check(lib().asr_lstm_recur_fwd(P.ptr, h0.ptr if h0 else None, c0.ptr if c0 else None, W_hh.ptr, b_ih.ptr,
                                    b_hh.ptr, out, ldh, pht, pct, pln, pwk, T, B, H, int(bool(reverse)),
                                    stream), "asr_lstm_recur_fwd")
     return hid
-
-
-class _DeviceView:
-    """Rows [r0, r0 + rows) of a DeviceMatrix, without owning them."""
-
-    def __init__(self, m: DeviceMatrix, r0: int, rows: int):
-        self.ptr, self.rows, self.cols, self._keep = m.ptr + 4 * r0 * m.cols, rows, m.cols, m
-
-
-class LSTM:
-    """torch.nn.LSTM(input_size, hidden_size, num_layers, bidirectional=...) for
-    inference on asr_lstm_fwd: device weights and one workspace, no arithmetic
-    here.  params[layer][direction] = (W_ih [in, 4H], W_hh [H, 4H], b_ih [4H],
-    b_hh [4H]) in this library's [in][out] layout (zeros if None); from_torch
-    takes them from a torch module.  No proj_size, no dropout."""
-
-    def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, bidirectional: bool = False,
-                 params: Optional[Sequence[Sequence[Tuple[np.ndarray, ...]]]] = None):
-        self.inp, self.H, self.L, self.D = input_size, hidden_size, num_layers, 2 if bidirectional else 1
-        H = hidden_size
-        self.layers = []
-        for l in range(num_layers):
-            i = input_size if l == 0 else self.D * H
-            shapes = ((i, 4 * H), (H, 4 * H), (4 * H, 1), (4 * H, 1))
-            dirs = []
-            for d in range(self.D):
-                p = [np.zeros(s, np.float32) for s in shapes] if params is None else params[l][d]
-                dirs.append(tuple(DeviceMatrix.from_numpy(np.asarray(a, np.float32).reshape(s))
-                                  for a, s in zip(p, shapes)))
-            self.layers.append(dirs)
-        self._work: Optional[DeviceBytes] = None
-        self._shape = None
-        self.outputs: List[DeviceMatrix] = []
-        self.h_n: Optional[DeviceMatrix] = None   # [L*D*B, H] as torch's h_n [L*D, B, H]
-        self.c_n: Optional[DeviceMatrix] = None
-
-    @classmethod
-    def from_torch(cls, module) -> "LSTM":
-        """The weight_*_l{k}[_reverse] tensors of a torch.nn.LSTM, transposed to
-        [in][out], and its biases."""
-        if getattr(module, "proj_size", 0) or not module.bias:
-            raise ValueError("LSTM.from_torch: proj_size and bias=False are not supported")
-        params = []
-        for l in range(module.num_layers):
-            dirs = []
-            for sfx in ("", "_reverse")[:2 if module.bidirectional else 1]:
-                get = lambda n: getattr(module, f"{n}_l{l}{sfx}").detach().cpu().float().numpy()   # noqa: E731
-                dirs.append((np.ascontiguousarray(get("weight_ih").T), np.ascontiguousarray(get("weight_hh").T),
-                             get("bias_ih"), get("bias_hh")))
-            params.append(dirs)
-        return cls(module.input_size, module.hidden_size, module.num_layers, module.bidirectional, params)
-
-    def forward(self, x: DeviceMatrix, T: int, B: int, lengths: Optional[Sequence[int]] = None,
-                stream: Optional[int] = None) -> DeviceMatrix:
-        """x time-major [T*B, input_size]; lengths: a sequence of B counts or a
-        device int32 [B] (DeviceBytes, e.g. Conv1d.forward's out_lengths);
-        returns the last layer's [T*B, H or 2H] (zeros past each utterance's
-        length); h_n / c_n hold the final states.  The two directions of a layer
-        write the two halves of one buffer."""
-        H, D, st = self.H, self.D, stream or 0
-        if self._shape != (T, B):
-            need = lstm_workspace_bytes(T, B, H)
-            if not need:
-                raise AsrError(ASR_ERR_UNSUPPORTED, "asr_lstm_workspace_bytes")
-            if self._work is None or self._work.nbytes < need:
-                self._work = DeviceBytes(need)
-            self.outputs = [DeviceMatrix(T * B, D * H) for _ in range(self.L)]
-            self.h_n, self.c_n = DeviceMatrix(self.L * D * B, H), DeviceMatrix(self.L * D * B, H)
-            self._shape = (T, B)
-        ln = lengths if lengths is None or isinstance(lengths, DeviceBytes) else device_lengths(lengths)
-        for l, dirs in enumerate(self.layers):
-            for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(dirs):
-                k = (l * D + d) * B
-                lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, self.outputs[l], T, B, self._work,
-                         hT=_DeviceView(self.h_n, k, B), cT=_DeviceView(self.c_n, k, B), lengths=ln,
-                         reverse=d == 1, col=d * H, stream=st)
-            x = self.outputs[l]
-        if ln is not None:   # the kernels read it: keep it until they are done
-            check(lib().asr_stream_sync(ctypes.c_void_p(st or None)), "asr_stream_sync")
-        return self.outputs[-1]
-
-
-# ----------------------------------------------------------------------- GRU
-def gru_workspace_bytes(T: int, B: int, H: int) -> int:
-    """asr_gru_workspace_bytes: 0 for a shape the GRU kernels do not take."""
-    return int(lib().asr_gru_workspace_bytes(T, B, H))
-
-
-def _gru_tail(hid: DeviceMatrix, col: int, H: int, hT, lengths, T: int, B: int):
-    """Arguments shared by gru_fwd / gru_recur_fwd: the output pointer of the
-    direction that writes columns [col, col + H) of hid's rows, and the rest."""
-    assert hid.rows == T * B and 0 <= col and col + H <= hid.cols, (hid.rows, hid.cols, col, H)
-    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
-    return hid.ptr + 4 * col, hid.cols, opt(hT), opt(lengths)
 
 
 def gru_fwd(x: DeviceMatrix, W_ih: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh: DeviceMatrix,
@@ -718,13 +633,9 @@ def gru_fwd(x: DeviceMatrix, W_ih: DeviceMatrix, W_hh: DeviceMatrix, b_ih: Devic
     row stride is hid.cols); lengths from device_lengths()."""
     inp, H = W_ih.rows, W_hh.rows
     assert x.rows == T * B and x.cols == inp and W_ih.cols == 3 * H and W_hh.cols == 3 * H
-    need = gru_workspace_bytes(T, B, H)
-    if need and (work is None or work.nbytes < need):
-        raise ValueError(f"GRU workspace of {need} bytes needed (asr_gru_workspace_bytes)")
-    out, ldh, pht, pln = _gru_tail(hid, col, H, hT, lengths, T, B)
+    out, ldh, pht, pln, pwk = _gated_tail("GRU", hid, col, H, T, B, work, True, hT, lengths, work)
     check(lib().asr_gru_fwd(x.ptr, h0.ptr if h0 else None, W_ih.ptr, W_hh.ptr, b_ih.ptr, b_hh.ptr, out, ldh, pht,
-                            pln, work.ptr if work is not None else None, T, B, inp, H, int(bool(reverse)), stream),
-          "asr_gru_fwd")
+                            pln, pwk, T, B, inp, H, int(bool(reverse)), stream), "asr_gru_fwd")
     return hid
 
 
@@ -736,27 +647,36 @@ def gru_recur_fwd(P: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh:
     (read only); no workspace."""
     H = W_hh.rows
     assert P.rows == T * B and P.cols == 3 * H and W_hh.cols == 3 * H
-    out, ldh, pht, pln = _gru_tail(hid, col, H, hT, lengths, T, B)
+    out, ldh, pht, pln = _gated_tail("GRU", hid, col, H, T, B, None, False, hT, lengths)
     check(lib().asr_gru_recur_fwd(P.ptr, h0.ptr if h0 else None, W_hh.ptr, b_ih.ptr, b_hh.ptr, out, ldh, pht, pln,
                                   T, B, H, int(bool(reverse)), stream), "asr_gru_recur_fwd")
     return hid
 
 
-class GRU:
-    """torch.nn.GRU(input_size, hidden_size, num_layers, bidirectional=...) for
-    inference on asr_gru_fwd: device weights and one workspace, no arithmetic
-    here.  params[layer][direction] = (W_ih [in, 3H], W_hh [H, 3H], b_ih [3H],
-    b_hh [3H]) in this library's [in][out] layout (zeros if None); from_torch
-    takes them from a torch module.  No dropout."""
+class _DeviceView:
+    """Rows [r0, r0 + rows) of a DeviceMatrix, without owning them."""
+
+    def __init__(self, m: DeviceMatrix, r0: int, rows: int):
+        self.ptr, self.rows, self.cols, self._keep = m.ptr + 4 * r0 * m.cols, rows, m.cols, m
+
+
+class _GatedRNN:
+    """What LSTM and GRU share: the device weights of every layer and direction,
+    one workspace, from_torch and the layer / direction loop of forward.  A
+    subclass names its gate count (_NG), its state matrices (_STATES, h_n
+    first), its workspace function, what from_torch refuses and the call of one
+    layer and direction."""
+    _NG = 0
+    _STATES: Tuple[str, ...] = ()
 
     def __init__(self, input_size: int, hidden_size: int, num_layers: int = 1, bidirectional: bool = False,
                  params: Optional[Sequence[Sequence[Tuple[np.ndarray, ...]]]] = None):
         self.inp, self.H, self.L, self.D = input_size, hidden_size, num_layers, 2 if bidirectional else 1
-        H = hidden_size
+        H, G = hidden_size, self._NG * hidden_size
         self.layers = []
         for l in range(num_layers):
             i = input_size if l == 0 else self.D * H
-            shapes = ((i, 3 * H), (H, 3 * H), (3 * H, 1), (3 * H, 1))
+            shapes = ((i, G), (H, G), (G, 1), (G, 1))
             dirs = []
             for d in range(self.D):
                 p = [np.zeros(s, np.float32) for s in shapes] if params is None else params[l][d]
@@ -766,14 +686,14 @@ class GRU:
         self._work: Optional[DeviceBytes] = None
         self._shape = None
         self.outputs: List[DeviceMatrix] = []
-        self.h_n: Optional[DeviceMatrix] = None   # [L*D*B, H] as torch's h_n [L*D, B, H]
+        for name in self._STATES:   # each [L*D*B, H] as torch's h_n [L*D, B, H]
+            setattr(self, name, None)
 
     @classmethod
-    def from_torch(cls, module) -> "GRU":
-        """The weight_*_l{k}[_reverse] tensors of a torch.nn.GRU, transposed to
-        [in][out], and its biases."""
-        if not module.bias:
-            raise ValueError("GRU.from_torch: bias=False is not supported")
+    def from_torch(cls, module):
+        """The weight_*_l{k}[_reverse] tensors of the torch.nn module of the same
+        name, transposed to [in][out], and its biases."""
+        cls._refuse(module)
         params = []
         for l in range(module.num_layers):
             dirs = []
@@ -784,6 +704,78 @@ class GRU:
             params.append(dirs)
         return cls(module.input_size, module.hidden_size, module.num_layers, module.bidirectional, params)
 
+    def _forward(self, x: DeviceMatrix, T: int, B: int, lengths, h0: Optional[DeviceMatrix], st: int) -> DeviceMatrix:
+        """The layers in turn, the two directions of a layer into the two halves
+        of one buffer; state k of _layer is rows [k, k + B) of h_n (c_n, h0)."""
+        H, D = self.H, self.D
+        if self._shape != (T, B):
+            need = self._workspace_bytes(T, B, H)
+            if not need:
+                raise AsrError(ASR_ERR_UNSUPPORTED, f"asr_{type(self).__name__.lower()}_workspace_bytes")
+            if self._work is None or self._work.nbytes < need:
+                self._work = DeviceBytes(need)
+            self.outputs = [DeviceMatrix(T * B, D * H) for _ in range(self.L)]
+            for name in self._STATES:
+                setattr(self, name, DeviceMatrix(self.L * D * B, H))
+            self._shape = (T, B)
+        assert h0 is None or (h0.rows == self.L * D * B and h0.cols == H), (h0.rows, h0.cols)
+        ln = lengths if lengths is None or isinstance(lengths, DeviceBytes) else device_lengths(lengths)
+        for l, dirs in enumerate(self.layers):
+            for d, weights in enumerate(dirs):
+                self._layer(x, weights, self.outputs[l], T, B, (l * D + d) * B, h0, lengths=ln, reverse=d == 1,
+                            col=d * H, stream=st)
+            x = self.outputs[l]
+        if ln is not None:   # the kernels read it: keep it until they are done
+            check(lib().asr_stream_sync(ctypes.c_void_p(st or None)), "asr_stream_sync")
+        return self.outputs[-1]
+
+
+class LSTM(_GatedRNN):
+    """torch.nn.LSTM(input_size, hidden_size, num_layers, bidirectional=...) for
+    inference on asr_lstm_fwd: device weights and one workspace, no arithmetic
+    here.  params[layer][direction] = (W_ih [in, 4H], W_hh [H, 4H], b_ih [4H],
+    b_hh [4H]) in this library's [in][out] layout (zeros if None); from_torch
+    takes them from a torch module.  No proj_size, no dropout."""
+    _NG, _STATES = 4, ("h_n", "c_n")
+    _workspace_bytes = staticmethod(lstm_workspace_bytes)
+
+    @staticmethod
+    def _refuse(module) -> None:
+        if getattr(module, "proj_size", 0) or not module.bias:
+            raise ValueError("LSTM.from_torch: proj_size and bias=False are not supported")
+
+    def _layer(self, x, weights, out, T, B, k, h0, **kw) -> None:
+        lstm_fwd(x, *weights, out, T, B, self._work, hT=_DeviceView(self.h_n, k, B), cT=_DeviceView(self.c_n, k, B),
+                 **kw)
+
+    def forward(self, x: DeviceMatrix, T: int, B: int, lengths: Optional[Sequence[int]] = None,
+                stream: Optional[int] = None) -> DeviceMatrix:
+        """x time-major [T*B, input_size]; lengths: a sequence of B counts or a
+        device int32 [B] (DeviceBytes, e.g. Conv1d.forward's out_lengths);
+        returns the last layer's [T*B, H or 2H] (zeros past each utterance's
+        length); h_n / c_n hold the final states.  The two directions of a layer
+        write the two halves of one buffer."""
+        return self._forward(x, T, B, lengths, None, stream or 0)
+
+
+class GRU(_GatedRNN):
+    """torch.nn.GRU(input_size, hidden_size, num_layers, bidirectional=...) for
+    inference on asr_gru_fwd: device weights and one workspace, no arithmetic
+    here.  params[layer][direction] = (W_ih [in, 3H], W_hh [H, 3H], b_ih [3H],
+    b_hh [3H]) in this library's [in][out] layout (zeros if None); from_torch
+    takes them from a torch module.  No dropout."""
+    _NG, _STATES = 3, ("h_n",)
+    _workspace_bytes = staticmethod(gru_workspace_bytes)
+
+    @staticmethod
+    def _refuse(module) -> None:
+        if not module.bias:
+            raise ValueError("GRU.from_torch: bias=False is not supported")
+
+    def _layer(self, x, weights, out, T, B, k, h0, **kw) -> None:
+        gru_fwd(x, *weights, out, T, B, self._work, h0=None if h0 is None else _DeviceView(h0, k, B),
+                hT=_DeviceView(self.h_n, k, B), **kw)
+
     def forward(self, x: DeviceMatrix, T: int, B: int, lengths: Optional[Sequence[int]] = None,
                 h0: Optional[DeviceMatrix] = None, stream: Optional[int] = None) -> DeviceMatrix:
         """x time-major [T*B, input_size]; h0 [L*D*B, H] in h_n's order (None =
@@ -792,28 +784,7 @@ class GRU:
         layer's [T*B, H or 2H] (zeros past each utterance's length); h_n holds
         the final states.  The two directions of a layer write the two halves
         of one buffer."""
-        H, D, st = self.H, self.D, stream or 0
-        if self._shape != (T, B):
-            need = gru_workspace_bytes(T, B, H)
-            if not need:
-                raise AsrError(ASR_ERR_UNSUPPORTED, "asr_gru_workspace_bytes")
-            if self._work is None or self._work.nbytes < need:
-                self._work = DeviceBytes(need)
-            self.outputs = [DeviceMatrix(T * B, D * H) for _ in range(self.L)]
-            self.h_n = DeviceMatrix(self.L * D * B, H)
-            self._shape = (T, B)
-        assert h0 is None or (h0.rows == self.L * D * B and h0.cols == H), (h0.rows, h0.cols)
-        ln = lengths if lengths is None or isinstance(lengths, DeviceBytes) else device_lengths(lengths)
-        for l, dirs in enumerate(self.layers):
-            for d, (w_ih, w_hh, b_ih, b_hh) in enumerate(dirs):
-                k = (l * D + d) * B
-                gru_fwd(x, w_ih, w_hh, b_ih, b_hh, self.outputs[l], T, B, self._work,
-                        h0=None if h0 is None else _DeviceView(h0, k, B), hT=_DeviceView(self.h_n, k, B),
-                        lengths=ln, reverse=d == 1, col=d * H, stream=st)
-            x = self.outputs[l]
-        if ln is not None:   # the kernels read it: keep it until they are done
-            check(lib().asr_stream_sync(ctypes.c_void_p(st or None)), "asr_stream_sync")
-        return self.outputs[-1]
+        return self._forward(x, T, B, lengths, h0, stream or 0)
 
 
 # -------------------------------------------------------------------- Conv1d

@@ -22,7 +22,7 @@
 // Row metadata (t', b, len_b) is computed once per row, by the thread that
 // fetches the row, before the stage loop.
 //
-// Operand layouts are those of lstm.hip / gru.hip: A[l & 15][k = l >> 4],
+// Operand layouts are those of gated_rnn.hip: A[l & 15][k = l >> 4],
 // B[k = l >> 4][l & 15], C rows 4g + i, column l & 15.  MFMA number m of a
 // 16-channel group contracts channels 4m .. 4m+3 (lane group g supplies
 // channel 4m + g), so every output element is accumulated from a zero

@@ -19,7 +19,7 @@
 // LSTM gathers P_t.  The walk is ONE launch: a workgroup of 8 waves owns 16
 // utterances, the rows of a v_mfma_f32_16x16x4_f32 tile; its waves split the
 // 16-column tiles (tile j belongs to wave j % 8), streaming the weights from L2
-// with lstm_step_kernel's register ring.  h (two buffers per layer) and z live
+// with gated_step_kernel's register ring.  h (two buffers per layer) and z live
 // in LDS; c and g are owned by the lane that computes them and sit in the
 // workgroup's slice of the workspace.  Each iteration: rows that emitted take a
 // predictor step (skipped by a workgroup-uniform branch when none did), every

@@ -43,7 +43,7 @@ __device__ __forceinline__ float rt_sigmoid(float z) { return 1.f / (1.f + expf(
 
 // acc[q] += A(16 x 16*nch) . W[:, col[q]] for the lane's column of NQ tiles.
 // a: this lane's row of A in LDS at k = 4g (row c of the tile); W: the matrix.
-// MFMA (i, e) of lane group g contracts k = 16i + 4g + e, as in lstm.hip; the
+// MFMA (i, e) of lane group g contracts k = 16i + 4g + e, as in gated_rnn.hip; the
 // fragments of chunk i + RT_DEPTH load while chunk i's MFMAs issue (loads past
 // the last chunk re-read it and are not used).
 template <int NQ>

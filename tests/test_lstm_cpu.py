@@ -38,6 +38,11 @@ def test_workspace_bytes_invalid_shape():
     assert L.asr_lstm_workspace_bytes(0, 4, 16) == 0
 
 
+def test_workspace_bytes_refuses_more_than_int_max_frames():
+    # T*B > INT_MAX, which asr_lstm_fwd refuses: 0, not a wrapped size
+    assert asr.lib().asr_lstm_workspace_bytes(2**31 - 1, 2**31 - 1, 2048) == 0
+
+
 def fwd(ptr, T, B, inp, H, ldh=None):
     p = ptr
     return asr.lib().asr_lstm_fwd(p, p, p, p, p, p, p, p, H if ldh is None else ldh, p, p, p, p,

@@ -154,6 +154,56 @@ def test_lstm_lengths(T, B, I, H, d):
     close(cT, cn[d], "c_T")
 
 
+@pytest.mark.parametrize("d", [0, 1], ids=["forward", "reverse"])
+@pytest.mark.parametrize("T,B,I,H", [(7, 5, 16, 16), (5, 3, 8, 144)])
+def test_lstm_length_zero(T, B, I, H, d):
+    """An utterance of length 0: all-zero rows, h_T == h0 and c_T == c0 bit for
+    bit; the other utterances are what they are without it (a negative length
+    clamps to 0)."""
+    p = params(T, B, I, H)
+    ln = [T] * B
+    ln[0], ln[B - 1] = 0, -3
+    got, hT, cT = run(T, B, I, H, d, True, lengths=tuple(ln))
+    full, hfull, cfull = run(T, B, I, H, d, True)
+    got, full = got.reshape(T, B, H), full.reshape(T, B, H)
+    for b in (0, B - 1):
+        assert not got[:, b].any()
+        assert np.array_equal(hT[b], p["h0"][d][b])
+        assert np.array_equal(cT[b], p["c0"][d][b])
+    assert np.array_equal(got[:, 1:B - 1], full[:, 1:B - 1])
+    assert np.array_equal(hT[1:B - 1], hfull[1:B - 1])
+    assert np.array_equal(cT[1:B - 1], cfull[1:B - 1])
+
+
+@pytest.mark.parametrize("H", [48, 144])
+def test_lstm_streaming_carry(H):
+    """Forward, T = 12 in one call == frames [0, 5) then [5, 12) with the first
+    call's d_hT / d_cT as the second's d_h0 / d_c0, bit for bit (how a streaming
+    caller runs an LSTM; also the carried registers / rows against the stored
+    ones)."""
+    T, T1, B, I = 12, 5, 5, 24
+    p = params(T, B, I, H)
+    W = [dm(p[0][0]), dm(p[0][1]), dm(p[0][2].reshape(-1, 1)), dm(p[0][3].reshape(-1, 1))]
+    h0, c0 = dm(p["h0"][0]), dm(p["c0"][0])
+    whole, hT, cT = asr.DeviceMatrix(T * B, H), asr.DeviceMatrix(B, H), asr.DeviceMatrix(B, H)
+    asr.lstm_fwd(dm(p["x"]), *W, whole, T, B, asr.DeviceBytes(asr.lstm_workspace_bytes(T, B, H)), h0=h0, c0=c0,
+                 hT=hT, cT=cT)
+    asr.synchronize()
+    parts, hc, cc = [], h0, c0
+    for lo, hi in ((0, T1), (T1, T)):
+        n = hi - lo
+        hid, hn, cn = asr.DeviceMatrix(n * B, H), asr.DeviceMatrix(B, H), asr.DeviceMatrix(B, H)
+        asr.lstm_fwd(dm(p["x"][lo * B:hi * B]), *W, hid, n, B, asr.DeviceBytes(asr.lstm_workspace_bytes(n, B, H)),
+                     h0=hc, c0=cc, hT=hn, cT=cn)
+        asr.synchronize()
+        parts.append(hid.toCpu())
+        hc, cc = hn, cn
+    assert np.array_equal(np.concatenate(parts), whole.toCpu())
+    assert np.array_equal(hc.toCpu(), hT.toCpu())
+    assert np.array_equal(cc.toCpu(), cT.toCpu())
+    assert np.array_equal(hT.toCpu(), whole.toCpu()[(T - 1) * B:])
+
+
 @pytest.mark.parametrize("T,B,I,H", [(9, 16, 24, 48), (6, 20, 24, 256)])
 def test_lstm_ldh_two_halves(T, B, I, H):
     """ldh = 2H: a forward and a reverse call fill the two halves of one buffer

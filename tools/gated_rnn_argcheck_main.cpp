@@ -1,0 +1,162 @@
+// Host-side argument and shape checks of asr_lstm_workspace_bytes / asr_lstm_fwd /
+// asr_lstm_recur_fwd and asr_gru_workspace_bytes / asr_gru_fwd /
+// asr_gru_recur_fwd, as a stand-alone program for a sanitizer build on the CPU
+// (`make -C gpu-accelerated-speech-recognition_amd argcheck` compiles
+// csrc/gated_rnn.hip and this file with -fsanitize=address,undefined and runs the
+// result).  Every call here is refused before any HIP call: invalid sizes, NULL
+// pointers and fake device pointers that are never dereferenced.  No GPU is
+// needed or used.
+#include "asr_amd.h"
+
+#include <cstdint>
+#include <cstdio>
+
+static int failures = 0;
+#define EXPECT(expr, want)                                                              \
+    do {                                                                                \
+        const long got_ = (long)(expr);                                                 \
+        if (got_ != (long)(want)) {                                                     \
+            std::printf("FAIL %s: got %ld, want %ld\n", #expr, got_, (long)(want));     \
+            failures++;                                                                 \
+        }                                                                               \
+    } while (0)
+
+static float* const F = reinterpret_cast<float*>(0x10000);        // 16-byte aligned, never dereferenced
+static int32_t* const L = reinterpret_cast<int32_t*>(0x10000);
+static void* const W = reinterpret_cast<void*>(0x10000);
+static float* const nul = nullptr;
+static const int shapes[][3] = {{1, 1, 16}, {7, 5, 16}, {12, 50, 128}, {5, 3, 144}, {3, 16, 1024}, {200, 1024, 2048}};
+
+static void gru() {
+    for (const auto& s : shapes) {
+        const size_t n = asr_gru_workspace_bytes(s[0], s[1], s[2]);
+        EXPECT(n >= (size_t)s[0] * s[1] * 3 * s[2] * 4, 1);
+        EXPECT(n % 16, 0);
+    }
+    EXPECT(asr_gru_workspace_bytes(4, 4, 0), 0);
+    EXPECT(asr_gru_workspace_bytes(4, 4, 20), 0);
+    EXPECT(asr_gru_workspace_bytes(4, 4, 2064), 0);
+    EXPECT(asr_gru_workspace_bytes(0, 4, 16), 0);
+    EXPECT(asr_gru_workspace_bytes(4, -1, 16), 0);
+    EXPECT(asr_gru_workspace_bytes(INT32_MAX, INT32_MAX, 2048), 0);   // T*B > INT_MAX: refused, no overflow
+
+    // ASR_ERR_ARG
+    EXPECT(asr_gru_fwd(nul, F, F, F, F, F, F, 16, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, nul, F, F, F, F, 16, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, nul, F, F, F, 16, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, nul, F, F, 16, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, nul, F, 16, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, nul, 16, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 16, F, L, nullptr, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 16, F, L, W, 0, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 16, F, L, W, 4, 0, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 16, F, L, W, 4, 4, 0, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 16, F, L, W, 4, 4, 8, 0, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 16, F, L, W, -4, -4, -8, -16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 15, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(nul, F, F, F, F, F, 16, F, L, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, nul, F, F, F, 16, F, L, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, F, nul, F, F, 16, F, L, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, nul, F, 16, F, L, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, nul, 16, F, L, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 16, F, L, 0, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 16, F, L, 4, 0, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 255, F, L, 4, 4, 256, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, -1, F, L, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+
+    // ASR_ERR_UNSUPPORTED
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 20, F, L, W, 4, 4, 8, 20, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 2064, F, L, W, 4, 4, 8, 2064, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 20, F, L, 4, 4, 20, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 2064, F, L, 4, 4, 2064, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    // one frame of P beyond one buffer resource: B*3H*4 > 0x7ff00000
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 2048, F, L, 1, 1 << 18, 2048, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 2048, F, L, 1, INT32_MAX, 2048, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 128, F, L, 1, 0x7ff00000 / (3 * 128 * 4) + 1, 128, 0, nullptr),
+           ASR_ERR_UNSUPPORTED);
+    // T*B > INT_MAX
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 16, F, L, INT32_MAX, 4096, 16, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 16, F, L, W, INT32_MAX, 4096, 8, 16, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    // the step form's 16-byte loads
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 258, F, L, 4, 4, 256, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F + 1, 256, F, L, 4, 4, 256, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_recur_fwd(F, F + 2, F, F, F, F, 256, F, L, 4, 4, 256, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 258, F, L, W, 4, 4, 8, 256, 0, nullptr), ASR_ERR_UNSUPPORTED);
+}
+
+// asr_lstm_fwd(x, h0, c0, W_ih, W_hh, b_ih, b_hh, hid, ldh, hT, cT, lengths, work, T, B, in, H, reverse, s)
+// asr_lstm_recur_fwd(P, h0, c0, W_hh, b_ih, b_hh, hid, ldh, hT, cT, lengths, work, T, B, H, reverse, s)
+static void lstm() {
+    for (const auto& s : shapes) {
+        const size_t n = asr_lstm_workspace_bytes(s[0], s[1], s[2]);
+        EXPECT(n >= ((size_t)s[0] * s[1] * 4 * s[2] + (size_t)s[1] * s[2]) * 4, 1);   // P, then c
+        EXPECT(n % 16, 0);
+    }
+    EXPECT(asr_lstm_workspace_bytes(4, 4, 0), 0);
+    EXPECT(asr_lstm_workspace_bytes(4, 4, 20), 0);
+    EXPECT(asr_lstm_workspace_bytes(4, 4, 2064), 0);
+    EXPECT(asr_lstm_workspace_bytes(0, 4, 16), 0);
+    EXPECT(asr_lstm_workspace_bytes(4, -1, 16), 0);
+    EXPECT(asr_lstm_workspace_bytes(INT32_MAX, INT32_MAX, 2048), 0);   // T*B > INT_MAX: refused, no overflow
+
+    // ASR_ERR_ARG
+    EXPECT(asr_lstm_fwd(nul, F, F, F, F, F, F, F, 16, F, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, nul, F, F, F, F, 16, F, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, nul, F, F, F, 16, F, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, nul, F, F, 16, F, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, nul, F, 16, F, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, nul, 16, F, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 16, F, F, L, nullptr, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 16, F, F, L, W, 0, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 16, F, F, L, W, 4, 0, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 16, F, F, L, W, 4, 4, 0, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 16, F, F, L, W, 4, 4, 8, 0, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 16, F, F, L, W, -4, -4, -8, -16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 15, F, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(nul, F, F, F, F, F, F, 16, F, F, L, W, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, nul, F, F, F, 16, F, F, L, W, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, nul, F, F, 16, F, F, L, W, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, nul, F, 16, F, F, L, W, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, nul, 16, F, F, L, W, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 16, F, F, L, W, 0, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 16, F, F, L, W, 4, 0, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 255, F, F, L, W, 4, 4, 256, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, -1, F, F, L, W, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    // the step form keeps c in the workspace; the resident form needs none
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 144, F, F, L, nullptr, 4, 4, 144, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 2048, F, F, L, nullptr, 4, 4, 2048, 0, nullptr), ASR_ERR_ARG);
+
+    // ASR_ERR_UNSUPPORTED
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 20, F, F, L, W, 4, 4, 8, 20, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 2064, F, F, L, W, 4, 4, 8, 2064, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 20, F, F, L, W, 4, 4, 20, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 2064, F, F, L, W, 4, 4, 2064, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    // one frame of P beyond one buffer resource: B*4H*4 > 0x7ff00000
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 2048, F, F, L, W, 1, 1 << 17, 2048, 0, nullptr),
+           ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 2048, F, F, L, W, 1, INT32_MAX, 2048, 0, nullptr),
+           ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 128, F, F, L, W, 1, 0x7ff00000 / (4 * 128 * 4) + 1, 128, 0, nullptr),
+           ASR_ERR_UNSUPPORTED);
+    // T*B > INT_MAX
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 16, F, F, L, W, INT32_MAX, 4096, 16, 0, nullptr),
+           ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 16, F, F, L, W, INT32_MAX, 4096, 8, 16, 0, nullptr),
+           ASR_ERR_UNSUPPORTED);
+    // the step form's 16-byte loads
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 258, F, F, L, W, 4, 4, 256, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F + 1, 256, F, F, L, W, 4, 4, 256, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_recur_fwd(F, F + 2, F, F, F, F, F, 256, F, F, L, W, 4, 4, 256, 0, nullptr), ASR_ERR_UNSUPPORTED);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 258, F, F, L, W, 4, 4, 8, 256, 0, nullptr), ASR_ERR_UNSUPPORTED);
+}
+
+int main() {
+    gru();
+    lstm();
+    if (failures) {
+        std::printf("gated rnn argcheck: %d failure(s)\n", failures);
+        return 1;
+    }
+    std::printf("gated rnn argcheck: ok\n");
+    return 0;
+}
