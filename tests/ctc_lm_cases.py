@@ -30,14 +30,30 @@ def assert_same_beams(got, ref, what=""):
                 assert close(hg[i], hr[i]), (what, b, k, i, hg[i], hr[i])
 
 
+def largest_difference(got, ref):
+    """Largest |score - reference score| over total, ctc_logp and lm_log10 of
+    beams that assert_same_beams would compare (a figure to report, no check)."""
+    return max((abs(hg[i] - hr[i]) for g, r in zip(got, ref) for hg, hr in zip(g, r) for i in (1, 2, 3)
+                if hg[i] != hr[i]), default=0.0)
+
+
+def zero_out(logp, seed, fraction, blank):
+    """logp [T][B][V] with `fraction` of the non-blank entries at -inf, chosen by
+    a second generator: the first one's draws (model, emissions) stay as they are."""
+    hit = np.random.default_rng([seed, 1]).random(logp.shape) < fraction
+    hit[:, :, blank] = False
+    return np.where(hit, -np.inf, logp)
+
+
 class Case:
     """One randomised configuration: a random ARPA model over the tokens w0..,
     labels of which the last n_oov are no token of the model, emissions drawn
-    from `seed`."""
+    from `seed`; `zero` is the fraction of the non-blank emissions set to
+    probability 0 (-inf when is_log), drawn from a generator of its own."""
 
     def __init__(self, seed, T, B, V, beam, order=3, bos=True, eos=False, unk=False, n_oov=0, alpha=0.7, beta=0.3,
                  top_n=0, quant=0.0, blank=0, is_log=True, batch_major=False, lengths=None, codes=None,
-                 max_states=0, sigma=2.0):
+                 max_states=0, sigma=2.0, zero=0.0):
         self.seed, self.T, self.B, self.V, self.beam, self.order = seed, T, B, V, beam, order
         self.bos, self.eos, self.alpha, self.beta, self.top_n = bos, eos, alpha, beta, top_n
         self.blank, self.is_log, self.batch_major, self.lengths = blank, is_log, batch_major, lengths
@@ -52,6 +68,8 @@ class Case:
         logp = logits - np.log(np.exp(logits).sum(-1, keepdims=True))
         if quant:
             logp = np.round(logp / quant) * quant   # few distinct values: the label-id tie rule decides
+        if zero:
+            logp = zero_out(logp, seed, zero, blank)
         self.emis = (logp if is_log else np.exp(logp)).astype(np.float32)   # [T][B][V]
 
     def lm(self):
@@ -113,6 +131,90 @@ HOST_CASES = {
     "blank_last_codes": dict(seed=118, T=8, B=2, V=6, beam=3, order=3, blank=5, codes=[9, 3, 7, 1, 8, 4]),
     "beam_wider_than_states": dict(seed=119, T=3, B=1, V=4, beam=200, order=3),
 }
+
+
+# ---- every option at the widths where the kernel's paths change -----------------
+def distinct_codes(n, seed):
+    """n distinct symbol codes in a fixed random order, not 0 .. n-1."""
+    return [int(x) for x in 3 * np.random.default_rng([seed, 2]).permutation(n) + 1]
+
+
+def ragged_lengths(B, T, seed):
+    """B lengths drawn in [1, T], the first T and the last 1."""
+    n = np.random.default_rng([seed, 3]).integers(1, T + 1, B)
+    n[0], n[-1] = T, 1
+    return [int(x) for x in n]
+
+
+# The smallest shapes that still span more than one wave of (state, label) pairs
+# or sit on a limit, each with the options that decide how the kernel indexes by
+# utterance, frame and lane.  Seeds chosen on the CPU with the reference alone,
+# as above.
+WIDE_OPTION_CASES = {
+    # strides, lengths, codes, blank last, probabilities across the wave width
+    "v65_strides_codes_blank_last": dict(seed=900, T=16, B=3, V=65, beam=8, blank=64, codes=distinct_codes(65, 900),
+                                         lengths=[16, 1, 7], batch_major=True, is_log=False),
+    # </s> on, <s> off, beta < 0, OOV labels without <unk>, wide beam
+    "beam50_eos_no_bos_oov": dict(seed=904, T=40, B=3, V=29, beam=50, order=5, sigma=6.0, eos=True, bos=False,
+                                  beta=-1.5, n_oov=3),
+    "beam50_oov_unk_eos": dict(seed=904, T=40, B=3, V=29, beam=50, order=5, sigma=6.0, n_oov=3, unk=True, eos=True),
+    # prefixes longer than the 7-token context: the window shifts
+    "order8_long_prefixes": dict(seed=901, T=48, B=2, V=29, beam=20, order=8, sigma=8.0),
+    # the label cutoff with strides, lengths, probabilities and quantised ties
+    "v1000_top40_strides_quant": dict(seed=900, T=24, B=3, V=1000, beam=20, top_n=40, batch_major=True,
+                                      lengths=[24, 5, 13], is_log=False, quant=0.5),
+    "v256_255_candidates": dict(seed=900, T=6, B=2, V=256, beam=4),
+    "v4096_top255": dict(seed=900, T=6, B=2, V=4096, beam=4, top_n=255, sigma=3.0),
+    # zero probabilities: log(0) and the -inf keys of the select
+    "zero_probabilities": dict(seed=900, T=24, B=4, V=29, beam=8, is_log=False, zero=0.3),
+    "minus_inf_log_probabilities": dict(seed=900, T=24, B=4, V=29, beam=8, is_log=True, zero=0.3),
+    # ragged lengths over more utterances than CUs, the blank in the middle
+    "b300_ragged_blank_mid": dict(seed=900, T=8, B=300, V=6, beam=3, blank=3, lengths=ragged_lengths(300, 8, 900)),
+    # the beam across the wave width with codes, the blank in the middle, </s>
+    "beam64_codes_blank_mid_eos": dict(seed=900, T=16, B=2, V=12, beam=64, blank=5, codes=distinct_codes(12, 900),
+                                       eos=True),
+}
+
+_WIDE = {}
+
+
+def wide_reference(name):
+    """(case, reference beams, gap) of a WIDE_OPTION_CASES entry, computed once per
+    session and never modified, with what the entry needs of its reference
+    checked: a gap >= MIN_GAP; order 8: a best hypothesis of more than 8 tokens;
+    zeroed emissions: at least `beam` hypotheses of finite total per utterance."""
+    if name not in _WIDE:
+        c = Case(**WIDE_OPTION_CASES[name])
+        ref, gap = c.reference()
+        _WIDE[name] = (c, ref, gap)
+    c, ref, gap = _WIDE[name]
+    assert gap >= MIN_GAP, gap
+    if c.order > 5:   # only then does the window shift (the 7-token context is full)
+        assert all(u[0][4] > 8 for u in ref), [u[0][4] for u in ref]
+    if WIDE_OPTION_CASES[name].get("zero"):
+        assert not np.isfinite(c.emis).all() if c.is_log else (c.emis == 0).any()
+        for u in ref:
+            assert sum(math.isfinite(h[1]) for h in u) >= c.beam, len(u)
+    return c, ref, gap
+
+
+def batch_independence(dec, emis, row, n):
+    """emis [T][6][V]: utterance `row` with n frames decoded alone, then as the
+    first and as the last of the six, time-major and batch-major, the other
+    rows with lengths of their own: bit-identical every time."""
+    T = emis.shape[0]
+    u = emis[:, row:row + 1]
+    dec.decode(u, is_log=True, lengths=[n])
+    alone = dec.beams(64)[0]
+    assert len(alone) >= 2
+    for at, others in ((0, [T, 1, 5, 3, T - 1]), (5, [2, T, 1, T - 2, 4])):
+        batch = emis.copy()
+        batch[:, at] = u[:, 0]
+        lengths = others[:at] + [n] + others[at:]
+        dec.decode(batch, is_log=True, lengths=lengths)
+        assert dec.beams(64)[at] == alone   # bit-identical: labels, ranks and every fp64 score
+        dec.decode(np.ascontiguousarray(batch.transpose(1, 0, 2)), is_log=True, lengths=lengths, batch_major=True)
+        assert dec.beams(64)[at] == alone
 
 
 # ---- the worked example: fusion keeps what the plain search pruned ------------

@@ -8,6 +8,7 @@ import re
 import numpy as np
 
 from conftest import asr
+from ctc_lm_cases import MIN_GAP, zero_out
 from ctc_wordlm_reference import WordFusedSearch
 from lm_reference import ArpaModel, random_arpa
 
@@ -24,12 +25,14 @@ class WordCase:
     tokens are those spellings, the emissions drawn from `seed`; `peak` =
     (labels per frame, logit bonus) pushes one label per frame; `oov` is the
     model's oov_log10; n_letters limits the random spellings to the first
-    letters and `boost` raises those letters' and the space's logits."""
+    letters and `boost` raises those letters' and the space's logits; `zero` is
+    the fraction of the non-blank emissions set to probability 0 (-inf when
+    is_log), drawn from a generator of its own."""
 
     def __init__(self, seed, T, B, V, beam, n_words=6, max_word=3, order=3, bos=True, eos=False, unk=False,
                  alpha=0.7, beta=0.3, top_n=0, quant=0.0, is_log=True, batch_major=False, lengths=None, closed=False,
                  max_states=0, sigma=2.0, words=None, peak=None, oov=-100.0, n_letters=0,
-                 boost=0.0):
+                 boost=0.0, zero=0.0):
         self.seed, self.T, self.B, self.V, self.beam, self.order = seed, T, B, V, beam, order
         self.bos, self.eos, self.alpha, self.beta, self.top_n = bos, eos, alpha, beta, top_n
         self.is_log, self.batch_major, self.lengths = is_log, batch_major, lengths
@@ -60,6 +63,8 @@ class WordCase:
         logp = logits - np.log(np.exp(logits).sum(-1, keepdims=True))
         if quant:
             logp = np.round(logp / quant) * quant   # few distinct values: the label-id tie rule decides
+        if zero:
+            logp = zero_out(logp, seed, zero, 0)
         self.emis = (logp if is_log else np.exp(logp)).astype(np.float32)   # [T][B][V]
 
     def lm(self):
@@ -140,6 +145,53 @@ HOST_CASES = {
     "nine_words_closed": dict(seed=25, T=20, B=2, V=5, beam=4, order=5, n_words=3, max_word=1, closed=True, eos=True,
                               peak=([1, 4, 2, 4, 3, 4, 1, 4, 1, 4, 2, 4, 3, 4, 2, 4, 1, 4, 3, 0], 12.0)),
 }
+
+
+# ---- every option at the widths where the kernel's paths change -----------------
+# Both lexicon modes between them; seeds chosen on the CPU with the reference
+# alone, as above.
+WIDE_OPTION_CASES = {
+    # closed, </s> on, <s> off, lengths, wide beam
+    "beam50_closed_eos_no_bos_lengths": dict(seed=900, T=48, B=3, V=29, beam=50, order=5, sigma=8.0, n_words=200,
+                                             max_word=3, n_letters=12, closed=True, eos=True, bos=False,
+                                             lengths=[48, 3, 20]),
+    # open, <unk>, beta < 0, strides, probabilities
+    "beam50_open_unk_strides": dict(seed=900, T=40, B=3, V=29, beam=50, order=5, sigma=8.0, n_words=200, max_word=3,
+                                    n_letters=12, oov=-4.0, unk=True, batch_major=True, is_log=False, beta=-1.5),
+    # open, the label cutoff, strides and lengths at V = 1000
+    "v1000_top40_open_strides": dict(seed=900, T=24, B=3, V=1000, beam=20, top_n=40, n_words=200, max_word=3,
+                                     n_letters=28, boost=6.0, oov=-4.0, batch_major=True, lengths=[24, 5, 13]),
+    # many short words: more than 8 are scored, the window shifts.  The word bonus is what makes them many:
+    # at the default beta the best hypotheses of 200 seeds had 1 to 4 words, the LM cost of a word being what it is
+    "order8_short_words": dict(seed=900, T=40, B=2, V=8, beam=20, order=8, n_words=20, max_word=2, n_letters=4,
+                               sigma=4.0, boost=2.0, oov=-4.0, beta=6.0),
+    # zero probabilities: log(0) and the -inf keys of the select
+    "zero_probabilities_closed": dict(seed=910, T=40, B=8, V=29, beam=8, n_words=60, max_word=4, n_letters=8,
+                                      closed=True, is_log=False, zero=0.3),
+}
+
+_WIDE = {}
+
+
+def wide_reference(name):
+    """(case, reference beams, gap) of a WIDE_OPTION_CASES entry, computed once per
+    session and never modified, with what the entry needs of its reference
+    checked: a gap >= MIN_GAP; order 8: more than 8 words scored in the best
+    hypothesis; zeroed emissions: at least `beam` hypotheses of finite total per
+    utterance."""
+    if name not in _WIDE:
+        c = WordCase(**WIDE_OPTION_CASES[name])
+        ref, gap = c.reference()
+        _WIDE[name] = (c, ref, gap)
+    c, ref, gap = _WIDE[name]
+    assert gap >= MIN_GAP, gap
+    if c.order > 5:   # only then does the window shift (the 7-token context is full)
+        assert all(u[0][4] > 8 for u in ref), [u[0][4] for u in ref]
+    if WIDE_OPTION_CASES[name].get("zero"):
+        assert (c.emis == 0).any()
+        for u in ref:
+            assert sum(math.isfinite(h[1]) for h in u) >= c.beam, len(u)
+    return c, ref, gap
 
 
 # ---- the worked example: the word LM keeps what the plain search pruned -------

@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import asr, oracle
-from ctc_lm_cases import (HOST_CASES, MIN_GAP, TOL, WORKED_ARPA, WORKED_BEST, WORKED_CTC, WORKED_EMIS, WORKED_LABELS,
-                          WORKED_LM10, WORKED_TOTAL, Case, assert_same_beams, close, tie_case)
+from ctc_lm_cases import (HOST_CASES, MIN_GAP, TOL, WIDE_OPTION_CASES, WORKED_ARPA, WORKED_BEST, WORKED_CTC,
+                          WORKED_EMIS, WORKED_LABELS, WORKED_LM10, WORKED_TOTAL, Case, assert_same_beams, close,
+                          tie_case, wide_reference)
 from ctc_lm_reference import LN10, FusedSearch
 from lm_reference import BOS, ArpaModel
 
@@ -66,10 +67,7 @@ def test_reference_exhaustive(T, V, blank, seed):
 
 
 # ---- 3. the host twin against the reference -----------------------------------
-@pytest.mark.parametrize("name", sorted(HOST_CASES))
-def test_host_twin_matches_reference(name):
-    c = Case(**HOST_CASES[name])
-    ref, gap = c.reference()
+def check_host(c, ref, gap, name):
     assert gap >= MIN_GAP, gap
     lm = c.lm()
     dec = c.decoder(lm)
@@ -80,6 +78,20 @@ def test_host_twin_matches_reference(name):
     assert labels == [list(u[0][0]) for u in ref]
     assert all(close(t, u[0][1]) for t, u in zip(totals, ref))
     dec.close()
+
+
+@pytest.mark.parametrize("name", sorted(HOST_CASES))
+def test_host_twin_matches_reference(name):
+    c = Case(**HOST_CASES[name])
+    ref, gap = c.reference()
+    check_host(c, ref, gap, name)
+
+
+@pytest.mark.parametrize("name", sorted(WIDE_OPTION_CASES))
+def test_host_twin_matches_reference_on_wide_option_cases(name):
+    """The table test_ctc_lm_gpu.py runs on the device: a failure there with
+    this one passing is the kernel's."""
+    check_host(*wide_reference(name), name)
 
 
 def test_host_twin_without_lm_weight_is_the_oracle():
@@ -121,6 +133,26 @@ def test_tie_overflow_is_reported():
     auto.decode_host(emis, is_log=False)
     with pytest.raises(asr.AsrError) as e:
         auto.beams(8)
+    assert e.value.status == asr.ASR_ERR_BEAM_OVERFLOW
+
+
+def test_capacity_exactly_full_and_one_state_more():
+    """32 tied states in 32 slots decode, 33 are an overflow."""
+    text, labels, emis = tie_case(V=32, beam=2, T=1)
+    lm = asr.NGramLM.from_string(text)
+    model = ArpaModel(text)
+    tok = [model.ids.get(s, -1) if s != "" else -1 for s in labels]
+    ref, _ = FusedSearch(model, 32, 2, 0, tok, 0.5, 0.0, bos=True).decode(emis[:, 0], is_log=False)
+    assert len(ref) == 32
+    dec = asr.CTCLMDecoder(32, 2, lm, lm.label_tokens(labels), 0.5, 0.0)
+    dec.decode_host(emis, is_log=False)
+    assert_same_beams(dec.beams(256), [ref])
+    text, labels, emis = tie_case(V=33, beam=2, T=1)
+    lm = asr.NGramLM.from_string(text)
+    dec = asr.CTCLMDecoder(33, 2, lm, lm.label_tokens(labels), 0.5, 0.0)
+    dec.decode_host(emis, is_log=False)
+    with pytest.raises(asr.AsrError) as e:
+        dec.beams(256)
     assert e.value.status == asr.ASR_ERR_BEAM_OVERFLOW
 
 

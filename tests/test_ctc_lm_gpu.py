@@ -1,21 +1,24 @@
 """GPU checks of the LM-fused CTC beam search (asr_ctc_lm_decode): the
-device against the library's host twin on the same handle (labels, ranks and
-n_tokens identical, scores to 1e-9), the small cases also against the Python
-reference; every randomised case asserts the smallest gap first (a seed chosen
-so that a rank difference cannot be rounding)."""
+device against the library's host twin on the same handle and against the Python
+reference (labels, ranks and n_tokens identical, scores to 1e-9), at every shape
+and under every option; every randomised case asserts the smallest gap first (a
+seed chosen so that a rank difference cannot be rounding)."""
 import numpy as np
 import pytest
 
 from conftest import asr
-from ctc_lm_cases import (HOST_CASES, MIN_GAP, WORKED_ARPA, WORKED_BEST, WORKED_EMIS, WORKED_LABELS, Case,
-                          assert_same_beams, close, tie_case)
+from ctc_lm_cases import (HOST_CASES, MIN_GAP, WIDE_OPTION_CASES, WORKED_ARPA, WORKED_BEST, WORKED_EMIS, WORKED_LABELS,
+                          Case, assert_same_beams, batch_independence, close, largest_difference, tie_case,
+                          wide_reference)
 from ctc_lm_reference import FusedSearch
 from lm_reference import ArpaModel
 
 pytestmark = pytest.mark.gpu
 
 
-def run(case, reference=False):
+def run(case, reference=None, what=""):
+    """Device against the host twin, then against the Python reference:
+    `reference` is (beams, gap) where the caller has it already."""
     lm = case.lm()
     lm.upload()
     dec = case.decoder(lm)
@@ -23,10 +26,10 @@ def run(case, reference=False):
     assert gap >= MIN_GAP, gap
     dev = case.device(dec)
     assert_same_beams(dev, host, "device vs host twin")
-    if reference:
-        ref, ref_gap = case.reference()
-        assert ref_gap >= MIN_GAP, ref_gap
-        assert_same_beams(dev, ref, "device vs reference")
+    ref, ref_gap = reference or case.reference()
+    assert ref_gap >= MIN_GAP, ref_gap
+    print("%s: reference gap %.3g, largest |device - reference| %.3g" % (what, ref_gap, largest_difference(dev, ref)))
+    assert_same_beams(dev, ref, "device vs reference")
     dec.close()
     return dev
 
@@ -35,25 +38,34 @@ def run(case, reference=False):
 # wide beam; V and beam + 1 across a wave boundary; more utterances than CUs; a
 # large vocabulary with the label cutoff.
 SHAPES = {
-    "t1": (dict(seed=201, T=1, B=3, V=5, beam=2), True),
-    "t6": (dict(seed=202, T=6, B=4, V=5, beam=3), True),
-    "t40_v29": (dict(seed=305, T=40, B=8, V=29, beam=8), False),
-    "t64_beam50_order5": (dict(seed=601, T=64, B=5, V=29, beam=50, order=5, sigma=8.0), False),
-    "v63": (dict(seed=205, T=16, B=2, V=63, beam=8), False),
-    "v64": (dict(seed=206, T=16, B=2, V=64, beam=8), False),
-    "v65": (dict(seed=207, T=16, B=2, V=65, beam=8), False),
-    "beam62": (dict(seed=208, T=16, B=2, V=12, beam=62), False),
-    "beam63": (dict(seed=302, T=16, B=2, V=12, beam=63), False),
-    "beam64": (dict(seed=210, T=16, B=2, V=12, beam=64), False),
-    "b300": (dict(seed=211, T=8, B=300, V=6, beam=3), False),
-    "v1000_top40": (dict(seed=302, T=24, B=2, V=1000, beam=20, top_n=40), False),
+    "t1": dict(seed=201, T=1, B=3, V=5, beam=2),
+    "t6": dict(seed=202, T=6, B=4, V=5, beam=3),
+    "t40_v29": dict(seed=305, T=40, B=8, V=29, beam=8),
+    "t64_beam50_order5": dict(seed=601, T=64, B=5, V=29, beam=50, order=5, sigma=8.0),
+    "v63": dict(seed=205, T=16, B=2, V=63, beam=8),
+    "v64": dict(seed=206, T=16, B=2, V=64, beam=8),
+    "v65": dict(seed=207, T=16, B=2, V=65, beam=8),
+    "beam62": dict(seed=208, T=16, B=2, V=12, beam=62),
+    "beam63": dict(seed=302, T=16, B=2, V=12, beam=63),
+    "beam64": dict(seed=210, T=16, B=2, V=12, beam=64),
+    "b300": dict(seed=211, T=8, B=300, V=6, beam=3),
+    "v1000_top40": dict(seed=302, T=24, B=2, V=1000, beam=20, top_n=40),
 }
 
 
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_device_matches_host_twin(name):
-    kw, small = SHAPES[name]
-    run(Case(**kw), reference=small)
+    """... and the Python reference, at every shape."""
+    run(Case(**SHAPES[name]), what=name)
+
+
+@pytest.mark.parametrize("name", sorted(WIDE_OPTION_CASES))
+def test_device_wide_option_cases(name):
+    """Every option at a width of more than one wave of pairs or on a limit:
+    device, host twin and reference agree (test_ctc_lm_cpu.py runs the twin
+    against the reference on the same table)."""
+    case, ref, gap = wide_reference(name)
+    run(case, reference=(ref, gap), what=name)
 
 
 @pytest.mark.parametrize("name", sorted(HOST_CASES))
@@ -62,7 +74,7 @@ def test_device_small_cases(name):
     the label cutoff on quantised emissions, lengths 1 .. T, batch-major
     strides, probabilities, a non-zero blank with codes: device, host twin and
     reference agree."""
-    run(Case(**HOST_CASES[name]), reference=True)
+    run(Case(**HOST_CASES[name]), what=name)
 
 
 @pytest.mark.parametrize("kw", [dict(seed=221, T=40, B=8, V=29, beam=8), dict(seed=222, T=16, B=3, V=65, beam=8),
@@ -112,6 +124,43 @@ def test_ties_and_overflow_on_the_device():
         d.close()
 
 
+def test_capacity_exactly_full_and_one_state_more():
+    """32 tied states in 32 slots decode, 33 are an overflow: the kernel's
+    comparison with the capacity, pinned from both sides."""
+    text, labels, emis = tie_case(V=32, beam=2, T=1)
+    lm = asr.NGramLM.from_string(text)
+    lm.upload()
+    model = ArpaModel(text)
+    tok = [model.ids.get(s, -1) if s != "" else -1 for s in labels]
+    ref, _ = FusedSearch(model, 32, 2, 0, tok, 0.5, 0.0, bos=True).decode(emis[:, 0], is_log=False)
+    assert len(ref) == 32
+    for max_states in (3, 0):   # explicit and automatic capacity: both 32 slots
+        dec = asr.CTCLMDecoder(32, 2, lm, lm.label_tokens(labels), 0.5, 0.0, max_states=max_states)
+        dec.decode(emis, is_log=False)
+        got = dec.beams(256)
+        assert len(got[0]) == 32
+        assert_same_beams(got, [ref])
+        dec.close()
+    text, labels, emis = tie_case(V=33, beam=2, T=1)
+    lm33 = asr.NGramLM.from_string(text)
+    lm33.upload()
+    untied = emis.copy()
+    untied[:, 0, 1:] *= np.linspace(1.0, 0.5, 32, dtype=np.float32)
+    model = ArpaModel(text)
+    tok = [model.ids.get(s, -1) if s != "" else -1 for s in labels]
+    ref33, _ = FusedSearch(model, 33, 2, 0, tok, 0.5, 0.0, bos=True).decode(untied[:, 0], is_log=False)
+    assert len(ref33) == 3
+    for max_states in (3, 0):
+        dec = asr.CTCLMDecoder(33, 2, lm33, lm33.label_tokens(labels), 0.5, 0.0, max_states=max_states)
+        dec.decode(emis, is_log=False)
+        with pytest.raises(asr.AsrError) as e:
+            dec.beams(256)
+        assert e.value.status == asr.ASR_ERR_BEAM_OVERFLOW
+        dec.decode(untied, is_log=False)   # the handle goes on working
+        assert_same_beams(dec.beams(256), [ref33])
+        dec.close()
+
+
 def test_results_do_not_depend_on_the_batch():
     c = Case(seed=231, T=12, B=6, V=9, beam=5, order=3)
     lm = c.lm()
@@ -138,6 +187,17 @@ def test_results_do_not_depend_on_the_batch():
     dec.close()
 
 
+def test_results_do_not_depend_on_the_batch_with_the_label_cutoff():
+    """The candidate labels of a frame are read at an index that depends on the
+    utterance's row and on T: 20 of 64 labels, lengths on every row."""
+    c = Case(seed=235, T=12, B=6, V=65, beam=8, top_n=20)
+    lm = c.lm()
+    lm.upload()
+    dec = c.decoder(lm)
+    batch_independence(dec, c.emis, 2, 9)
+    dec.close()
+
+
 def test_workspace_reuse_growing_then_shrinking():
     small = Case(seed=232, T=5, B=2, V=7, beam=4)
     large = Case(seed=232, T=20, B=9, V=7, beam=4)   # the same model (same seed and V), more frames and rows
@@ -149,6 +209,25 @@ def test_workspace_reuse_growing_then_shrinking():
         host, gap = c.host(dec)
         assert gap >= MIN_GAP, gap
         assert_same_beams(c.device(dec), host)
+    dec.close()
+
+
+def test_workspace_reuse_with_the_label_cutoff():
+    """A longer decode leaves candidate rows behind: the shorter one after it
+    must read none of them."""
+    small = Case(seed=236, T=5, B=2, V=12, beam=4, top_n=4)
+    large = Case(seed=236, T=20, B=9, V=12, beam=4, top_n=4)   # the same model (same seed and V)
+    assert small.text == large.text
+    lm = small.lm()
+    lm.upload()
+    dec = small.decoder(lm)
+    for c in (large, small, large, small):
+        host, gap = c.host(dec)
+        assert gap >= MIN_GAP, gap
+        assert_same_beams(c.device(dec), host)
+    ref, ref_gap = small.reference()
+    assert ref_gap >= MIN_GAP, ref_gap
+    assert_same_beams(small.device(dec), ref)
     dec.close()
 
 

@@ -12,8 +12,9 @@ import pytest
 from conftest import asr, oracle
 from ctc_lm_cases import MIN_GAP, assert_same_beams, close
 from ctc_lm_reference import LN10, FusedSearch
-from ctc_wordlm_cases import (HOST_CASES, WORKED_ARPA, WORKED_BEAM, WORKED_BEST, WORKED_CTC, WORKED_EMIS,
-                              WORKED_LABELS, WORKED_LM10, WORKED_PLAIN, WORKED_RANKED, WORKED_TOTAL, WordCase)
+from ctc_wordlm_cases import (HOST_CASES, WIDE_OPTION_CASES, WORKED_ARPA, WORKED_BEAM, WORKED_BEST, WORKED_CTC,
+                              WORKED_EMIS, WORKED_LABELS, WORKED_LM10, WORKED_PLAIN, WORKED_RANKED, WORKED_TOTAL,
+                              WordCase, wide_reference)
 from ctc_wordlm_reference import WordFusedSearch
 from lm_reference import ArpaModel
 
@@ -36,9 +37,10 @@ def check_hypotheses(c, lm, beams):
             assert abs(total - model) <= 1e-12 * max(1.0, abs(model)), (h, model)
 
 
-def run_host(c, name=""):
-    """Host twin against the reference; -> (beams, reference, lm)."""
-    ref, gap = c.reference()
+def run_host(c, name="", reference=None):
+    """Host twin against the reference ((beams, gap) where the caller has it
+    already); -> (beams, reference, lm)."""
+    ref, gap = reference or c.reference()
     assert gap >= MIN_GAP, gap
     lm = c.lm()
     lex = c.lexicon(lm)
@@ -59,6 +61,14 @@ def run_host(c, name=""):
 @pytest.mark.parametrize("name", sorted(HOST_CASES))
 def test_host_twin_matches_reference(name):
     run_host(WordCase(**HOST_CASES[name]), name)
+
+
+@pytest.mark.parametrize("name", sorted(WIDE_OPTION_CASES))
+def test_host_twin_matches_reference_on_wide_option_cases(name):
+    """The table test_ctc_wordlm_gpu.py runs on the device: a failure there with
+    this one passing is the kernel's."""
+    c, ref, gap = wide_reference(name)
+    run_host(c, name, reference=(ref, gap))
 
 
 def test_context_window_shifts_past_seven_words():

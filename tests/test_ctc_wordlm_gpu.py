@@ -1,16 +1,16 @@
 """GPU checks of the word mode of the LM-fused CTC beam search (the lexicon trie
 on the device): the device against the library's host twin on the
-same handle (labels, ranks and word counts identical, scores to 1e-9), the small
-cases also against the Python reference; every compared case asserts the host
-twin's smallest gap first (seeds chosen on the CPU so that a rank difference
-cannot be rounding)."""
+same handle and against the Python reference (labels, ranks and word counts
+identical, scores to 1e-9), at every shape and under every option; every
+compared case asserts the smallest gap first (seeds chosen on the CPU so that a
+rank difference cannot be rounding)."""
 import numpy as np
 import pytest
 
 from conftest import asr
-from ctc_lm_cases import MIN_GAP, assert_same_beams, close
-from ctc_wordlm_cases import (HOST_CASES, WORKED_ARPA, WORKED_BEAM, WORKED_BEST, WORKED_EMIS, WORKED_LABELS, WordCase,
-                              letter)
+from ctc_lm_cases import MIN_GAP, assert_same_beams, batch_independence, close, largest_difference
+from ctc_wordlm_cases import (HOST_CASES, WIDE_OPTION_CASES, WORKED_ARPA, WORKED_BEAM, WORKED_BEST, WORKED_EMIS,
+                              WORKED_LABELS, WordCase, letter, wide_reference)
 from ctc_wordlm_reference import WordFusedSearch
 from lm_reference import ArpaModel
 
@@ -25,16 +25,18 @@ def handles(case):
     return lm, lex, case.decoder(lm, lex)
 
 
-def run(case, reference=False):
+def run(case, reference=None, what=""):
+    """Device against the host twin, then against the Python reference:
+    `reference` is (beams, gap) where the caller has it already."""
     lm, lex, dec = handles(case)
     host, gap = case.host(dec)
     assert gap >= MIN_GAP, gap
     dev = case.device(dec)
     assert_same_beams(dev, host, "device vs host twin")
-    if reference:
-        ref, ref_gap = case.reference()
-        assert ref_gap >= MIN_GAP, ref_gap
-        assert_same_beams(dev, ref, "device vs reference")
+    ref, ref_gap = reference or case.reference()
+    assert ref_gap >= MIN_GAP, ref_gap
+    print("%s: reference gap %.3g, largest |device - reference| %.3g" % (what, ref_gap, largest_difference(dev, ref)))
+    assert_same_beams(dev, ref, "device vs reference")
     dec.close()
     lex.close()
     return dev
@@ -50,52 +52,61 @@ def all_letters(V, extra):
 # pairs; order 5 with a wide beam and peaked emissions; more than 7 words; the
 # widest sibling search (a root with 63 and with 64 children, across the wave
 # width); capacities 64 and 256; a large vocabulary with the label cutoff; more
-# utterances than CUs.  The flag says whether the Python reference runs too.
+# utterances than CUs.
 SHAPES = {
-    "t1_open": (dict(seed=401, T=1, B=3, V=5, beam=2), True),
-    "t1_closed": (dict(seed=402, T=1, B=3, V=5, beam=2, closed=True), True),
-    "t8_open": (dict(seed=403, T=8, B=4, V=5, beam=3), True),
-    "t8_closed": (dict(seed=404, T=8, B=4, V=5, beam=3, closed=True), True),
-    "t40_v29_open": (dict(seed=405, T=40, B=8, V=29, beam=8, n_words=60, max_word=4, n_letters=8, oov=-4.0,
-                          boost=3.0), False),
-    "t40_v29_closed": (dict(seed=1406, T=40, B=8, V=29, beam=8, n_words=60, max_word=4, n_letters=8, closed=True),
-                       False),
-    "t64_beam50_order5_open": (dict(seed=10407, T=64, B=5, V=29, beam=50, order=5, sigma=8.0, n_words=200, max_word=3,
-                                    n_letters=12, oov=-4.0), False),
-    "t64_beam50_order5_closed": (dict(seed=23408, T=64, B=5, V=29, beam=50, order=5, sigma=8.0, n_words=200, max_word=3,
-                                      n_letters=12, closed=True), False),
-    "nine_words": (HOST_CASES["nine_words"], True),
-    "nine_words_closed": (HOST_CASES["nine_words_closed"], True),
-    "v65_root63_open": (dict(seed=409, T=12, B=2, V=65, beam=8, oov=-4.0, n_letters=10, boost=3.0,
-                            words=all_letters(65, [(0, 1), (62, 0), (5, 5)])), False),
-    "v65_root63_closed": (dict(seed=410, T=12, B=2, V=65, beam=8, closed=True, n_letters=10, boost=3.0,
-                               words=all_letters(65, [(0, 1), (62, 0), (5, 5)])), False),
-    "v66_root64_open": (dict(seed=411, T=12, B=2, V=66, beam=8, oov=-4.0, n_letters=10, boost=3.0,
-                            words=all_letters(66, [(0, 1), (63, 0), (63, 63)])), False),
-    "v66_root64_closed": (dict(seed=412, T=12, B=2, V=66, beam=8, closed=True, n_letters=10, boost=3.0,
-                               words=all_letters(66, [(0, 1), (63, 0), (63, 63)])), False),
-    "capacity64": (dict(seed=413, T=16, B=2, V=12, beam=40, max_states=64, n_words=30, n_letters=5, sigma=8.0,
-                        oov=-4.0), False),
-    "capacity256_closed": (dict(seed=414, T=16, B=2, V=12, beam=200, n_words=30, n_letters=5, closed=True,
-                                sigma=8.0), False),
-    "capacity256_open": (dict(seed=415, T=12, B=2, V=8, beam=220, max_states=256, n_words=12, n_letters=4,
-                              sigma=8.0, oov=-4.0), False),
-    "v1000_top40_closed": (dict(seed=416, T=24, B=2, V=1000, beam=20, top_n=40, closed=True, n_words=200, max_word=3,
-                                n_letters=28, boost=6.0), False),
-    "b300_open": (dict(seed=1417, T=8, B=300, V=6, beam=3), False),
-    "b300_closed": (dict(seed=418, T=8, B=300, V=6, beam=3, closed=True), False),
+    "t1_open": dict(seed=401, T=1, B=3, V=5, beam=2),
+    "t1_closed": dict(seed=402, T=1, B=3, V=5, beam=2, closed=True),
+    "t8_open": dict(seed=403, T=8, B=4, V=5, beam=3),
+    "t8_closed": dict(seed=404, T=8, B=4, V=5, beam=3, closed=True),
+    "t40_v29_open": dict(seed=405, T=40, B=8, V=29, beam=8, n_words=60, max_word=4, n_letters=8, oov=-4.0,
+                         boost=3.0),
+    "t40_v29_closed": dict(seed=1406, T=40, B=8, V=29, beam=8, n_words=60, max_word=4, n_letters=8, closed=True),
+    "t64_beam50_order5_open": dict(seed=10407, T=64, B=5, V=29, beam=50, order=5, sigma=8.0, n_words=200, max_word=3,
+                                   n_letters=12, oov=-4.0),
+    "t64_beam50_order5_closed": dict(seed=23408, T=64, B=5, V=29, beam=50, order=5, sigma=8.0, n_words=200, max_word=3,
+                                     n_letters=12, closed=True),
+    "nine_words": HOST_CASES["nine_words"],
+    "nine_words_closed": HOST_CASES["nine_words_closed"],
+    "v65_root63_open": dict(seed=409, T=12, B=2, V=65, beam=8, oov=-4.0, n_letters=10, boost=3.0,
+                           words=all_letters(65, [(0, 1), (62, 0), (5, 5)])),
+    "v65_root63_closed": dict(seed=410, T=12, B=2, V=65, beam=8, closed=True, n_letters=10, boost=3.0,
+                              words=all_letters(65, [(0, 1), (62, 0), (5, 5)])),
+    "v66_root64_open": dict(seed=411, T=12, B=2, V=66, beam=8, oov=-4.0, n_letters=10, boost=3.0,
+                           words=all_letters(66, [(0, 1), (63, 0), (63, 63)])),
+    "v66_root64_closed": dict(seed=412, T=12, B=2, V=66, beam=8, closed=True, n_letters=10, boost=3.0,
+                              words=all_letters(66, [(0, 1), (63, 0), (63, 63)])),
+    "capacity64": dict(seed=413, T=16, B=2, V=12, beam=40, max_states=64, n_words=30, n_letters=5, sigma=8.0,
+                       oov=-4.0),
+    "capacity256_closed": dict(seed=414, T=16, B=2, V=12, beam=200, n_words=30, n_letters=5, closed=True,
+                               sigma=8.0),
+    "capacity256_open": dict(seed=415, T=12, B=2, V=8, beam=220, max_states=256, n_words=12, n_letters=4,
+                             sigma=8.0, oov=-4.0),
+    "v1000_top40_closed": dict(seed=416, T=24, B=2, V=1000, beam=20, top_n=40, closed=True, n_words=200, max_word=3,
+                               n_letters=28, boost=6.0),
+    "b300_open": dict(seed=1417, T=8, B=300, V=6, beam=3),
+    "b300_closed": dict(seed=418, T=8, B=300, V=6, beam=3, closed=True),
 }
 
 
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_device_matches_host_twin(name):
-    kw, small = SHAPES[name]
-    run(WordCase(**kw), reference=small)
+    """... and the Python reference, at every shape."""
+    run(WordCase(**SHAPES[name]), what=name)
+
+
+@pytest.mark.parametrize("name", sorted(WIDE_OPTION_CASES))
+def test_device_wide_option_cases(name):
+    """Every option at a width of more than one wave of pairs, in one lexicon
+    mode or the other: device, host twin and reference agree
+    (test_ctc_wordlm_cpu.py runs the twin against the reference on the same
+    table)."""
+    case, ref, gap = wide_reference(name)
+    run(case, reference=(ref, gap), what=name)
 
 
 def test_widest_sibling_runs():
     for V, n in ((65, 63), (66, 64)):
-        c = WordCase(**SHAPES["v%d_root%d_open" % (V, n)][0])
+        c = WordCase(**SHAPES["v%d_root%d_open" % (V, n)])
         lm = c.lm()
         assert c.lexicon(lm).info()["max_children"] == n
 
@@ -103,7 +114,7 @@ def test_widest_sibling_runs():
 @pytest.mark.parametrize("name", ["bos_off_eos_on_closed", "beta_neg", "unk", "top3_closed", "lengths_closed",
                                   "batch_major", "probabilities"])
 def test_device_small_cases(name):
-    run(WordCase(**HOST_CASES[name]), reference=True)
+    run(WordCase(**HOST_CASES[name]), what=name)
 
 
 @pytest.mark.parametrize("kw", [dict(seed=421, T=40, B=8, V=29, beam=8, n_words=40, n_letters=8),
@@ -194,6 +205,15 @@ def test_results_do_not_depend_on_the_batch(closed):
     for o in outs:
         assert o == alone   # bit-identical: labels, ranks and every fp64 score
     dec.close()
+
+
+def test_results_do_not_depend_on_the_batch_with_the_label_cutoff():
+    """Closed mode with 20 of 64 candidate labels a frame, lengths on every row."""
+    c = WordCase(seed=436, T=12, B=6, V=65, beam=8, top_n=20, closed=True, n_words=40, n_letters=8, boost=3.0)
+    lm, lex, dec = handles(c)
+    batch_independence(dec, c.emis, 2, 9)
+    dec.close()
+    lex.close()
 
 
 def test_workspace_reuse_across_decodes_of_different_T():
