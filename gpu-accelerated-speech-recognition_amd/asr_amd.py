@@ -56,6 +56,12 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           the same search with the n-gram LM fused
                                           into every prune (asr_rnnt_lm_*,
                                           asr_rnnt_beam_lm*); no reference member
+    TransducerDecoder.score(enc, targets) / .align(enc, targets) / .rescore(nbest, enc)
+                                          exact transducer log-likelihood, best
+                                          alignment and emission frames of given
+                                          transcripts, the joint fused over the
+                                          (t, u) grid (asr_rnnt_align*); no
+                                          reference member
 
 The native library is required: importing this module on a machine where
 libasr_amd.so is missing raises, there is no fallback path.
@@ -115,6 +121,7 @@ EXPORTS = [
     "asr_rnnt_beam_workspace_bytes", "asr_rnnt_beam", "asr_rnnt_beam_host",
     "asr_rnnt_lm_create", "asr_rnnt_lm_destroy", "asr_rnnt_beam_lm_workspace_bytes", "asr_rnnt_beam_lm",
     "asr_rnnt_beam_lm_host",
+    "asr_rnnt_align_workspace_bytes", "asr_rnnt_align", "asr_rnnt_align_host",
     "asr_ctc_create", "asr_ctc_destroy", "asr_ctc_decode",
     "asr_ctc_get_best", "asr_ctc_get_beams", "asr_ctc_last_kernel_ms", "asr_ctc_set_waves",
     "asr_ctc_get_config", "asr_ctc_decode_ex", "asr_ctc_decode_segment", "asr_ctc_set_semantics",
@@ -271,6 +278,8 @@ def lib() -> ctypes.CDLL:
         "asr_rnnt_lm_destroy": [_vp],
         "asr_rnnt_beam_lm": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_beam_lm_host": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_align": [_vp, _vp, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_align_host": [_vp, _vp, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
         "asr_ctc_create": [_vp, _i, _i, _i, _i, ctypes.POINTER(_vp)],
         "asr_ctc_destroy": [_vp],
         "asr_ctc_decode": [_vp, _vp, _i, _i, _i, _vp],
@@ -309,6 +318,8 @@ def lib() -> ctypes.CDLL:
     L.asr_rnnt_beam_workspace_bytes.restype = _sz
     L.asr_rnnt_beam_lm_workspace_bytes.argtypes = [_vp, _i, _i, _i]
     L.asr_rnnt_beam_lm_workspace_bytes.restype = _sz
+    L.asr_rnnt_align_workspace_bytes.argtypes = [_vp, _i, _i, _i, _i]
+    L.asr_rnnt_align_workspace_bytes.restype = _sz
     _lib = L
     return L
 
@@ -2036,6 +2047,8 @@ class CTCLMDecoder:
 # ------------------------------------------------------------ RNN-T (transducer)
 RNNT_ACT_RELU, RNNT_ACT_TANH = 0, 1    # ASR_RNNT_ACT_*
 RNNT_ACTS = {"relu": RNNT_ACT_RELU, "tanh": RNNT_ACT_TANH}
+RNNT_LATTICE_STANDARD, RNNT_LATTICE_ONE_PER_FRAME = 0, 1   # asr_rnnt_align's topology
+RNNT_TOPOLOGIES = {"standard": RNNT_LATTICE_STANDARD, "one_per_frame": RNNT_LATTICE_ONE_PER_FRAME}
 ASR_RNNT_MAX_LAYERS = 2
 
 
@@ -2447,6 +2460,128 @@ class TransducerDecoder:
                                        _ptr(margin) if margins else None), "asr_rnnt_beam_host")
         res = self._beam_unpack(B, max_out, tok, ts, hl, sc, nhyp)
         return (res, margin) if margins else res
+
+    # ---- lattice scoring and forced alignment (asr_rnnt_align*; defined in include/asr_amd.h)
+    def align_workspace_bytes(self, T: int, B: int, N: int, max_target_len: int) -> int:
+        return int(lib().asr_rnnt_align_workspace_bytes(self.h, T, B, N, max_target_len))
+
+    def align_device(self, d_enc: int, T: int, B: int, d_targets: int, ldt: int, d_target_lengths: int, N: int,
+                     max_target_len: int, topology: int, d_score: int, d_vscore: int, d_frames: int, d_work: int,
+                     d_lengths: int = 0, d_utt: int = 0, stream: int = 0) -> None:
+        """asr_rnnt_align on device pointers (0 = NULL): asynchronous on stream."""
+        check(lib().asr_rnnt_align(self.h, d_enc or None, d_lengths or None, T, B, d_targets or None, ldt,
+                                   d_target_lengths or None, d_utt or None, N, max_target_len, topology,
+                                   d_score or None, d_vscore or None, d_frames or None, d_work or None,
+                                   stream or None), "asr_rnnt_align")
+
+    def _align_prepare(self, enc, targets, lengths, utt, topology, max_target_len):
+        enc, ln, T, B, _mo = self._prepare(enc, lengths, 0)
+        tg, tl, mtl = _pack_rows(targets)
+        if max_target_len is not None:    # a wider table: the results do not depend on it
+            mtl = int(max_target_len)
+            wide = np.zeros((tg.shape[0], max(mtl, 1)), np.int32)
+            k = min(wide.shape[1], tg.shape[1])
+            wide[:, :k] = tg[:, :k]
+            tg = wide
+        N = len(targets)
+        ut = None
+        if utt is not None:
+            ut = np.ascontiguousarray(utt, dtype=np.int32)
+            if ut.shape != (N,):
+                raise ValueError(f"utt: shape {ut.shape}, expected ({N},)")
+        topo = RNNT_TOPOLOGIES[topology] if isinstance(topology, str) else int(topology)
+        return enc, ln, T, B, tg, tl, mtl, N, ut, topo
+
+    def _align(self, enc, targets, lengths, utt, topology, stream, want, max_target_len=None):
+        """want = (score, vscore, frames): which outputs are asked for."""
+        enc, ln, T, B, tg, tl, mtl, N, ut, topo = self._align_prepare(enc, targets, lengths, utt, topology,
+                                                                      max_target_len)
+        if not self._uploaded:
+            self.upload()
+        ldt = tg.shape[1]
+        d_enc, d_tg, d_tl = _upload(enc, stream), _upload(tg, stream), _upload(tl, stream)
+        d_len = _upload(ln, stream) if ln is not None else None
+        d_utt = _upload(ut, stream) if ut is not None else None
+        d_sc = DeviceBytes(max(8 * N, 16)) if want[0] else None
+        d_vs = DeviceBytes(max(8 * N, 16)) if want[1] else None
+        d_fr = DeviceBytes(max(4 * N * ldt, 16)) if want[2] else None
+        need = self.align_workspace_bytes(T, B, N, mtl)
+        if need and (self._work is None or self._work.nbytes < need):
+            self._work = DeviceBytes(need)
+        self.align_device(d_enc.ptr, T, B, d_tg.ptr, ldt, d_tl.ptr, N, mtl, topo, d_sc.ptr if d_sc else 0,
+                          d_vs.ptr if d_vs else 0, d_fr.ptr if d_fr else 0, self._work.ptr if self._work else 0,
+                          d_len.ptr if d_len else 0, d_utt.ptr if d_utt else 0, stream)
+        check(lib().asr_stream_sync(stream or None), "asr_stream_sync")
+        score = _download(d_sc, (N,), np.float64, stream) if want[0] else None
+        vscore = _download(d_vs, (N,), np.float64, stream) if want[1] else None
+        frames = None
+        if want[2]:
+            fr = _download(d_fr, (N, ldt), np.int32, stream)
+            frames = [fr[n, :min(len(targets[n]), mtl)].copy() for n in range(N)]
+        return score, vscore, frames
+
+    def _align_host(self, enc, targets, lengths, utt, topology, want):
+        enc, ln, T, B, tg, tl, mtl, N, ut, topo = self._align_prepare(enc, targets, lengths, utt, topology, None)
+        ldt = tg.shape[1]
+        score = np.zeros(N, np.float64) if want[0] else None
+        vscore = np.zeros(N, np.float64) if want[1] else None
+        fr = np.zeros((N, ldt), np.int32) if want[2] else None
+        check(lib().asr_rnnt_align_host(self.h, _ptr(enc), _ptr(ln) if ln is not None else None, T, B, _ptr(tg), ldt,
+                                        _ptr(tl), _ptr(ut) if ut is not None else None, N, mtl, topo,
+                                        _ptr(score) if want[0] else None, _ptr(vscore) if want[1] else None,
+                                        _ptr(fr) if want[2] else None), "asr_rnnt_align_host")
+        frames = [fr[n, :len(targets[n])].copy() for n in range(N)] if want[2] else None
+        return score, vscore, frames
+
+    def score(self, enc, targets: Sequence[Sequence[int]], lengths=None, utt=None, topology="standard",
+              stream: int = 0) -> np.ndarray:
+        """Exact transducer log-likelihood log p(target | enc) of every target,
+        fp64 [N] (-inf: infeasible).  enc [T, B, E] time-major; targets: a list
+        of label lists, target n scored against utterance utt[n] (default n);
+        topology "standard" (a label arc stays in the frame: the training
+        lattice) or "one_per_frame" (the lattice beam_search searches)."""
+        return self._align(enc, targets, lengths, utt, topology, stream, (True, False, False))[0]
+
+    def align(self, enc, targets: Sequence[Sequence[int]], lengths=None, utt=None, topology="standard",
+              stream: int = 0):
+        """(score, vscore, frames): the forward score, the log-probability of the
+        best alignment and, per target, the frame at which that alignment emits
+        each label (int32 [U_n]; -1 when the target is infeasible), the
+        convention of decode's and beam_search's timesteps."""
+        return self._align(enc, targets, lengths, utt, topology, stream, (True, True, True))
+
+    def score_host(self, enc, targets, lengths=None, utt=None, topology="standard") -> np.ndarray:
+        """score through asr_rnnt_align_host (one thread, fp64)."""
+        return self._align_host(enc, targets, lengths, utt, topology, (True, False, False))[0]
+
+    def align_host(self, enc, targets, lengths=None, utt=None, topology="standard"):
+        """align through asr_rnnt_align_host (one thread, fp64)."""
+        return self._align_host(enc, targets, lengths, utt, topology, (True, True, True))
+
+    def rescore(self, nbest, enc, lengths=None, topology="one_per_frame", stream: int = 0, host: bool = False):
+        """An n-best of beam_search re-ranked by the exact score, as
+        CTCDecoder.rescore does: per utterance [(tokens, search_score,
+        exact_score)], exact score descending (equal scores keep the search
+        order).  A search score sums only the alignments that survived the
+        width-K prune, a lower bound; the exact one is asr_rnnt_align's forward
+        score of every hypothesis against its utterance, one call for the whole
+        batch (N = sum of K, utt[n] = the utterance; host=True: through
+        asr_rnnt_align_host).  The exact scores go into
+        nbest_mbr(log_weights_per_utt=...) as they are."""
+        targets = [list(h[0]) for u in nbest for h in u]
+        utt = [b for b, u in enumerate(nbest) for _ in u]
+        if not targets:
+            return [[] for _ in nbest]
+        if host:
+            exact = self.score_host(enc, targets, lengths=lengths, utt=utt, topology=topology)
+        else:
+            exact = self.score(enc, targets, lengths=lengths, utt=utt, topology=topology, stream=stream)
+        out, k = [], 0
+        for u in nbest:
+            rows = [(list(h[0]), float(h[2]), float(exact[k + j])) for j, h in enumerate(u)]
+            k += len(u)
+            out.append(sorted(rows, key=lambda r: -r[2]))
+        return out
 
     def close(self) -> None:
         for z, _lm in getattr(self, "_fuse", {}).values():

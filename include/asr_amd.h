@@ -1505,6 +1505,92 @@ int asr_rnnt_beam_lm_host(const asr_rnnt_lm_t* z, const float* h_enc, const int3
                           double* h_total, double* h_am, double* h_lm_log10, int32_t* h_ntok, int32_t* h_nhyp,
                           double* h_margin);
 
+/* ---- RNN-T lattice scoring and forced alignment --------------
+ * What comes after a transducer search: the exact log-likelihood of a GIVEN
+ * transcript, its best alignment and the frames at which that alignment emits
+ * each label, in fp64 log domain with the decoder's lse.  The model is an
+ * asr_rnnt handle as asr_rnnt_create / asr_rnnt_upload make it.  Target n is
+ * scored against utterance b = utt[n]; its labels are y_1 .. y_U, the
+ * utterance has len_b frames.
+ *   Predictor, teacher-forced: the greedy walk's start (h = c = 0, then one
+ *     step on Emb[blank]), then one step on each of y_1 .. y_U; h_top(u) is the
+ *     top layer's h after u labels, u = 0 .. U; g_u = h_top(u).W_pred + b_pred.
+ *   Joint: f_t = enc_t.W_enc + b_enc, z = act(f_t + g_u), logit = z.W_out +
+ *     b_out, lpb(t, u) = logit[blank] - lse(logit), and for u < U
+ *     lpy(t, u) = logit[y_{u+1}] - lse(logit).
+ *   Lattice, selected by topology:
+ *   ASR_RNNT_LATTICE_STANDARD (0): a label arc stays in the frame: the training
+ *     lattice, and the one the greedy walk moves in while it never reaches
+ *     max_symbols.
+ *       a(0, 0) = 0
+ *       a(t, u) = lse(a(t-1, u) + lpb(t-1, u), a(t, u-1) + lpy(t, u-1))
+ *       score   = a(len-1, U) + lpb(len-1, U)
+ *   ASR_RNNT_LATTICE_ONE_PER_FRAME (1): a label arc consumes the frame too: the
+ *     lattice asr_rnnt_beam searches.
+ *       a(0, 0) = 0
+ *       a(t+1, u)   (+)= a(t, u) + lpb(t, u)
+ *       a(t+1, u+1) (+)= a(t, u) + lpy(t, u)          ((+) is lse)
+ *       score = a(len, U); the target is infeasible when U > len.
+ *   Viterbi: the same recursion with max for lse; where the two candidates of a
+ *     node are exactly equal the blank predecessor wins.  vscore is the
+ *     log-probability of that best alignment, and frames[i] the frame whose
+ *     label arc emits label i: the convention of the timesteps of
+ *     asr_rnnt_greedy / asr_rnnt_beam, so they are non-decreasing under
+ *     topology 0 and strictly increasing under topology 1.
+ * d_enc [T*B][E] time-major, as asr_rnnt_greedy takes it; d_lengths int32 [B],
+ * clamped to [0, T], NULL = T; d_targets int32 [N][ldt], ldt >=
+ * max_target_len; d_target_lengths int32 [N], clamped to [0, max_target_len];
+ * d_utt int32 [N], NULL = utterance n (then N <= B); an n-best list is N = B*K
+ * targets with d_utt[n] = n / K.
+ * Outputs, each may be NULL, at least one given: d_score [N] double, the
+ * forward log-likelihood log p(y | x); d_vscore [N] double; d_frames int32
+ * [N][ldt]: entries U_n <= i < max_target_len are -1, entries at and beyond
+ * max_target_len are not touched.
+ * Infeasible target (a label that is the blank or outside [0, V), utt[n]
+ * outside [0, B), U > len under topology 1, no frames with U > 0): scores
+ * -inf, frames -1; never an out-of-range read.  No frames and U = 0: both
+ * scores 0.0.
+ * max_target_len is at most 255.
+ * d_work: asr_rnnt_align_workspace_bytes(h, T, B, N, max_target_len) bytes,
+ * 16-byte aligned; with U1 = max_target_len + 1 and up4 rounding up to a
+ * multiple of 4,
+ *     4 * (T*B*J + U1*N*(4*Hp + L*Hp + J) + N*Hp + 2*up4(N*T*U1) + up4(2*N))
+ *       + 64 * N * (T + U1)
+ * bytes: f, the predictor's input projections with its cell state, its hidden
+ * states per layer, g, the two node values lpb and lpy, two int32 per target,
+ * and one byte of back-pointers per lane and lattice step.  0 for an argument
+ * the call refuses.
+ * The device call is four stages on s: f by one GEMM; the predictor over the
+ * N targets through the library's LSTM recurrence (asr_lstm_recur_fwd /
+ * asr_lstm_fwd with the lengths U_n + 1) and g by one GEMM, both GEMMs
+ * following asr_set_dense_arith; the fused joint kernel, which forms z in LDS,
+ * multiplies by W_out on the fp32 matrix cores with a running log-sum-exp over
+ * V and writes two floats per lattice node (no logit reaches memory); and the
+ * lattice kernel, one wave per target.  Asynchronous on s, no allocation, no
+ * host synchronisation.  A target's results depend only on its own encoder
+ * frames, labels and lengths: never on N, its position, max_target_len, T, or
+ * which outputs were asked for.
+ * asr_rnnt_align_host: the same on host memory, one thread, fp64 from the fp32
+ * weights, the same tie rule; needs no upload.
+ * Checks of both, before any HIP call — ASR_ERR_ARG: h, the encoder output, the
+ * targets or their lengths NULL; non-positive T, B or N; max_target_len < 0;
+ * ldt < max_target_len; no output given; a topology other than 0 or 1; NULL
+ * d_utt with N > B.  ASR_ERR_UNSUPPORTED: max_target_len > 255; T*B, N*U1, T*U1
+ * or N * ceil(T*U1 / 16) beyond INT_MAX; N*16*Hp bytes beyond one buffer
+ * resource of the recurrence (0x7ff00000).  asr_rnnt_align only, then:
+ * ASR_ERR_ARG for a NULL d_work; ASR_ERR_STATE when the weights were not
+ * uploaded. */
+enum { ASR_RNNT_LATTICE_STANDARD = 0, ASR_RNNT_LATTICE_ONE_PER_FRAME = 1 };
+size_t asr_rnnt_align_workspace_bytes(const asr_rnnt_t* h, int T, int B, int N, int max_target_len);
+int asr_rnnt_align(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_lengths, int T, int B,
+                   const int32_t* d_targets, long ldt, const int32_t* d_target_lengths, const int32_t* d_utt, int N,
+                   int max_target_len, int topology, double* d_score, double* d_vscore, int32_t* d_frames,
+                   void* d_work, asr_stream_t s);
+int asr_rnnt_align_host(const asr_rnnt_t* h, const float* h_enc, const int32_t* h_lengths, int T, int B,
+                        const int32_t* h_targets, long ldt, const int32_t* h_target_lengths, const int32_t* h_utt,
+                        int N, int max_target_len, int topology, double* h_score, double* h_vscore,
+                        int32_t* h_frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,332 @@
+// The host code of csrc/rnnt_align.hip as a stand-alone program for a sanitizer
+// build on the CPU (`make -C gpu-accelerated-speech-recognition_amd
+// rnntaligncheck` compiles csrc/rnnt_align.hip, csrc/rnnt.hip and this file with
+// -fsanitize=address,undefined and runs the result).  It runs random small
+// scorings of the fp64 twin asr_rnnt_align_host in heap buffers of the exact
+// size (a read or write past the end is an ASan report) against a restatement
+// written here: the joint by column-wise dot products in another summation
+// order, then EVERY alignment of the target enumerated in both topologies (the
+// sum of their probabilities is the score, the largest is vscore, and the
+// alignment the frames describe must have vscore's probability), at T <= 5 and
+// U <= 3; infeasible targets, clamped lengths, each output asked for alone; and
+// every refusal of the asr_rnnt_align* entry points.  No HIP call is made; no
+// GPU is needed or used.
+#include "asr_amd.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <random>
+#include <vector>
+
+static int failures = 0;
+#define EXPECT(expr, want)                                                              \
+    do {                                                                                \
+        const long got_ = (long)(expr);                                                 \
+        if (got_ != (long)(want)) {                                                     \
+            std::printf("FAIL %s:%d %s: got %ld, want %ld\n", __FILE__, __LINE__, #expr, got_, (long)(want)); \
+            failures++;                                                                 \
+        }                                                                               \
+    } while (0)
+#define EXPECT_TRUE(expr) EXPECT(!!(expr), 1)
+
+struct Model {
+    asr_rnnt_desc d;
+    std::vector<float> emb, wih[2], whh[2], bih[2], bhh[2], wenc, benc, wpred, bpred, wout, bout;
+    asr_rnnt_weights ptrs() const {
+        asr_rnnt_weights w{};
+        w.emb = emb.data();
+        for (int l = 0; l < d.L && l < 2; l++) {
+            w.w_ih[l] = wih[l].data();
+            w.w_hh[l] = whh[l].data();
+            w.b_ih[l] = bih[l].data();
+            w.b_hh[l] = bhh[l].data();
+        }
+        w.w_enc = wenc.data(); w.b_enc = benc.data();
+        w.w_pred = wpred.data(); w.b_pred = bpred.data();
+        w.w_out = wout.data(); w.b_out = bout.data();
+        return w;
+    }
+};
+
+static std::mt19937 rng(2828);
+static void fill(std::vector<float>& v, size_t n, float bound) {
+    std::uniform_real_distribution<float> u(-bound, bound);
+    v.resize(n);
+    for (float& x : v) x = u(rng);
+}
+
+static Model make_model(int V, int blank, int E, int D, int Hp, int L, int J, int act) {
+    Model m;
+    m.d = asr_rnnt_desc{V, blank, E, D, Hp, L, J, act, 1};
+    const float k = 1.0f / std::sqrt((float)Hp);
+    fill(m.emb, (size_t)V * D, 1.0f);
+    for (int l = 0; l < L && l < 2; l++) {
+        fill(m.wih[l], (size_t)(l ? Hp : D) * 4 * Hp, k);
+        fill(m.whh[l], (size_t)Hp * 4 * Hp, k);
+        fill(m.bih[l], 4 * (size_t)Hp, k);
+        fill(m.bhh[l], 4 * (size_t)Hp, k);
+    }
+    fill(m.wenc, (size_t)E * J, std::sqrt(3.0f / E));
+    fill(m.benc, J, 0.1f);
+    fill(m.wpred, (size_t)Hp * J, 4.0f * std::sqrt(3.0f / Hp));
+    fill(m.bpred, J, 0.1f);
+    fill(m.wout, (size_t)J * V, 4.0f * std::sqrt(3.0f / J));
+    fill(m.bout, V, 0.1f);
+    m.bout[blank] = 1.0f;
+    return m;
+}
+
+// ---- the restatement: dot products column by column, long double sums, k descending
+static double dotcol(const std::vector<double>& x, const float* W, int K, int N, int n) {
+    long double s = 0;
+    for (int k = K - 1; k >= 0; k--) s += (long double)x[k] * (long double)W[(size_t)k * N + n];
+    return (double)s;
+}
+static double sigm(double v) { return 1.0 / (1.0 + std::exp(-v)); }
+static void ref_step(const Model& m, int tok, std::vector<double>& h, std::vector<double>& c) {
+    const int Hp = m.d.Hp;
+    std::vector<double> x(m.emb.begin() + (size_t)tok * m.d.D, m.emb.begin() + (size_t)(tok + 1) * m.d.D);
+    for (int l = 0; l < m.d.L; l++) {
+        std::vector<double> hl(h.begin() + (size_t)l * Hp, h.begin() + (size_t)(l + 1) * Hp), z(4 * Hp);
+        for (int n = 0; n < 4 * Hp; n++)
+            z[n] = (dotcol(x, m.wih[l].data(), (int)x.size(), 4 * Hp, n) + dotcol(hl, m.whh[l].data(), Hp, 4 * Hp, n)) +
+                   ((double)m.bih[l][n] + (double)m.bhh[l][n]);
+        x.resize(Hp);
+        for (int n = 0; n < Hp; n++) {
+            const double cn = sigm(z[Hp + n]) * c[(size_t)l * Hp + n] + sigm(z[n]) * std::tanh(z[2 * Hp + n]);
+            c[(size_t)l * Hp + n] = cn;
+            x[n] = h[(size_t)l * Hp + n] = sigm(z[3 * Hp + n]) * std::tanh(cn);
+        }
+    }
+}
+
+// lp[t][u][v] = log_softmax(joint(f_t, g_u)) of one target against utterance b
+static std::vector<double> ref_grid(const Model& m, const float* enc, int B, int b, int len, const std::vector<int>& y) {
+    const asr_rnnt_desc& d = m.d;
+    const int U1 = (int)y.size() + 1;
+    std::vector<double> h((size_t)d.L * d.Hp, 0.0), c((size_t)d.L * d.Hp, 0.0), g((size_t)U1 * d.J);
+    for (int u = 0; u < U1; u++) {
+        ref_step(m, u ? y[u - 1] : d.blank, h, c);
+        std::vector<double> ht(h.begin() + (size_t)(d.L - 1) * d.Hp, h.end());
+        for (int j = 0; j < d.J; j++) g[(size_t)u * d.J + j] = dotcol(ht, m.wpred.data(), d.Hp, d.J, j) + (double)m.bpred[j];
+    }
+    std::vector<double> lp((size_t)len * U1 * d.V), f(d.J), z(d.J);
+    for (int t = 0; t < len; t++) {
+        std::vector<double> e(enc + ((size_t)t * B + b) * d.E, enc + ((size_t)t * B + b + 1) * d.E);
+        for (int j = 0; j < d.J; j++) f[j] = dotcol(e, m.wenc.data(), d.E, d.J, j) + (double)m.benc[j];
+        for (int u = 0; u < U1; u++) {
+            for (int j = 0; j < d.J; j++) {
+                const double v = f[j] + g[(size_t)u * d.J + j];
+                z[j] = d.act == ASR_RNNT_ACT_TANH ? std::tanh(v) : (v > 0 ? v : 0);
+            }
+            double* row = &lp[((size_t)t * U1 + u) * d.V];
+            double top = -HUGE_VAL, se = 0;
+            for (int v = 0; v < d.V; v++) {
+                row[v] = dotcol(z, m.wout.data(), d.J, d.V, v) + (double)m.bout[v];
+                top = std::max(top, row[v]);
+            }
+            for (int v = 0; v < d.V; v++) se += std::exp(row[v] - top);
+            for (int v = 0; v < d.V; v++) row[v] -= top + std::log(se);
+        }
+    }
+    return lp;
+}
+
+// Every alignment from node (t, u) on, its log-probability so far in acc: appended to all.
+struct Enum {
+    const Model& m;
+    const std::vector<double>& lp;
+    const std::vector<int>& y;
+    int len, topology;
+    std::vector<double> all;
+    double at(int t, int u, int v) const { return lp[((size_t)t * (y.size() + 1) + u) * m.d.V + v]; }
+    void walk(int t, int u, double acc) {
+        const int U = (int)y.size();
+        if (t == len) {
+            if (u == U) all.push_back(acc);
+            return;
+        }
+        walk(t + 1, u, acc + at(t, u, m.d.blank));                                  // the blank arc: the next frame
+        if (u < U) walk(topology ? t + 1 : t, u + 1, acc + at(t, u, y[u]));         // the label arc
+    }
+};
+
+// The log-probability of the alignment that emits label i at frame fr[i].
+static double path_logp(const Model& m, const std::vector<double>& lp, const std::vector<int>& y, int len, int topology,
+                        const int32_t* fr) {
+    const int U = (int)y.size(), U1 = U + 1;
+    double acc = 0;
+    int u = 0;
+    for (int t = 0; t < len; t++) {
+        bool emitted = false;
+        while (u < U && fr[u] == t && !(topology && emitted)) {
+            acc += lp[((size_t)t * U1 + u) * m.d.V + y[u]];
+            u++;
+            emitted = true;
+        }
+        if (!(topology && emitted)) acc += lp[((size_t)t * U1 + u) * m.d.V + m.d.blank];
+    }
+    return u == U ? acc : -HUGE_VAL;
+}
+
+static bool close(double a, double b) {
+    if (std::isinf(a) || std::isinf(b)) return a == b;
+    return std::fabs(a - b) <= 1e-9 * (1.0 + std::fabs(b));
+}
+
+static void random_scorings() {
+    std::uniform_real_distribution<float> u01(-1.f, 1.f);
+    int scored = 0, infeasible = 0;
+    for (int trial = 0; trial < 120; trial++) {
+        const int L = 1 + trial % 2, act = (trial / 2) % 2, V = 2 + (int)(rng() % 5), topology = (trial / 4) % 2;
+        const int T = 1 + (int)(rng() % 5), B = 1 + (int)(rng() % 3), blank = (int)(rng() % V);
+        const int N = 1 + (int)(rng() % 8), mtl = (int)(rng() % 4), ldt = std::max(1, mtl + (int)(rng() % 2));
+        const Model m = make_model(V, blank, 8, 16, 16, L, 16, act);
+        asr_rnnt_weights w = m.ptrs();
+        asr_rnnt_t* h = nullptr;
+        EXPECT(asr_rnnt_create(&m.d, &w, &h), ASR_OK);
+        if (!h) return;
+        std::vector<float> enc((size_t)T * B * m.d.E);
+        for (float& x : enc) x = u01(rng);
+        std::vector<int32_t> lens(B), tgt((size_t)N * ldt, -7), tl(N), utt(N);
+        for (int b = 0; b < B; b++) lens[b] = (int)(rng() % (T + 3)) - 1;   // -1 .. T + 1: clamped
+        for (int n = 0; n < N; n++) {
+            tl[n] = (int)(rng() % (mtl + 3)) - 1;                          // -1 .. mtl + 1: clamped
+            utt[n] = (rng() % 10) ? (int)(rng() % B) : (rng() % 2 ? -1 : B);   // now and then out of range
+            for (int i = 0; i < mtl; i++) {
+                int y = (int)(rng() % (V - 1));
+                y = y < blank ? y : y + 1;                                 // never the blank ...
+                if (rng() % 40 == 0) y = (rng() % 3 == 0) ? blank : (rng() % 2 ? -1 : V);   // ... but now and then a bad label
+                tgt[(size_t)n * ldt + i] = y;
+            }
+        }
+        std::vector<double> score(N), vscore(N), s1(N), v1(N);
+        std::vector<int32_t> frames((size_t)N * ldt, -5), f1((size_t)N * ldt, -5);
+        EXPECT(asr_rnnt_align_host(h, enc.data(), lens.data(), T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl,
+                                   topology, score.data(), vscore.data(), frames.data()), ASR_OK);
+        // each output alone: equal bits
+        EXPECT(asr_rnnt_align_host(h, enc.data(), lens.data(), T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl,
+                                   topology, s1.data(), nullptr, nullptr), ASR_OK);
+        EXPECT(asr_rnnt_align_host(h, enc.data(), lens.data(), T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl,
+                                   topology, nullptr, v1.data(), nullptr), ASR_OK);
+        EXPECT(asr_rnnt_align_host(h, enc.data(), lens.data(), T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl,
+                                   topology, nullptr, nullptr, f1.data()), ASR_OK);
+        for (int n = 0; n < N; n++) {
+            EXPECT_TRUE(s1[n] == score[n] && v1[n] == vscore[n]);
+            for (int i = 0; i < ldt; i++) EXPECT(f1[(size_t)n * ldt + i], frames[(size_t)n * ldt + i]);
+            const int U = std::min(std::max(tl[n], 0), mtl), b = utt[n];
+            const bool utt_ok = b >= 0 && b < B;
+            const int len = utt_ok ? std::min(std::max(lens[b], 0), T) : 0;
+            std::vector<int> y(tgt.begin() + (size_t)n * ldt, tgt.begin() + (size_t)n * ldt + U);
+            bool bad = false;
+            for (int v : y) bad = bad || v < 0 || v >= V || v == blank;
+            const int32_t* fr = &frames[(size_t)n * ldt];
+            for (int i = mtl; i < ldt; i++) EXPECT(fr[i], -5);             // beyond max_target_len: not touched
+            double want_s = -HUGE_VAL, want_v = -HUGE_VAL;
+            std::vector<double> lp;
+            if (!utt_ok || bad || (len == 0 && U > 0) || (topology == 1 && U > len)) {
+                infeasible++;
+            } else if (len == 0) {
+                want_s = want_v = 0.0;
+            } else {
+                lp = ref_grid(m, enc.data(), B, b, len, y);
+                Enum e{m, lp, y, len, topology, {}};
+                e.walk(0, 0, 0.0);
+                EXPECT_TRUE(!e.all.empty());
+                want_v = *std::max_element(e.all.begin(), e.all.end());
+                long double s = 0;
+                for (double x : e.all) s += std::exp((long double)(x - want_v));
+                want_s = want_v + (double)std::log(s);
+                scored++;
+            }
+            EXPECT_TRUE(close(score[n], want_s));
+            EXPECT_TRUE(close(vscore[n], want_v));
+            EXPECT_TRUE(score[n] >= vscore[n] || std::isinf(want_s));
+            const bool feasible = !std::isinf(want_v);
+            for (int i = 0; i < mtl; i++) {
+                if (!feasible || i >= U) {
+                    EXPECT(fr[i], -1);
+                } else {
+                    EXPECT_TRUE(fr[i] >= 0 && fr[i] < len);
+                    if (i) EXPECT_TRUE(topology ? fr[i] > fr[i - 1] : fr[i] >= fr[i - 1]);
+                }
+            }
+            if (feasible && len > 0) EXPECT_TRUE(close(path_logp(m, lp, y, len, topology, fr), want_v));
+        }
+        EXPECT(asr_rnnt_destroy(h), ASR_OK);
+    }
+    std::printf("random scorings: %d targets against the enumeration of every alignment, %d infeasible\n", scored,
+                infeasible);
+    EXPECT_TRUE(scored >= 200 && infeasible > 0);
+}
+
+static void refusals() {
+    const Model m = make_model(5, 0, 8, 16, 16, 1, 16, ASR_RNNT_ACT_RELU);
+    asr_rnnt_weights w = m.ptrs();
+    asr_rnnt_t* h = nullptr;
+    EXPECT(asr_rnnt_create(&m.d, &w, &h), ASR_OK);
+    if (!h) return;
+    const int T = 3, B = 2, N = 2, mtl = 2;
+    const long ldt = 2;
+    std::vector<float> enc((size_t)T * B * m.d.E, 0.25f);
+    std::vector<int32_t> tgt = {1, 2, 3, 4}, tl = {2, 1}, utt = {0, 1}, fr(4);
+    std::vector<double> sc(N), vs(N);
+    double work[2] = {0, 0};
+    auto both = [&](const asr_rnnt_t* hh, const float* e, int t, int b, const int32_t* tg, long ld, const int32_t* l,
+                    const int32_t* ut, int n, int mt, int topo, double* s, double* v, int32_t* f) {
+        const int a = asr_rnnt_align_host(hh, e, nullptr, t, b, tg, ld, l, ut, n, mt, topo, s, v, f);
+        const int d = asr_rnnt_align(hh, e, nullptr, t, b, tg, ld, l, ut, n, mt, topo, s, v, f, work, nullptr);
+        // the device entry refuses the same way before any HIP call; what the host accepts ends at "not uploaded"
+        EXPECT(d, a == ASR_OK ? ASR_ERR_STATE : a);
+        return a;
+    };
+    const float* e = enc.data();
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_OK);
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), nullptr, N, mtl, 1, sc.data(), nullptr, nullptr), ASR_OK);
+    EXPECT(both(nullptr, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, nullptr, T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, B, nullptr, ldt, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, nullptr, utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, 0, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, 0, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), 0, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), N, -1, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, B, tgt.data(), 1, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 0, nullptr, nullptr, nullptr), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 2, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, -1, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);
+    EXPECT(both(h, e, T, 1, tgt.data(), ldt, tl.data(), nullptr, N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_ARG);   // N > B
+    EXPECT(both(h, e, T, B, tgt.data(), 256, tl.data(), utt.data(), N, 256, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_UNSUPPORTED);
+    EXPECT(both(h, e, 1 << 30, 4, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_UNSUPPORTED);   // T * B
+    EXPECT(both(h, e, 1 << 30, 1, tgt.data(), ldt, tl.data(), utt.data(), 1, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_UNSUPPORTED);   // T * U1
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), 1 << 30, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_UNSUPPORTED);   // N * U1
+    EXPECT(both(h, e, 1 << 20, 1, tgt.data(), ldt, tl.data(), utt.data(), 1 << 20, mtl, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_UNSUPPORTED);   // N * tiles
+    EXPECT(both(h, e, T, B, tgt.data(), ldt, tl.data(), utt.data(), 1 << 24, 0, 0, sc.data(), vs.data(), fr.data()), ASR_ERR_UNSUPPORTED);   // N * 16 Hp bytes
+    EXPECT(asr_rnnt_align(h, e, nullptr, T, B, tgt.data(), ldt, tl.data(), utt.data(), N, mtl, 0, sc.data(), vs.data(),
+                          fr.data(), nullptr, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_rnnt_align_workspace_bytes(nullptr, T, B, N, mtl), 0);
+    EXPECT(asr_rnnt_align_workspace_bytes(h, 0, B, N, mtl), 0);
+    EXPECT(asr_rnnt_align_workspace_bytes(h, T, 0, N, mtl), 0);
+    EXPECT(asr_rnnt_align_workspace_bytes(h, T, B, 0, mtl), 0);
+    EXPECT(asr_rnnt_align_workspace_bytes(h, T, B, N, -1), 0);
+    EXPECT(asr_rnnt_align_workspace_bytes(h, T, B, N, 256), 0);
+    EXPECT(asr_rnnt_align_workspace_bytes(h, 1 << 30, 4, N, mtl), 0);
+    // the header's formula: Hp = J = 16, L = 1, U1 = 3
+    EXPECT(asr_rnnt_align_workspace_bytes(h, T, B, N, mtl),
+           4 * (T * B * 16 + 3 * N * (4 * 16 + 16 + 16) + N * 16 + 2 * ((N * T * 3 + 3) / 4 * 4) + (2 * N + 3) / 4 * 4) +
+               64 * N * (T + 3));
+    EXPECT(asr_rnnt_destroy(h), ASR_OK);
+}
+
+int main() {
+    random_scorings();
+    refusals();
+    if (failures) {
+        std::printf("rnnt_align_check: %d failure(s)\n", failures);
+        return 1;
+    }
+    std::printf("rnnt_align_check: ok\n");
+    return 0;
+}
