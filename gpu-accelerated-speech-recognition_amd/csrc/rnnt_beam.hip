@@ -72,21 +72,9 @@ namespace asr {
 constexpr int RB_LDS_SMALL = 8192;   // the beam state, the candidates and the wave partials
 constexpr int RB_MAX_K = 16;
 
-static long rnnt_beam_lds_bytes(int L, int Hp, int J) {
-    return ((long)2 * L * (Hp + 4) + (J + 4)) * RT_ROWS * 4 + RB_LDS_SMALL;
-}
-
 struct BeamArgs {
     const float* f;          // [T*B][J]
-    const float* embw;       // [V][4Hp] = Emb.W_ih of layer 0
-    const float* wih1;       // [Hp][4Hp], layer 1 (L = 2)
-    const float* whh[2];
-    const float* bih[2];
-    const float* bhh[2];
-    const float* wpred;
-    const float* bpred;
-    const float* wout;
-    const float* bout;
+    RtNet net;
     const int32_t* lengths;
     int32_t* tokens;         // [B][nbest][max_out]
     int32_t* timesteps;
@@ -95,7 +83,7 @@ struct BeamArgs {
     int32_t* nhyp;           // [B]
     float* slices;           // per workgroup: c [2][L][16][Hp], g [16][J], logits [16][V]
     int4* nodes;             // [B][T*K + 1]: (parent, token, t, length); node 0 is the empty sequence
-    int T, B, Hp, J, V, L, blank, act, K, lgR, nbest, max_out, max_iters;
+    int T, B, K, lgR, nbest, max_out, max_iters;
 };
 
 // What the LM = true instantiation takes beside BeamArgs (p.score is then am).
@@ -214,8 +202,9 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int g = lane >> 4, c = lane & 15;
-    const int Hp = p.Hp, J = p.J, V = p.V, L = p.L, B = p.B, K = p.K;
-    const int H4 = 4 * Hp, LDH = Hp + 4, LDJ = J + 4;
+    const RtNet& net = p.net;
+    const int Hp = net.Hp, J = net.J, V = net.V, L = net.L, B = p.B, K = p.K;
+    const int LDH = Hp + 4, LDJ = J + 4;
     const int lgR = p.lgR, R = 1 << lgR, U = RT_ROWS >> lgR;
     const int b0 = blockIdx.x * U;
     // LDS: h [2][L][16][LDH], z [16][LDJ], then the small area
@@ -278,7 +267,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
         row_node[tid] = 0;
         row_len[tid] = 0;
         row_prow[tid] = tid;
-        row_tok[tid] = p.blank;    // the start step on Emb[blank], every row
+        row_tok[tid] = net.blank;    // the start step on Emb[blank], every row
         const int b = b0 + tid;
         utt_len[tid] = (tid < U && b < B) ? (p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T) : 0;
         utt_live[tid] = 1;
@@ -336,86 +325,20 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
 #pragma unroll
                     for (int j = 0; j < LM_CTX; j++) ctx[j] = lm_ctx[row * LM_CTX + j];
                     double val = 0.0;
-                    if (v != p.blank) val = lm_value_after(q.lm, ctx, lm_m[row], q.tok[v], false, q.flags);
+                    if (v != net.blank) val = lm_value_after(q.lm, ctx, lm_m[row], q.tok[v], false, q.flags);
                     lmw[(unsigned)(row_slot[row] * V + v)] = val;
                 }
             }
             // Predictor step by parent row; rows without a token copy their parent's h and c.
-            const float* cold_b = cw + (size_t)cur * csz;
-            float* cnew_b = cw + (size_t)(cur ^ 1) * csz;
-            const int prc = row_prow[c];
-            for (int l = 0; l < L; l++) {
-                const float* hold = hb(cur, l);
-                float* hnew = hb(cur ^ 1, l);
-                const float* Whh = p.whh[l];
-                for (int jt = w; jt < (Hp >> 4); jt += RT_WAVES) {
-                    const int n = 16 * jt + c;
-                    const int col[4] = {n, Hp + n, 2 * Hp + n, 3 * Hp + n};
-                    f32x4 acc[4], accx[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) acc[q] = accx[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    rt_mma<4>(hold + prc * LDH + 4 * g, Hp >> 4, Whh, H4, g, col, acc);
-                    if (l > 0)   // x = the layer below's new h, already in the new rows' order
-                        rt_mma<4>(hb(cur ^ 1, l - 1) + c * LDH + 4 * g, Hp >> 4, p.wih1, H4, g, col, accx);
-                    float bias[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) bias[q] = p.bih[l][col[q]] + p.bhh[l][col[q]];
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const int row = 4 * g + j, pr = row_prow[row], tk = row_tok[row];
-                        const bool em = tk >= 0;
-                        float px[4];
-                        if (l == 0) {
-                            const float* e = p.embw + (unsigned)(max(tk, 0) * H4);   // V * 4Hp <= INT_MAX
-#pragma unroll
-                            for (int q = 0; q < 4; q++) px[q] = e[col[q]];
-                        } else {
-#pragma unroll
-                            for (int q = 0; q < 4; q++) px[q] = accx[q][j];
-                        }
-                        const float cold = cold_b[(unsigned)((l * RT_ROWS + pr) * Hp + n)];
-                        const float zi = (px[0] + acc[0][j]) + bias[0], zf = (px[1] + acc[1][j]) + bias[1];
-                        const float zg = (px[2] + acc[2][j]) + bias[2], zo = (px[3] + acc[3][j]) + bias[3];
-                        const float ig = rt_sigmoid(zi), fg = rt_sigmoid(zf), gg = tanhf(zg), og = rt_sigmoid(zo);
-                        const float cn = fg * cold + ig * gg;
-                        const float hn = og * tanhf(cn);
-                        cnew_b[(unsigned)((l * RT_ROWS + row) * Hp + n)] = em ? cn : cold;
-                        hnew[row * LDH + n] = em ? hn : hold[pr * LDH + n];
-                    }
-                }
-                __syncthreads();   // layer l's new h, before layer l + 1 and g read it
-            }
+            rt_lstm_step(net, hb, cur, cw + (size_t)cur * csz, cw + (size_t)(cur ^ 1) * csz,
+                         [&](int row) { return row_prow[row]; }, [&](int row) { return row_tok[row]; }, w, g, c);
             cur ^= 1;
             // g = h_top.W_pred + b_pred of every row
-            const float* ht = hb(cur, L - 1) + c * LDH + 4 * g;
-            const int nt = J >> 4;
-            for (int base = 0; base < nt; base += 4 * RT_WAVES) {
-                const int t0 = base + w;
-                const int nv = t0 < nt ? min(4, (nt - 1 - t0) / RT_WAVES + 1) : 0;
-                if (nv == 4) {
-                    const int col[4] = {16 * t0 + c, 16 * (t0 + RT_WAVES) + c, 16 * (t0 + 2 * RT_WAVES) + c,
-                                        16 * (t0 + 3 * RT_WAVES) + c};
-                    f32x4 acc[4];
+            rt_sweep<1, false>(hb(cur, L - 1) + c * LDH + 4 * g, 0, Hp >> 4, net.wpred, net.bpred, J, w, g, c,
+                               [&](int, int n, f32x4 x) {
 #pragma unroll
-                    for (int q = 0; q < 4; q++) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    rt_mma<4>(ht, Hp >> 4, p.wpred, J, g, col, acc);
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const float b = p.bpred[col[q]];
-#pragma unroll
-                        for (int j = 0; j < 4; j++) gw[(unsigned)((4 * g + j) * J + col[q])] = acc[q][j] + b;
-                    }
-                } else {
-                    for (int q = 0; q < nv; q++) {
-                        const int col[1] = {16 * (t0 + q * RT_WAVES) + c};
-                        f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-                        rt_mma<1>(ht, Hp >> 4, p.wpred, J, g, col, acc);
-                        const float b = p.bpred[col[0]];
-#pragma unroll
-                        for (int j = 0; j < 4; j++) gw[(unsigned)((4 * g + j) * J + col[0])] = acc[0][j] + b;
-                    }
-                }
-            }
+                                   for (int j = 0; j < 4; j++) gw[(unsigned)((4 * g + j) * J + n)] = x[j];
+                               });
         }
         if (!any_live || it >= p.max_iters) break;
 
@@ -429,7 +352,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
                     const int row = 4 * g + j;
                     const int du = min(row >> lgR, B - 1 - b0);
                     const float x = ft[(unsigned)(du * J + n)] + gw[(unsigned)(row * J + n)];
-                    zbuf[row * LDJ + n] = p.act ? tanhf(x) : fmaxf(x, 0.f);
+                    zbuf[row * LDJ + n] = rt_act(x, net.act);
                 }
             }
         }
@@ -439,72 +362,19 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
         RtTop top[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) top[j] = RtTop{-INFINITY, 0.f, 0};   // no argmax here: every index is 0
-        {
-            const float* za = zbuf + c * LDJ + 4 * g;
-            const int nt = (V + 15) >> 4;
-            for (int base = 0; base < nt; base += 4 * RT_WAVES) {
-                const int t0 = base + w;
-                const int nv = t0 < nt ? min(4, (nt - 1 - t0) / RT_WAVES + 1) : 0;
-                if (nv == 4) {
-                    int n[4], col[4];
+        rt_sweep<1, true>(zbuf + c * LDJ + 4 * g, 0, J >> 4, net.wout, net.bout, V, w, g, c, [&](int, int n, f32x4 x) {
 #pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        n[q] = 16 * (t0 + q * RT_WAVES) + c;
-                        col[q] = min(n[q], V - 1);
-                    }
-                    f32x4 acc[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    rt_mma<4>(za, J >> 4, p.wout, V, g, col, acc);
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        if (n[q] >= V) continue;
-                        const float b = p.bout[n[q]];
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            const float x = acc[q][j] + b;
-                            rt_push(top[j], x, 0);
-                            lg[(unsigned)(4 * g + j) * (unsigned)V + (unsigned)n[q]] = x;
-                        }
-                    }
-                } else {
-                    for (int q = 0; q < nv; q++) {
-                        const int n = 16 * (t0 + q * RT_WAVES) + c;
-                        const int col[1] = {min(n, V - 1)};
-                        f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-                        rt_mma<1>(za, J >> 4, p.wout, V, g, col, acc);
-                        if (n >= V) continue;
-                        const float b = p.bout[n];
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            const float x = acc[0][j] + b;
-                            rt_push(top[j], x, 0);
-                            lg[(unsigned)(4 * g + j) * (unsigned)V + (unsigned)n] = x;
-                        }
-                    }
-                }
+            for (int j = 0; j < 4; j++) {
+                rt_push(top[j], x[j], 0);
+                lg[(unsigned)(4 * g + j) * (unsigned)V + (unsigned)n] = x[j];
             }
-        }
-        // the 16 lanes of a row, then the waves in the order 0..7 (rnnt.hip's order)
+        });
+        // the 16 lanes of a row, then the waves in the order 0..7
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1) {
-                RtTop o;
-                o.m = __shfl_xor(top[j].m, d);
-                o.s = __shfl_xor(top[j].s, d);
-                o.i = 0;
-                top[j] = rt_join(top[j], o);
-            }
-            if (c == 0) {
-                red_m[w * RT_ROWS + 4 * g + j] = top[j].m;
-                red_s[w * RT_ROWS + 4 * g + j] = top[j].s;
-            }
-        }
+        for (int j = 0; j < 4; j++) rt_row_partial<false>(top[j], c, w * RT_ROWS + 4 * g + j, red_m, red_s, nullptr);
         __syncthreads();
         if (tid < RT_ROWS) {
-            RtTop a{red_m[tid], red_s[tid], 0};
-            for (int x = 1; x < RT_WAVES; x++) a = rt_join(a, RtTop{red_m[x * RT_ROWS + tid], red_s[x * RT_ROWS + tid], 0});
+            const RtTop a = rt_row_total<false>(tid, RT_ROWS, red_m, red_s, nullptr);
             row_m[tid] = a.m;
             row_ls[tid] = logf(a.s);   // lp[v] = (logit[v] - max) - log(sum-exp): -logf(s) at the maximum, as in rnnt.hip
         }
@@ -527,7 +397,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
                 int bv = RT_NONE;
                 for (int v = lane; v < V; v += 64) {
                     double sc = s + (double)((lr[v] - m) - ls);
-                    if constexpr (LM) sc = __dadd_rn(sc, v == p.blank ? Wr : rb_weight(Wr, q.aln10, wr[v], q.beta));
+                    if constexpr (LM) sc = __dadd_rn(sc, v == net.blank ? Wr : rb_weight(Wr, q.aln10, wr[v], q.beta));
                     if ((r == 0 || rb_before(lsc, lv, sc, v)) && (bv == RT_NONE || rb_before(sc, v, bs, bv))) {
                         bs = sc;
                         bv = v;
@@ -573,7 +443,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
                     kept_v[base + rank] = v;
                     kept_sc[base + rank] = sc;
                     if constexpr (LM) {   // the parts of sc, by step 2's operations
-                        const bool bl = v == p.blank;
+                        const bool bl = v == net.blank;
                         const double val = bl ? 0.0 : lmw[(unsigned)(row_slot[row] * V + v)];
                         kept_ac[base + rank] =
                             row_score[row] + (double)((lg[(unsigned)row * (unsigned)V + (unsigned)v] - row_m[row]) - row_ls[row]);
@@ -595,7 +465,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
                 const int nk = min(K, total);
                 for (int j = 0; j < nk; j++) {
                     const int e = base + j, row = kept_row[e], v = kept_v[e];
-                    const bool bl = v == p.blank;
+                    const bool bl = v == net.blank;
                     ent_score[e] = LM ? kept_ac[e] : kept_sc[e];
                     if constexpr (LM) {
                         ent_W[e] = kept_W[e];
@@ -842,31 +712,19 @@ static int rnnt_beam_launch(const asr_rnnt* h, const asr_rnnt_lm* z, const LmTab
                             int32_t* d_timesteps, int32_t* d_len, double* d_score, double* d_total, double* d_lm_log10,
                             int32_t* d_ntok, int32_t* d_nhyp, void* d_work, asr_stream_t s) {
     const asr_rnnt_desc& d = h->d;
-    const long lds = rnnt_beam_lds_bytes(d.L, d.Hp, d.J);
+    const long lds = rnnt_lds_bytes(d.L, d.Hp, d.J, RB_LDS_SMALL);
     float* f = (float*)d_work;
-    asr::GemmArgs g{};
-    g.A = d_enc; g.B = h->d_wenc; g.b1 = h->d_benc; g.C = f;
-    g.M = T * B; g.N = d.J; g.K = d.E;
-    g.sam = d.E; g.sak = 1; g.sbk = d.J; g.sbn = 1; g.ldc = d.J;
-    if (int rc = asr::gemm_launch(g, asr::EPI_BIAS, asr_stream(s))) return rc;
+    if (int rc = rnnt_enc_launch(h, d_enc, T, B, f, asr_stream(s))) return rc;
     const int lgR = asr::rb_log2_rows(K), U = asr::RT_ROWS >> lgR;
     const size_t tiles = ((size_t)B + U - 1) / U;
     asr::BeamArgs a{};
     a.f = f;
-    a.embw = h->d_embw;
-    a.wih1 = h->d_wih1;
-    for (int l = 0; l < d.L; l++) {
-        a.whh[l] = h->d_whh[l];
-        a.bih[l] = h->d_bih[l];
-        a.bhh[l] = h->d_bhh[l];
-    }
-    a.wpred = h->d_wpred; a.bpred = h->d_bpred; a.wout = h->d_wout; a.bout = h->d_bout;
+    a.net = rnnt_net(h);
     a.lengths = d_lengths;
     a.tokens = d_tokens; a.timesteps = d_timesteps; a.len = d_len; a.score = d_score; a.nhyp = d_nhyp;
     a.slices = f + (size_t)T * B * d.J;
     a.nodes = reinterpret_cast<int4*>(a.slices + tiles * asr::RT_ROWS * ((size_t)2 * d.L * d.Hp + d.J + d.V));
-    a.T = T; a.B = B; a.Hp = d.Hp; a.J = d.J; a.V = d.V; a.L = d.L; a.blank = d.blank; a.act = d.act;
-    a.K = K; a.lgR = lgR; a.nbest = nbest; a.max_out = max_out;
+    a.T = T; a.B = B; a.K = K; a.lgR = lgR; a.nbest = nbest; a.max_out = max_out;
     a.max_iters = T;   // one joint evaluation per hypothesis and frame
     asr::BeamLmArgs q{};
     if (z) {
@@ -907,7 +765,7 @@ int asr_rnnt_beam(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_leng
     if (int rc = asr::rnnt_beam_check(h, d_enc, T, B, K, nbest, max_out, d_tokens, d_timesteps, d_len, d_score, d_nhyp))
         return rc;
     if (!d_work) return ASR_ERR_ARG;
-    if (asr::rnnt_beam_lds_bytes(h->d.L, h->d.Hp, h->d.J) > asr::RT_LDS_MAX) return ASR_ERR_UNSUPPORTED;
+    if (asr::rnnt_lds_bytes(h->d.L, h->d.Hp, h->d.J, asr::RB_LDS_SMALL) > asr::RT_LDS_MAX) return ASR_ERR_UNSUPPORTED;
     if (!h->d_blob) return ASR_ERR_STATE;
     return asr::rnnt_beam_launch(h, nullptr, nullptr, d_enc, d_lengths, T, B, K, nbest, max_out, d_tokens, d_timesteps,
                                  d_len, d_score, nullptr, nullptr, nullptr, d_nhyp, d_work, s);
@@ -970,16 +828,10 @@ static int rnnt_beam_host_run(const asr_rnnt* h, const asr_rnnt_lm* z, const flo
                 m.enc_proj(h_enc + ((size_t)t * B + b) * d.E);
                 cands.clear();
                 for (int i = 0; i < (int)A.size(); i++) {
-                    for (int j = 0; j < d.J; j++) {
-                        const double v = m.f[j] + A[i].g[j];
-                        m.z[j] = d.act == ASR_RNNT_ACT_TANH ? std::tanh(v) : (v > 0.0 ? v : 0.0);
-                    }
-                    asr::RnntHost::matvec(m.z.data(), h->wout.data(), d.J, d.V, logit.data());
+                    m.logits(A[i].g.data(), logit.data());
                     double best = -HUGE_VAL;
-                    for (int v = 0; v < d.V; v++) {
-                        logit[v] += (double)h->bout[v];
+                    for (int v = 0; v < d.V; v++)
                         if (logit[v] > best) best = logit[v];
-                    }
                     double se = 0.0;
                     for (int v = 0; v < d.V; v++) se += std::exp(logit[v] - best);
                     const double lse = best + std::log(se);
@@ -1153,7 +1005,7 @@ int asr_rnnt_beam_lm(asr_rnnt_lm_t* z, const float* d_enc, const int32_t* d_leng
     if (int rc = asr::rnnt_beam_check(h, d_enc, T, B, K, nbest, max_out, d_tokens, d_timesteps, d_len, d_total, d_nhyp))
         return rc;
     if (!d_work) return ASR_ERR_ARG;
-    if (asr::rnnt_beam_lds_bytes(h->d.L, h->d.Hp, h->d.J) > asr::RT_LDS_MAX) return ASR_ERR_UNSUPPORTED;
+    if (asr::rnnt_lds_bytes(h->d.L, h->d.Hp, h->d.J, asr::RB_LDS_SMALL) > asr::RT_LDS_MAX) return ASR_ERR_UNSUPPORTED;
     const asr::LmTables *host, *dev;
     if (!h->d_blob || !asr_internal_lm_tables(z->lm, &host, &dev)) return ASR_ERR_STATE;
     if (!z->d_tok) {   // once per handle

@@ -48,10 +48,12 @@ NBEST_CASE = _a("s2-nbest", rc.S2, "relu", rc.L2, 0, 2.0, [(n // 2, 2 + n % 4) f
 # path.
 LONG_CASE = _a("long", (6, 2, 16, 16, 16, 16, 17, 1), "relu", [6, 5], 1, -2.0, [(0, 70), (1, 130), (1, 3)], 0,
                greedy=40, out_scale=8.0)
-# V = 257 (two layers, 320) and V = 1025 (640: the LDS limit, V no multiple of 16, three column sweeps), T <= 12, U <= 6
+# V = 257 (two layers, 320) and V = 1025 (640: the LDS limit, V no multiple of 16, three column sweeps), T <= 12, U <= 6;
+# V = 437 (rnnt_cases.MIXED: 28 column tiles, waves on both paths of the sweep at once)
 UPPER_CASES = [
     AlignCase("l2-320", bc.UPPER_CASES[1].model, ((0, 6), (0, 0), (2, 3), (3, 5), (3, 1), (1, 0)), 0, 0),
     AlignCase("c640", bc.UPPER_CASES[0].model, ((0, 6), (2, 4), (3, 1), (4, 5), (0, 0)), 0, 0),
+    _a("mixed", rc.MIXED, "relu", [6, 0, 4], 0, 2.0, [(0, 4), (0, 0), (2, 3), (2, 1), (0, 6), (1, 0)], 0),
 ]
 # The joint kernel takes three row tiles of 16 nodes up to J = 816, two from J = 832 and one from J = 1264 (what
 # fits in LDS): the smallest J of the other two kernels, at a small V and T; 36 nodes are more than one workgroup of either

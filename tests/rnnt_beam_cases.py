@@ -43,12 +43,13 @@ WIDE_CASES = [
 ]
 # One seed each.  None of the seeds 0..39 of either shape has both the margin and a merge (c640: margin at seeds 0 and
 # 22, merges at 2, 3, 5, 6, ... without it; l2-320: margin at seed 14 only, no merge at any), so these two are held
-# to the margin alone.
+# to the margin alone.  rnnt_cases.MIXED (both paths of the column-tile sweep in one sweep) has both at seed 10.
 UPPER_CASES = [
     _b("c640-k4", (12, 5, 64, 640, 640, 640, 1025, 1), "relu", [12, 0, 7, 12, 9], 0, 6.0, 4),
     _b("l2-320-k8", (8, 4, 16, 320, 320, 320, 257, 2), "tanh", [8, 0, 8, 5], 14, 5.0, 8),
+    _b("mixed-k4", rc.MIXED, "relu", [6, 0, 4], 10, 6.0, 4),
 ]
-UPPER_NEEDS_MERGE = {"c640-k4": False, "l2-320-k8": False}
+UPPER_NEEDS_MERGE = {"c640-k4": False, "l2-320-k8": False, "mixed-k4": True}
 
 
 @functools.lru_cache(maxsize=None)

@@ -46,12 +46,16 @@ SMALL_CASES = [
     _c("s3-b0-m3", S3, False, 3, "tanh", L3, 1, 4.0, 2.0),
     _c("s3-bl-m3", S3, True, 3, "tanh", L3, 2, 4.0, 5.0),
 ]
-# GPU only: two row tiles (the second with one row), the required upper range, two layers at 320
+# GPU only: two row tiles (the second with one row), the required upper range, two layers at 320, and 28 column tiles
+# of J and V (waves 0-3 take four tiles in one product, waves 4-7 three single ones; the last V tile is partial and
+# holds the blank, 436)
+MIXED = (6, 3, 8, 16, 16, 448, 437, 1)
 LARGE_CASES = [
     _c("tiles", (6, 17, 16, 16, 16, 16, 17, 1), False, 3, "relu",
        [6, 0, 3, 6, 5, 6, 2, 6, 6, 1, 6, 4, 6, 6, 0, 6, 6], 0, 4.0, 4.0),
     _c("c640", (12, 5, 64, 640, 640, 640, 1025, 1), True, 3, "relu", [12, 0, 7, 12, 9], 0, 4.0, 6.0),
     _c("l2-320", (8, 4, 16, 320, 320, 320, 257, 2), False, 2, "tanh", [8, 0, 8, 5], 0, 4.0, 5.0),
+    _c("mixed", MIXED, True, 3, "relu", [6, 0, 4], 2, 4.0, 4.0),
 ]
 
 
