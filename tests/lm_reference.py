@@ -162,6 +162,48 @@ def random_arpa(rng, vocab, order, ngrams, bos=True, eos=True, unk=False, low=-4
     return "\n".join(out)
 
 
+def windowed_arpa(rng, vocab, order, seqs, extra, low=-4.0):
+    """ARPA text of a model of the given order over w0.. with <s> and </s> that
+    is hit at every order: its n-grams of order k = 2 .. order are every window
+    of k tokens of <s> seq </s> for each seq of `seqs` (lists of indices into
+    w0..), and beside them extra[k-2] random ones made as random_arpa makes
+    them.  Well formed: the prefix of a window is a window, and a random n-gram
+    extends an n-gram of the order below on the right."""
+    names = ["w%d" % i for i in range(vocab)]
+    names.insert(int(rng.integers(0, len(names) + 1)), "<s>")
+    names.insert(int(rng.integers(0, len(names) + 1)), "</s>")
+    V = len(names)
+    bos_id, eos_id = names.index("<s>"), names.index("</s>")
+    rows = [[bos_id] + [names.index("w%d" % int(t)) for t in s] + [eos_id] for s in seqs]
+    levels = [[(i,) for i in range(V)]]
+    for k in range(2, order + 1):
+        got = {tuple(r[i:i + k]) for r in rows for i in range(len(r) - k + 1)}
+        prev = [g for g in levels[-1] if g[-1] != eos_id]   # nothing follows </s>
+        want = len(got) + extra[k - 2]
+        tries = 0
+        while len(got) < want and prev and tries < 50 * want + 100:
+            tries += 1
+            g = prev[int(rng.integers(0, len(prev)))]
+            w = int(rng.integers(0, V))
+            if w == bos_id:
+                continue
+            got.add(g + (w,))
+        levels.append(sorted(sorted(got), key=lambda g: rng.random()))
+    out = ["", "\\data\\"]
+    for k, lv in enumerate(levels, 1):
+        out.append("ngram %d=%d" % (k, len(lv)))
+    for k, lv in enumerate(levels, 1):
+        out.append("")
+        out.append("\\%d-grams:" % k)
+        for g in lv:
+            line = _fmt(np.float32(rng.uniform(low, 0.0))) + "\t" + " ".join(names[i] for i in g)
+            if k < len(levels) and rng.random() < 0.8:
+                line += "\t" + _fmt(np.float32(rng.uniform(-2.0, 0.5)))
+            out.append(line)
+    out += ["", "\\end\\", ""]
+    return "\n".join(out)
+
+
 def random_hypotheses(rng, model_vocab, lengths, oov_rate=0.0):
     """Token lists of the given lengths over [0, vocab); with oov_rate > 0 some
     ids are -1, vocab or beyond."""

@@ -52,6 +52,43 @@ UPPER_CASES = [
 UPPER_NEEDS_MERGE = {"c640-k4": False, "l2-320-k8": False, "mixed-k4": True}
 
 
+def _o(name, shape, blank, act, lengths, seed, blank_bias, beam):
+    return BeamCase(name, rc.Case(name, shape, blank, 1, act, tuple(lengths), seed, 4.0, blank_bias), beam)
+
+
+# The options the cases above leave alone: the blank in the middle and at V - 1 (MIXED: in the partial last column
+# tile, beside kept labels), K > V and V < 16.  Seeds 0..199 were tried per case with the reference alone and the
+# first that meets check_conditions (the margin, a merge, a best that is not the greedy one) and the case's own
+# condition (check_option) is pinned.  Of the 200, 47 meet the margin for s2-bl-k4 (9 is the first with the rest);
+# s2-bm-k8 has six with the margin and four with everything (73, 90, 111, 156), s3-bl-k8 four (89, 96, 138, 182),
+# mixed-bl-k4 four (46, 62, 121, 196); at V <= 3 more than half meet the margin.  No merge condition was waived.
+V3, V2 = (6, 3, 8, 16, 16, 16, 3, 1), (5, 2, 8, 16, 16, 16, 2, 1)
+OPTION_CASES = [
+    _o("s2-bl-k4", rc.S2, 16, "relu", rc.L2, 9, 2.0, 4),
+    _o("s2-bm-k8", rc.S2, 8, "relu", rc.L2, 73, 2.0, 8),
+    _o("s3-bl-k8", rc.S3, 32, "tanh", rc.L3, 89, 3.0, 8),
+    _o("mixed-bl-k4", rc.MIXED, 436, "relu", [6, 0, 4], 46, 6.0, 4),
+    _o("v3-k4", V3, 0, "relu", [6, 0, 4], 2, 1.0, 4),
+    _o("v3-bl-k16", V3, 2, "relu", [6, 0, 4], 13, 1.0, 16),
+    _o("v2-k4", V2, 1, "relu", [5, 3], 3, 1.0, 4),
+]
+OPTION_NEEDS_MERGE = {c.name: True for c in OPTION_CASES}
+
+
+def check_option(case, ref):
+    """The option case's own condition, asserted on the reference alone, after check_conditions."""
+    V, K = case.model.shape[6], case.beam
+    live = [s for s in ref["frame_sizes"] if s]
+    if case.name == "mixed-bl-k4":      # a kept label in the partial last column tile, beside the blank
+        assert any(432 <= v < V and v != case.model.blank for v in ref["kept_labels"]), sorted(ref["kept_labels"])
+    if case.name == "v3-k4":            # a live row proposes all its V < K candidates: some frame keeps more than V
+        assert V < K and any(kept > V for s in live for kept, _n in s), ref["frame_sizes"]
+    if case.name == "v3-bl-k16":        # the first frame keeps exactly V, a later one ends short of K
+        assert all(s[0] == (V, V) for s in live) and any(n < K for s in live for _k, n in s[1:]), ref["frame_sizes"]
+    if case.name == "v2-k4":            # sequences are 0^n: at most t + 2 after frame t, always short of K
+        assert all(n < K for s in live for _k, n in s) and any(len(s) >= K for s in live), ref["frame_sizes"]
+
+
 @functools.lru_cache(maxsize=None)
 def reference(case):
     """(weights, enc, the reference's search of the case), computed once and not to be changed."""

@@ -49,7 +49,13 @@ class BeamReference(Reference):
         ones: what is left beside exact ties), max_abs_logit, merges, deep_merges
         (constituents whose creating nodes have different parents), short_frames (frames
         that end with fewer than `beam` hypotheses), frames (frames walked per
-        utterance) and greedy (per utterance the K = 1 tokens, when beam > 1)."""
+        utterance) and greedy (per utterance the K = 1 tokens, when beam > 1).
+        For the option cases also: frame_sizes (per utterance, per frame, (candidates
+        kept, hypotheses left after merging)), kept_labels (the non-blank labels
+        of kept candidates), cut_margin [B] (the smallest kept-against-rejected
+        margin alone, inf when nothing was rejected) and tied_neighbours
+        (neighbours of a final list with equal scores that were extended from
+        different parents)."""
         enc = _t(enc)
         T, B = enc.shape[0], enc.shape[1]
         K = int(beam)
@@ -57,7 +63,7 @@ class BeamReference(Reference):
         max_out = T if max_out is None else int(max_out)
         V = self.w["b_out"].shape[0]
         out = {"hyps": [], "lens": [], "margin": [], "margin_nonzero": [], "frames": [], "merges": 0, "deep_merges": 0,
-               "short_frames": 0}
+               "short_frames": 0, "frame_sizes": [], "kept_labels": set(), "cut_margin": [], "tied_neighbours": 0}
         max_abs = 0.0
         for b in range(B):
             h = [torch.zeros(self.Hp, dtype=F64) for _ in range(self.L)]
@@ -66,7 +72,7 @@ class BeamReference(Reference):
             A = [_Hyp((), (), 0.0, h, c, 0, None)]
             nodes = 0
             ln = T if lengths is None else max(0, min(int(lengths[b]), T))
-            margins = []
+            margins, cuts, sizes = [], [], []
             for t in range(ln):
                 f = enc[t, b] @ self.w["w_enc"] + self.w["b_enc"]
                 cands = []
@@ -79,9 +85,12 @@ class BeamReference(Reference):
                 nk = min(K, len(cands))
                 if len(cands) > nk:
                     margins.append(cands[nk - 1][0] - cands[nk][0])
+                    cuts.append(cands[nk - 1][0] - cands[nk][0])
                 ent = []
                 for pos, (s, i, v) in enumerate(cands[:nk]):
                     hyp = A[i]
+                    if v != self.blank:
+                        out["kept_labels"].add(v)
                     if v == self.blank:
                         ent.append(dict(score=s, ys=hyp.ys, ts=hyp.ts, src=hyp, tok=None, pos=pos, node=hyp.node,
                                         pnode=hyp.pnode))
@@ -108,6 +117,7 @@ class BeamReference(Reference):
                 merged.sort(key=lambda x: _key(x["score"], x["pos"]))
                 if len(merged) < K:
                     out["short_frames"] += 1
+                sizes.append((nk, len(merged)))
                 new = []
                 for e in merged:
                     src = e["src"]
@@ -123,6 +133,9 @@ class BeamReference(Reference):
                 A = new
             for x, y in zip(A, A[1:]):
                 margins.append(x.score - y.score)
+                out["tied_neighbours"] += int(x.score == y.score and x.pnode != y.pnode)
+            out["frame_sizes"].append(sizes)
+            out["cut_margin"].append(min(cuts, default=math.inf))
             out["hyps"].append([(list(x.ys[:max_out]), list(x.ts[:max_out]), x.score) for x in A[:nbest]])
             out["lens"].append([len(x.ys) for x in A[:nbest]])
             out["margin"].append(min(margins, default=math.inf))

@@ -16,7 +16,7 @@ from collections import namedtuple
 import numpy as np
 
 import rnnt_cases as rc
-from lm_reference import BOS, EOS, ArpaModel, random_arpa
+from lm_reference import BOS, EOS, ArpaModel, random_arpa, windowed_arpa
 from rnnt_beam_reference import BeamReference
 from rnnt_lm_reference import LmBeamReference
 
@@ -55,10 +55,52 @@ UPPER_CASES = [
 UPPER_NEEDS_MERGE = {"e-c640-k4": True}
 
 
+def _o(name, shape, blank, act, lengths, seed, blank_bias, beam, lm, bos, eos, alpha, beta, oov=()):
+    return LmCase(name, rc.Case(name, shape, blank, 1, act, tuple(lengths), seed, 4.0, blank_bias), beam, lm, bos, eos,
+                  alpha, beta, tuple(oov))
+
+
+TRI436 = (3, (1500, 1500), 436, False, 3, -100.0)      # sparse over MIXED's 436 labels
+BI2 = (2, (4,), 2, False, 5, -100.0)                   # a bigram over the two labels of the V = 3 shape
+# order 8 over 16 tokens: a seventh field makes lm_text build the model from the windows of the case's own unfused
+# K-best (lm_reference.windowed_arpa), with (30,) * 7 random n-grams beside them
+O8 = (8, (30,) * 7, 16, False, 21, -100.0, "windows")
+V3 = (6, 3, 8, 16, 16, 16, 3, 1)
+S12 = (12, 3, 24, 16, 48, 32, 17, 1)
+# The options the cases above leave alone: the blank in the middle and at V - 1, both flags together and neither,
+# beta < 0, alpha = 0, beta = 0, K > V, and an order-8 model whose context is cut to its last seven tokens.  Model
+# seeds 0..199 were tried per case with the reference alone; the first that meets the margin, a merge and the case's
+# own condition (check_option) is pinned.  Of the 200 the margin holds at 78 (f-bl-k4), 26 (f-bm-k8), 88, 101, 38,
+# 101, 121 (f-mixed, 33 with a kept label >= 432), 143 (f-v3) and 100 (f-o8, 58 with its four conditions; at a blank
+# bias of 1.0 instead of 0.0: 117 and 45).  No merge condition was waived.
+OPTION_CASES = [
+    _o("f-bl-k4", rc.S2, 16, "relu", rc.L2, 3, 2.0, 4, TRI16, True, False, 0.5, 0.5),
+    _o("f-bm-k8", rc.S2, 8, "relu", rc.L2, 5, 2.0, 8, TRI16, True, True, 0.5, 0.5),
+    _o("f-s3-bl", rc.S3, 32, "tanh", rc.L3, 4, 3.0, 4, FOUR32U, False, False, 0.4, 0.3, (5, 9)),
+    _o("f-neg", rc.S2, 0, "relu", rc.L2, 4, 2.0, 4, TRI16, True, False, 0.5, -0.7),
+    _o("f-a0", rc.S2, 0, "relu", rc.L2, 13, 2.0, 4, TRI16, True, False, 0.0, 0.6),
+    _o("f-b0", rc.S2, 16, "relu", rc.L2, 0, 2.0, 4, TRI16, False, True, 0.5, 0.0),
+    _o("f-mixed", rc.MIXED, 436, "relu", [6, 0, 4], 62, 6.0, 4, TRI436, True, False, 0.3, 0.5),
+    _o("f-v3", V3, 2, "relu", [6, 0, 4], 0, 1.0, 16, BI2, True, True, 0.5, 0.5),
+    _o("f-o8", S12, 0, "relu", [12, 0, 10], 29, 0.0, 4, O8, True, True, 0.5, 0.5),
+]
+OPTION_NEEDS_MERGE = {c.name: True for c in OPTION_CASES}
+
+
 @functools.lru_cache(maxsize=None)
 def lm_text(case):
-    order, ngrams, vocab, unk, seed, _oov = case.lm
+    order, ngrams, vocab, unk, seed, _oov = case.lm[:6]
+    if len(case.lm) > 6:     # the windows of the case's own unfused K-best, as LM tokens (the indices of w0..)
+        w, enc = rc.make_model(case.model)
+        plain = BeamReference(w, case.model.blank, case.model.act, 1).search(enc, case.model.lengths, beam=case.beam)
+        seqs = [[_w_index(case, y) for y in ys] for u in plain["hyps"] for ys, _ts, _s in u]
+        return windowed_arpa(np.random.default_rng(seed), vocab, order, seqs, list(ngrams))
     return random_arpa(np.random.default_rng(seed), vocab, order, list(ngrams), bos=True, eos=True, unk=unk)
+
+
+def _w_index(case, v):
+    """Label v is the model's token w<this>: the non-blank labels in label order."""
+    return v - (1 if v > case.model.blank else 0)
 
 
 @functools.lru_cache(maxsize=None)
@@ -72,10 +114,11 @@ def flags_of(case):
 
 @functools.lru_cache(maxsize=None)
 def tok_of_label(case):
-    """Label v > 0 is the model's token w(v-1); the blank (0) and the labels in case.oov map to -1."""
+    """The blank and the labels in case.oov map to -1, the other labels to the model's tokens w0, w1, ... in label
+    order (an OOV label keeps its place in the count): with the blank at 0, label v > 0 is w(v-1)."""
     m = lm_model(case)
     V = case.model.shape[6]
-    return tuple(-1 if v == 0 or v in case.oov else m.ids["w%d" % (v - 1)] for v in range(V))
+    return tuple(-1 if v == case.model.blank or v in case.oov else m.ids["w%d" % _w_index(case, v)] for v in range(V))
 
 
 @functools.lru_cache(maxsize=None)
@@ -131,6 +174,33 @@ def check_conditions(case, ref, need_merge=True):
         assert ref["backoffs"].get(1, 0) >= 1 and ref["backoffs"].get(2, 0) >= 1, (case.name, ref["backoffs"])
     if case.oov:
         assert ref["oov"] >= 1, case.name
+
+
+def check_option(case):
+    """The option case's own condition, asserted on the reference alone, after check_conditions."""
+    _w, _enc, ref, plain = reference(case)
+    V, K, name = case.model.shape[6], case.beam, case.name
+    if name == "f-bl-k4":      # lookups that back off by one and by two orders
+        assert ref["backoffs"].get(1, 0) >= 1 and ref["backoffs"].get(2, 0) >= 1, ref["backoffs"]
+    if name == "f-bm-k8":      # the </s> term reorders a final list, and within its first two
+        assert any(r[:2] != [0, 1] for r in ref["pre_eos_rank"] if len(r) >= 2), ref["pre_eos_rank"]
+    if name == "f-neg":        # the fused best is not the unfused best
+        assert any(f and f[0][0] != u[0][0] for f, u in zip(ref["hyps"], plain["hyps"]))
+    if name == "f-a0":         # alpha = 0: any other model over the same tokens gives the same search
+        other = reference(case._replace(lm=BI16))[2]
+        assert [[(h[0], h[1], h[2], h[5]) for h in u] for u in other["hyps"]] == \
+            [[(h[0], h[1], h[2], h[5]) for h in u] for u in ref["hyps"]]
+        assert any(h[4] != o[4] for u, v in zip(ref["hyps"], other["hyps"]) for h, o in zip(u, v))   # not the same LM
+    if name == "f-mixed":      # a kept label in the partial last column tile, beside the blank
+        assert any(432 <= v < V and v != case.model.blank for v in ref["kept_labels"]), sorted(ref["kept_labels"])
+    if name == "f-v3":
+        assert V < K and ref["short_frames"] >= 1
+    if name == "f-o8":
+        assert lm_model(case).order == 8
+        assert ref["max_len"] >= 9                  # a context was cut to its last 7 tokens
+        assert ref["max_order"] == 8                # a lookup answered at order 8, without backing off
+        assert ref["full_ctx_backoffs"] >= 1        # a lookup that backed off from a 7-token context
+        assert ref["eos_full_ctx"] >= 1             # a final hypothesis's </s> term looked up with a full context
 
 
 def check_suite(cases):

@@ -63,7 +63,16 @@ class LmBeamReference(BeamReference):
         the dict also has backoffs ({orders backed off: lookups} over the tokens
         hypotheses took), oov (OOV tokens scored), and per hypothesis weights (W)
         and eos_terms (aln10 * v_eos, 0.0 without ASR_LM_EOS): total is
-        (am + W) + eos_term where the flag is set, am + W where not."""
+        (am + W) + eos_term where the flag is set, am + W where not.
+        For the option cases also: frame_sizes and kept_labels as in
+        BeamReference.search; over the tokens hypotheses took: max_order (the
+        highest order a lookup was answered at), max_ctx (the longest context in
+        reach of a lookup) and full_ctx_backoffs (lookups with order - 1 tokens
+        in reach that backed off); over the final lists: eos_full_ctx (</s>
+        terms looked up with order - 1 tokens in reach), max_len (the longest
+        final hypothesis) and pre_eos_rank (per utterance and final hypothesis,
+        its rank before the </s> term, so [0, 1, ..] where the term reorders
+        nothing)."""
         enc = _t(enc)
         T, B = enc.shape[0], enc.shape[1]
         K = int(beam)
@@ -71,7 +80,9 @@ class LmBeamReference(BeamReference):
         max_out = T if max_out is None else int(max_out)
         V = self.w["b_out"].shape[0]
         out = {"hyps": [], "lens": [], "margin": [], "frames": [], "merges": 0, "deep_merges": 0, "short_frames": 0,
-               "backoffs": {}, "oov": 0, "weights": [], "eos_terms": []}
+               "backoffs": {}, "oov": 0, "weights": [], "eos_terms": [], "frame_sizes": [], "kept_labels": set(),
+               "max_order": 0, "max_ctx": 0, "full_ctx_backoffs": 0, "eos_full_ctx": 0, "max_len": 0,
+               "pre_eos_rank": []}
         max_abs = 0.0
 
         def hyp(ys, ts, score, h, c, node, pnode, W, L):
@@ -86,7 +97,7 @@ class LmBeamReference(BeamReference):
             A = [hyp((), (), 0.0, h, c, 0, None, 0.0, 0.0)]
             nodes = 0
             ln = T if lengths is None else max(0, min(int(lengths[b]), T))
-            margins = []
+            margins, sizes = [], []
             for t in range(ln):
                 f = enc[t, b] @ self.w["w_enc"] + self.w["b_enc"]
                 cands = []
@@ -115,8 +126,11 @@ class LmBeamReference(BeamReference):
                     else:
                         val, q, reach, oov = self._value(x.ys + (v,))
                         out["oov"] += int(oov)
+                        out["kept_labels"].add(v)
+                        out["max_order"], out["max_ctx"] = max(out["max_order"], q), max(out["max_ctx"], reach)
                         if q >= 1 and reach + 1 - q > 0:
                             out["backoffs"][reach + 1 - q] = out["backoffs"].get(reach + 1 - q, 0) + 1
+                            out["full_ctx_backoffs"] += int(reach == self.lm.order - 1)
                         ent.append(dict(fused=fu, score=ac, W=w, L=x.L + val, ys=x.ys + (v,), ts=x.ts + (t,), src=x,
                                         tok=v, pos=pos, node=None, pnode=x.node))
                 merged = []
@@ -141,6 +155,7 @@ class LmBeamReference(BeamReference):
                 merged.sort(key=lambda e: _key(e["fused"], e["pos"]))
                 if len(merged) < K:
                     out["short_frames"] += 1
+                sizes.append((nk, len(merged)))
                 new = []
                 for e in merged:
                     src = e["src"]
@@ -158,7 +173,8 @@ class LmBeamReference(BeamReference):
             for rank, x in enumerate(A):
                 total, L, term = x.score + x.W, x.L, 0.0
                 if self.flags & EOS:
-                    ve = self._value(x.ys, eos=True)[0]
+                    ve, _q, reach, _oov = self._value(x.ys, eos=True)
+                    out["eos_full_ctx"] += int(reach == self.lm.order - 1)
                     term = self.aln10 * ve
                     total = total + term
                     L = L + ve
@@ -173,5 +189,8 @@ class LmBeamReference(BeamReference):
             out["eos_terms"].append([e[4] for e in final[:nbest]])
             out["margin"].append(min(margins, default=math.inf))
             out["frames"].append(ln)
+            out["frame_sizes"].append(sizes)
+            out["pre_eos_rank"].append([e[1] for e in final])
+            out["max_len"] = max([out["max_len"]] + [len(e[2].ys) for e in final])
         out["max_abs_logit"] = max_abs
         return out

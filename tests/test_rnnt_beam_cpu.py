@@ -20,6 +20,40 @@ def test_the_suite_has_a_deep_merge_and_a_short_frame():
     bc.check_suite(bc.SMALL_CASES)
 
 
+@pytest.mark.parametrize("case", bc.OPTION_CASES, ids=lambda c: c.name)
+def test_option_twin_matches_reference(case):
+    """The blank in the middle and at V - 1, K > V and V < 16: the twin against the reference."""
+    w, enc, ref = bc.reference(case)
+    bc.check_conditions(case, ref, need_merge=bc.OPTION_NEEDS_MERGE[case.name])
+    bc.check_option(case, ref)
+    dec = bc.make_decoder(asr, case, w)
+    res, margin = dec.beam_search_host(enc, rc.lengths_of(case.model), beam=case.beam, margins=True)
+    assert [len(u) for u in res] == [len(u) for u in ref["hyps"]]
+    for b, (got, want) in enumerate(zip(res, ref["hyps"])):
+        for (tok, ts, score), (rtok, rts, rscore) in zip(got, want):
+            assert tok == rtok and ts == rts, b
+            assert close(score, rscore), (b, score, rscore)
+        assert (np.isinf(margin[b]) and np.isinf(ref["margin"][b])) or \
+            abs(margin[b] - ref["margin"][b]) <= 1e-9 * (1 + abs(ref["margin"][b])) + 1e-9 * ref["max_abs_logit"]
+    for b, n in enumerate(case.model.lengths):
+        if n == 0:
+            assert res[b] == [([], [], 0.0)]
+    dec.close()
+
+
+def test_lengths_are_clamped_and_optional():
+    """lengths = NULL is every length T; a length above T is T and a negative one 0."""
+    case = bc.OPTION_CASES[0]   # s2-bl-k4
+    w, enc, _ref = bc.reference(case)
+    dec = bc.make_decoder(asr, case, w)
+    T, K = enc.shape[0], case.beam
+    assert dec.beam_search_host(enc, None, beam=K) == dec.beam_search_host(enc, [T] * enc.shape[1], beam=K)
+    wild = dec.beam_search_host(enc, [T + 5, -3, 4, T, 7], beam=K)
+    assert wild == dec.beam_search_host(enc, [T, 0, 4, T, 7], beam=K)
+    assert wild[1] == [([], [], 0.0)] and max(len(h[0]) for h in wild[0]) > 0
+    dec.close()
+
+
 @pytest.mark.parametrize("case", bc.SMALL_CASES, ids=lambda c: c.name)
 def test_twin_matches_reference(case):
     w, enc, ref = bc.reference(case)

@@ -2,7 +2,10 @@
 tests/rnnt_beam_reference.py and the host twin: tokens, timesteps, lengths and
 hypothesis counts exactly, scores within test_rnnt_gpu.py's bound for totals;
 K = 1 against the greedy kernel, batch independence, exact token ties, the
-upper range of shapes and zero-length utterances.
+upper range of shapes and zero-length utterances; the option table (a moved
+blank, K > V, V < 16) and what only the device can show: nothing written
+beyond the counts, clamped and absent lengths, a workspace that holds another
+search, and hypotheses that tie in every candidate.
 
 Measured on an MI355X (max over the case of |gpu - ref| / ((1 + |ref|) * frames
 walked)) are in DESIGN.md §25; the bound is 2e-5."""
@@ -70,7 +73,38 @@ def test_upper_range(case):
     dec.close()
 
 
-@pytest.mark.parametrize("case", [bc.SMALL_CASES[0], bc.SMALL_CASES[6]], ids=lambda c: c.name)
+@pytest.mark.parametrize("case", bc.OPTION_CASES, ids=lambda c: c.name)
+def test_option_kernel_matches_reference(case):
+    """The blank in the middle and at V - 1, K > V and V < 16: the kernel against the reference and the twin."""
+    w, enc, ref = bc.reference(case)
+    bc.check_conditions(case, ref, need_merge=bc.OPTION_NEEDS_MERGE[case.name])
+    bc.check_option(case, ref)
+    dec = bc.make_decoder(asr, case, w)
+    ln = rc.lengths_of(case.model)
+    res = dec.beam_search(enc, ln, beam=case.beam)
+    host = dec.beam_search_host(enc, ln, beam=case.beam)
+    assert [len(u) for u in host] == [len(u) for u in res]
+    compare(case.name, res, ref, host)
+    assert [[len(h[0]) for h in u] for u in res] == ref["lens"]
+    for b, n in enumerate(case.model.lengths):
+        if n == 0:
+            assert res[b] == [([], [], 0.0)]
+    dec.close()
+
+
+def _greedy_case(name, seed=None):
+    """rnnt_cases' large model of that name on a max_symbols = 1 handle, searched at K = 1.  "tiles" is compared
+    with the reference too and takes a seed of its own: at max_symbols = 1 rnnt_cases' seed 0 walks within 0.52 of
+    the near-tie bound; seed 5 is the first of 0..199 with the margin, 20 tokens or more and an emission in the
+    last utterance, which is alone in the second workgroup."""
+    c = next(c for c in rc.LARGE_CASES if c.name == name)
+    return bc.BeamCase(name, c._replace(max_symbols=1, seed=c.seed if seed is None else seed), 1)
+
+
+# beside S2 and S3: the 28-tile shape with the blank at 436 (waves on both paths of the column-tile sweep), two
+# layers at 320, and 17 utterances (16 rows a workgroup at K = 1, the second workgroup with one utterance)
+@pytest.mark.parametrize("case", [bc.SMALL_CASES[0], bc.SMALL_CASES[6], _greedy_case("mixed"), _greedy_case("l2-320"),
+                                  _greedy_case("tiles", 5)], ids=lambda c: c.name)
 def test_beam_one_is_the_greedy_kernel(case):
     """K = 1 against asr_rnnt_greedy on a max_symbols = 1 handle of the same weights."""
     w, enc = rc.make_model(case.model)
@@ -84,7 +118,104 @@ def test_beam_one_is_the_greedy_kernel(case):
         assert beam[b][0][0] == greedy[b][0] and beam[b][0][1] == greedy[b][1]
         total = greedy[b][3]
         assert abs(beam[b][0][2] - total) <= TOL * (1 + abs(total)) * max(int(ln[b]), 1)
+    if case.name == "tiles":     # and the reference's K = 1 search of all 17
+        ref = BeamReference(w, case.model.blank, case.model.act, 1).search(enc, case.model.lengths, beam=1)
+        assert min(ref["margin"]) >= bc.margin_bound(ref) and len(ref["hyps"][16][0][0]) >= 1
+        compare("tiles-k1", beam, ref)
     dec.close()
+
+
+def raw(dec, e, lens, K, nbest=None, max_out=None, fill=0, work=None, arrays=True):
+    """Every output array of one asr_rnnt_beam call, downloaded as it is: tokens and timesteps [B][nbest][max_out],
+    lengths and scores [B][nbest], counts [B].  The arrays hold the byte `fill` before the call; lens None passes no
+    lengths, arrays False no token and timestep arrays (max_out = 0); work None is a fresh zeroed workspace."""
+    e = np.ascontiguousarray(e, np.float32)
+    T, nb = e.shape[0], e.shape[1]
+    nbest = K if nbest is None else nbest
+    max_out = T if max_out is None else max_out
+    mo = max(max_out, 1)
+    dec.upload()
+    d_enc = asr._upload(e, 0)
+    d_ln = None if lens is None else asr._upload(np.ascontiguousarray(lens, np.int32), 0)
+    shapes = [((nb, nbest, mo), np.int32), ((nb, nbest, mo), np.int32), ((nb, nbest), np.int32),
+              ((nb, nbest), np.float64), ((nb,), np.int32)]
+    outs = [asr.DeviceBytes(max(int(np.prod(sh)) * np.dtype(dt).itemsize, 16)) for sh, dt in shapes]
+    for o in outs:
+        asr.check(asr.lib().asr_memset(o.ptr, fill, o.nbytes, None), "asr_memset")
+    if work is None:
+        work = asr.DeviceBytes(dec.beam_workspace_bytes(T, nb, K))
+        asr.check(asr.lib().asr_memset(work.ptr, 0, work.nbytes, None), "asr_memset")
+    dec.beam_search_device(d_enc.ptr, T, nb, K, nbest, max_out, outs[0].ptr if arrays else 0,
+                           outs[1].ptr if arrays else 0, outs[2].ptr, outs[3].ptr, outs[4].ptr, work.ptr,
+                           d_ln.ptr if d_ln else 0)
+    asr.check(asr.lib().asr_stream_sync(None), "asr_stream_sync")
+    return [asr._download(o, sh, dt, 0) for o, (sh, dt) in zip(outs, shapes)]
+
+
+def untouched(a, written, fill=0x5A):
+    """Every entry of `a` outside the mask `written` still holds the fill byte."""
+    return bool((a.view(np.uint8).reshape(a.shape + (a.itemsize,))[~written] == fill).all())
+
+
+def test_nothing_is_written_beyond_the_counts():
+    """nbest = 2 < K and max_out = 2 below a length: what lies below the counts and the cut lengths is the full
+    call's (and the reference's), the lengths are the uncut ones, and every other byte is as it was."""
+    case = bc.OPTION_CASES[0]   # s2-bl-k4
+    w, enc, ref = bc.reference(case)
+    assert max(n for u in ref["lens"] for n in u) > 2
+    dec = bc.make_decoder(asr, case, w)
+    ln = rc.lengths_of(case.model)
+    K, B = case.beam, enc.shape[1]
+    full = raw(dec, enc, ln, K)
+    for max_out in (2, 0):
+        tok, ts, hl, sc, nh = raw(dec, enc, ln, K, nbest=2, max_out=max_out, fill=0x5A, arrays=max_out > 0)
+        assert nh.tolist() == [min(len(u), 2) for u in ref["hyps"]] == np.minimum(full[4], 2).tolist()
+        wrote3, wrote2 = np.zeros(tok.shape, bool), np.zeros(hl.shape, bool)
+        for b in range(B):
+            for j in range(nh[b]):
+                n = min(int(hl[b, j]), max_out)
+                wrote2[b, j] = True
+                wrote3[b, j, :n] = True
+                assert hl[b, j] == full[2][b, j] == ref["lens"][b][j] and sc[b, j] == full[3][b, j]
+                assert tok[b, j, :n].tolist() == full[0][b, j, :n].tolist() == ref["hyps"][b][j][0][:n]
+                assert ts[b, j, :n].tolist() == full[1][b, j, :n].tolist() == ref["hyps"][b][j][1][:n]
+        assert not wrote2[1, 1:].any() and nh[1] == 1      # the zero-length utterance: one empty hypothesis
+        assert untouched(tok, wrote3) and untouched(ts, wrote3) and untouched(hl, wrote2) and untouched(sc, wrote2)
+    dec.close()
+
+
+def test_lengths_are_clamped_and_optional():
+    """No lengths is every length T; a length above T is T and a negative one 0: equal bytes."""
+    case = bc.OPTION_CASES[0]   # s2-bl-k4
+    w, enc, _ref = bc.reference(case)
+    dec = bc.make_decoder(asr, case, w)
+    T, B, K = enc.shape[0], enc.shape[1], case.beam
+    for a, b in zip(raw(dec, enc, None, K), raw(dec, enc, [T] * B, K)):
+        assert np.array_equal(a, b)
+    wild, tame = raw(dec, enc, [T + 5, -3, 4, T, 7], K), raw(dec, enc, [T, 0, 4, T, 7], K)
+    for a, b in zip(wild, tame):
+        assert np.array_equal(a, b)
+    assert wild[4][1] == 1 and wild[2][1, 0] == 0 and wild[2][0].max() > 0
+    dec.close()
+
+
+def test_a_workspace_that_holds_another_search():
+    """s2-bm-k8, then v3-bl-k16, then s2-bl-k4 in one workspace: each finds the node table, the c slices and the
+    logits of another model's search at other T, B, K and V, and gives the bytes of its own run in a zeroed one."""
+    runs = []
+    for case in (bc.OPTION_CASES[1], bc.OPTION_CASES[5], bc.OPTION_CASES[0]):
+        w, enc, _ref = bc.reference(case)
+        runs.append((case, enc, bc.make_decoder(asr, case, w)))
+    work = asr.DeviceBytes(max(d.beam_workspace_bytes(e.shape[0], e.shape[1], c.beam) for c, e, d in runs))
+    asr.check(asr.lib().asr_memset(work.ptr, 0, work.nbytes, None), "asr_memset")
+    for case, enc, dec in runs:
+        ln = rc.lengths_of(case.model)
+        shared, fresh = raw(dec, enc, ln, case.beam, work=work), raw(dec, enc, ln, case.beam)
+        assert int(fresh[4].sum()) > enc.shape[1]
+        for a, b in zip(shared, fresh):
+            assert np.array_equal(a, b), case.name
+    for _c, _e, dec in runs:
+        dec.close()
 
 
 def test_batch_independent():
@@ -170,6 +301,51 @@ def test_exact_token_tie(blank, src, dup, seed):
         assert [(h[0], h[1]) for h in got1[b]] == [(h[0], h[1]) for h in ref1["hyps"][b]]
         assert [(h[0], h[1]) for h in got2[b]] == [(h[0], h[1]) for h in ref2["hyps"][b]]
         assert got2[b][0][2] == got2[b][1][2]       # equal bits: the same row and equal logits
+    dec.close()
+
+
+DUP_LIFT = 1.5    # the pair's bias: the blank's (1.5), not the tie case's 4.0, so the beam is not one chain
+
+
+def dup_references(blank, src, dup, seed):
+    """The tie case with label src duplicated whole into dup (the W_out column,
+    b_out and the Emb row), and its conditions, asserted on the reference
+    alone.  After the first emission [.., src] and [.., dup] have equal states
+    and equal scores, so the candidates (i, v) and (i', v) tie for every v: the
+    order of two hypotheses is decided by i, and a cut at K falls inside a tie."""
+    case, w, enc = _tie_case(blank, src, dup, seed)
+    w["b_out"][dup] = w["b_out"][src] = DUP_LIFT
+    w["emb"][dup] = w["emb"][src]
+    refs = {K: BeamReference(w, blank, case.act, 1).search(enc, case.lengths, beam=K) for K in (3, 4)}
+    for K, ref in refs.items():
+        bound = 1e-3 * (1 + ref["max_abs_logit"])
+        assert min(ref["cut_margin"]) == 0.0, K                 # a kept candidate ties with a rejected one
+        assert min(ref["margin_nonzero"]) >= bound, (K, min(ref["margin_nonzero"]), bound)
+    assert refs[4]["tied_neighbours"] >= 1      # equal scores, different parents: ordered by i alone
+    assert any(len({tuple(h[0][:1]) for h in u}) > 1 for u in refs[4]["hyps"])     # not one chain
+    return case, w, enc, refs
+
+
+# seeds 0..199 tried per placement; at this lift 63, 80 and 75 of them meet the conditions, and these are the first
+# with four or more tied neighbours at K = 4
+@pytest.mark.parametrize("blank,src,dup,seed", [(8, 2, 14, 8), (0, 5, 16, 11), (16, 0, 9, 3)])
+def test_a_duplicated_label_ties_hypotheses(blank, src, dup, seed):
+    """K = 4 and K = 3 (an odd cut splits a tied pair): the reference's tokens and timesteps in the reference's
+    order, which only "then i, then v ascending" gives, and equal bits where the reference's scores are equal."""
+    case, w, enc, refs = dup_references(blank, src, dup, seed)
+    dec = rc.make_decoder(asr, case, w)
+    ln = rc.lengths_of(case)
+    for K, ref in refs.items():
+        got = dec.beam_search(enc, ln, beam=K)
+        ties = 0
+        for b in range(enc.shape[1]):
+            assert [(h[0], h[1]) for h in got[b]] == [(h[0], h[1]) for h in ref["hyps"][b]], (K, b)
+            for (g0, r0), (g1, r1) in zip(zip(got[b], ref["hyps"][b]), zip(got[b][1:], ref["hyps"][b][1:])):
+                if r0[2] == r1[2]:
+                    ties += 1
+                    assert g0[2] == g1[2], (K, b)     # equal bits: equal states and equal logits
+                assert abs(g0[2] - r0[2]) <= TOL * (1 + abs(r0[2])) * ref["frames"][b]
+        assert ties >= 1, K
     dec.close()
 
 

@@ -45,6 +45,24 @@ def test_twin_matches_reference(case):
     dec.close()
 
 
+@pytest.mark.parametrize("case", lc.OPTION_CASES, ids=lambda c: c.name)
+def test_option_twin_matches_reference(case):
+    """The moved blank, both flags and neither, beta < 0, a zero weight, K > V and the order-8 model: the twin
+    against the reference."""
+    w, enc, ref, _plain = lc.reference(case)
+    lc.check_conditions(case, ref, need_merge=lc.OPTION_NEEDS_MERGE[case.name])
+    lc.check_option(case)
+    dec = lc.make_decoder(asr, case, w)
+    lm = lc.make_lm(asr, case)
+    res, margin = dec.beam_search_host(enc, rc.lengths_of(case.model), margins=True, lm=lm, **lc.search_kwargs(case))
+    lc.compare(case.name, res, ref, rel, REL)
+    for b in range(len(res)):
+        assert (np.isinf(margin[b]) and np.isinf(ref["margin"][b])) or \
+            abs(margin[b] - ref["margin"][b]) <= 1e-9 * (1 + abs(ref["margin"][b])) + 1e-9 * ref["max_abs_logit"]
+    assert [[len(h[0]) for h in u] for u in res] == ref["lens"]
+    dec.close()
+
+
 def _raw_host(dec, fuse, enc, ln, K, nbest, max_out):
     """Every output array of asr_rnnt_beam_lm_host (fuse) or asr_rnnt_beam_host (None)."""
     enc = np.ascontiguousarray(enc, np.float32)

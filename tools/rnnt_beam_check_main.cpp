@@ -107,7 +107,7 @@ static void random_searches() {
     std::uniform_real_distribution<float> u(-1.f, 1.f);
     int compared = 0, skipped = 0, merges_seen = 0;
     for (int trial = 0; trial < 120; trial++) {
-        const int L = 1 + trial % 2, act = (trial / 2) % 2, V = 3 + (int)(rng() % 6), K = 1 + (int)(rng() % 6);
+        const int L = 1 + trial % 2, act = (trial / 2) % 2, V = 2 + (int)(rng() % 7), K = 1 + (int)(rng() % 16);   // K > V too
         const int T = 1 + (int)(rng() % 6), B = 1 + (int)(rng() % 3), blank = (int)(rng() % V);
         const Model m = make_model(V, blank, 8, 16, 16, L, 16, act);
         asr_rnnt_weights w = m.ptrs();
