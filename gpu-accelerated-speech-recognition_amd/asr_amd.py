@@ -30,6 +30,14 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           LayerNorm and TransformerEncoderLayer,
                                           time-major (asr_attention_fwd,
                                           asr_layernorm_fwd); no reference member
+    ConformerLayer.from_torch(ffn1=..., attn=..., conv=..., ffn2=..., final_norm=...).forward
+    ConformerConv.from_torch(norm, pw1, dw, bn, pw2).forward / Conformer(layers).forward
+                                          a Conformer encoder block, time-major:
+                                          SiLU feed-forwards (EPI_BIAS_SILU),
+                                          attention, and the convolution module
+                                          with GLU -> depthwise -> BatchNorm ->
+                                          SiLU in one launch (asr_glu_dwconv_fwd);
+                                          no reference member
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
                                           waveform -> log-mel / MFCC features
                                           (asr_fbank_*); no reference member
@@ -90,7 +98,7 @@ ASR_ERR_UNSUPPORTED = 5
 ASR_ERR_STATE = 6
 ASR_ERR_INTERNAL = 7
 
-EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_LOGSOFTMAX = 0, 1, 2, 3
+EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_LOGSOFTMAX, EPI_BIAS_SILU = 0, 1, 2, 3, 4
 SEMANTICS_CPU, SEMANTICS_CUDA = 0, 1   # asr_ctc_set_semantics
 ASR_CTC_WAVES_LIST = -1                # asr_ctc_set_waves: the one-wave list kernel
 ASR_CTC_TS_MAX_T = 65536               # longest decode with timesteps on (16-bit frames)
@@ -105,7 +113,7 @@ EXPORTS = [
     "asr_rnn_cell_fwd", "asr_rnn_fwd", "asr_rnn_recur_fwd", "asr_rnn_persist_stats", "asr_rnn_emit_fwd", "asr_rnn_bidir_workspace_bytes", "asr_rnn_bidir_fwd",
     "asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd",
     "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
-    "asr_conv1d_out_frames", "asr_conv1d_fwd",
+    "asr_conv1d_out_frames", "asr_conv1d_fwd", "asr_glu_dwconv_fwd",
     "asr_attention_fwd", "asr_layernorm_fwd", "asr_mask_rows",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
@@ -228,6 +236,7 @@ def lib() -> ctypes.CDLL:
         "asr_gru_recur_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _i, _vp],
         "asr_conv1d_out_frames": [_vp, _i],
         "asr_conv1d_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i, _vp],
+        "asr_glu_dwconv_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _vp],
         "asr_attention_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp,
                               ctypes.c_long, _i, _i, _i, _i, _i, _vp],
         "asr_layernorm_fwd": [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _f, _vp, _vp, ctypes.c_long,
@@ -1199,6 +1208,327 @@ class TransformerEncoderLayer:
             self.norm2.forward(f2, T, B, lengths, res=h, out=out, stream=st)
         self._keep = lengths
         return out
+
+
+# ------------------------------------------------------------------ Conformer
+GLU_ACT_NONE, GLU_ACT_RELU, GLU_ACT_SILU = 0, 1, 2
+GLU_ACTS = {None: GLU_ACT_NONE, "none": GLU_ACT_NONE, "relu": GLU_ACT_RELU, "silu": GLU_ACT_SILU,
+            "swish": GLU_ACT_SILU}
+GLU_DWCONV_MAX_KERNEL = 80   # ASR_GLU_DWCONV_MAX_KERNEL
+
+
+class GluDwconvDesc(ctypes.Structure):
+    """asr_glu_dwconv_desc (include/asr_amd.h)."""
+    _fields_ = [("channels", _i), ("kernel", _i), ("pad_left", _i), ("pad_right", _i), ("act", _i)]
+
+
+def glu_dwconv_desc(channels: int, kernel: int, pad_left: Optional[int] = None, pad_right: Optional[int] = None,
+                    act="silu") -> GluDwconvDesc:
+    """A GluDwconvDesc from keywords; the pads default to "same"
+    ((k-1)//2, k-1 - (k-1)//2); act: None, "relu", "silu" or an ASR_GLU_ACT_* value."""
+    if pad_left is None:
+        pad_left = (kernel - 1) // 2 if pad_right is None else kernel - 1 - pad_right
+    if pad_right is None:
+        pad_right = kernel - 1 - pad_left
+    a = GLU_ACTS[act.lower()] if isinstance(act, str) else GLU_ACT_NONE if act is None else int(act)
+    return GluDwconvDesc(channels, kernel, pad_left, pad_right, a)
+
+
+def glu_dwconv_fwd(u, w: DeviceMatrix, b: Optional[DeviceMatrix], out, T: int, B: int, desc: GluDwconvDesc,
+                   lengths: Optional[DeviceBytes] = None, col: int = 0, stream: int = 0):
+    """GLU -> depthwise convolution over time -> bias -> activation in one
+    launch (asr_glu_dwconv_fwd): u [T*B, >= 2C] time-major, values in columns
+    [0, C) and gates in [C, 2C) (the row stride is u.cols), w [k, C], b [C] or
+    None, the result into columns [col, col + C) of out [T*B, >= C] (the row
+    stride is out.cols); lengths from device_lengths()."""
+    C = desc.channels
+    assert u.rows == T * B and u.cols >= 2 * C, (u.rows, u.cols)
+    assert out.rows == T * B, (out.rows, T, B)
+    assert 0 <= col and col + C <= out.cols, (out.cols, col)
+    assert w.rows * w.cols == desc.kernel * C, (w.rows, w.cols)
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_glu_dwconv_fwd(ctypes.byref(desc), u.ptr, u.cols, opt(lengths), w.ptr, opt(b),
+                                   out.ptr + 4 * col, out.cols, T, B, stream), "asr_glu_dwconv_fwd")
+    return out
+
+
+def _torch_linear(lin):
+    """(W [in][out], b [out]) float32 of a torch.nn.Linear."""
+    host = lambda p: p.detach().cpu().float().numpy()   # noqa: E731
+    b = host(lin.bias) if lin.bias is not None else np.zeros(lin.out_features, np.float32)
+    return np.ascontiguousarray(host(lin.weight).T), b
+
+
+class ConformerConv:
+    """The convolution module of a Conformer block for inference, time-major:
+    LayerNorm -> pointwise conv to 2E -> GLU -> depthwise conv -> BatchNorm ->
+    SiLU -> pointwise conv to E, as asr_layernorm_fwd, asr_linear_fwd,
+    asr_glu_dwconv_fwd (the eval-mode BatchNorm folded into its weights and
+    bias) and asr_linear_fwd.  No arithmetic here.  w1 [E, 2E], wd [k, E] and
+    w2 [E, E] in this library's [in][out] / [tap][channel] layouts; padding
+    'same', 'causal' or (left, right) with left + right = k - 1."""
+
+    def __init__(self, norm: LayerNorm, w1, b1, wd, bd, w2, b2, padding="same", act="silu"):
+        E = norm.N
+        wd = np.asarray(wd, np.float32)
+        k = wd.shape[0]
+        assert wd.shape == (k, E), wd.shape
+        pl, pr = Conv1d.parse_padding(padding, k)
+        self.E, self.norm = E, norm
+        self.desc = glu_dwconv_desc(E, k, pl, pr, act)
+        up = lambda a, shape: DeviceMatrix.from_numpy(np.asarray(a, np.float32).reshape(shape))   # noqa: E731
+        self.w1, self.b1 = up(w1, (E, 2 * E)), up(b1, (2 * E, 1))
+        self.wd, self.bd = up(wd, (k, E)), up(bd, (E, 1))
+        self.w2, self.b2 = up(w2, (E, E)), up(b2, (E, 1))
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_torch(norm, pw1, dw, bn, pw2, padding=None):
+        """A dict of float32 arrays and the padding from the five torch
+        modules of a convolution module: w1 [E, 2E] / b1 and w2 [E, E] / b2
+        (the 1x1 Conv1d weights transposed to [in][out]), wd [k, E] / bd (the
+        depthwise weights with the eval-mode BatchNorm1d folded in float64, as
+        Conv1d.pack_torch does, rounded to fp32 once), 'padding': (left,
+        right) from dw.padding, or from the padding argument ((left, right) or
+        'causal') when dw.padding is 0 (models that pad by hand), and the
+        LayerNorm's 'norm_weight' / 'norm_bias' / 'norm_eps'.  No device call.
+        Raises ValueError for a GroupNorm / LayerNorm in place of the BatchNorm,
+        a BatchNorm in training mode or without running statistics,
+        dw.groups != channels, a stride or dilation other than 1, a pointwise
+        kernel size other than 1, or pads that do not sum to k - 1."""
+        E = dw.in_channels
+        if not hasattr(bn, "running_mean") or not hasattr(bn, "running_var"):
+            raise ValueError(f"ConformerConv.pack_torch: {type(bn).__name__} in place of the BatchNorm1d is not "
+                             "supported")
+        if dw.groups != E or dw.out_channels != E:
+            raise ValueError("ConformerConv.pack_torch: the depthwise convolution needs groups == channels")
+        if dw.stride[0] != 1 or dw.dilation[0] != 1:
+            raise ValueError("ConformerConv.pack_torch: the depthwise convolution needs stride 1 and dilation 1")
+        for name, pw, cout in (("first", pw1, 2 * E), ("second", pw2, E)):
+            if pw.kernel_size[0] != 1 or pw.stride[0] != 1 or pw.groups != 1 or pw.padding not in ((0,), "valid"):
+                raise ValueError(f"ConformerConv.pack_torch: the {name} pointwise convolution needs kernel size 1, "
+                                 "stride 1, no padding and groups 1")
+            if pw.in_channels != E or pw.out_channels != cout:
+                raise ValueError(f"ConformerConv.pack_torch: the {name} pointwise convolution is "
+                                 f"{pw.in_channels} -> {pw.out_channels}, not {E} -> {cout}")
+        if tuple(norm.normalized_shape) != (E,):
+            raise ValueError(f"ConformerConv.pack_torch: LayerNorm over {tuple(norm.normalized_shape)}, not ({E},)")
+        wd, bd, kw = Conv1d.pack_torch(dw, bn)          # refuses a BatchNorm in training mode; folds in float64
+        k = kw["kernel"]
+        pads = kw["padding"]
+        if padding is not None:
+            if pads != (0, 0):
+                raise ValueError("ConformerConv.pack_torch: a padding argument needs dw.padding == 0")
+            pads = Conv1d.parse_padding(padding, k)
+        if pads[0] < 0 or pads[1] < 0 or pads[0] + pads[1] != k - 1:
+            raise ValueError(f"ConformerConv.pack_torch: pads {pads} do not sum to kernel - 1 = {k - 1}")
+        host = lambda p: p.detach().cpu().float().numpy()   # noqa: E731
+        pwb = lambda pw: (host(pw.bias) if pw.bias is not None   # noqa: E731
+                          else np.zeros(pw.out_channels, np.float32))
+        return dict(w1=np.ascontiguousarray(host(pw1.weight)[:, :, 0].T), b1=pwb(pw1), wd=wd.reshape(k, E), bd=bd,
+                    w2=np.ascontiguousarray(host(pw2.weight)[:, :, 0].T), b2=pwb(pw2), padding=pads,
+                    norm_weight=None if getattr(norm, "weight", None) is None else host(norm.weight),
+                    norm_bias=None if getattr(norm, "bias", None) is None else host(norm.bias),
+                    norm_eps=float(norm.eps))
+
+    @classmethod
+    def _from_packed(cls, p) -> "ConformerConv":
+        norm = LayerNorm(p["w2"].shape[0], p["norm_eps"], p["norm_weight"], p["norm_bias"])
+        return cls(norm, p["w1"], p["b1"], p["wd"], p["bd"], p["w2"], p["b2"], padding=p["padding"])
+
+    @classmethod
+    def from_torch(cls, norm, pw1, dw, bn, pw2, padding=None) -> "ConformerConv":
+        return cls._from_packed(cls.pack_torch(norm, pw1, dw, bn, pw2, padding))
+
+    def forward(self, x, T: int, B: int, lengths=None, out=None, zero_padding: bool = True, stream: int = 0):
+        """The module (without its residual) of time-major x [T*B, E]; lengths
+        None, a sequence of B counts or a DeviceBytes of int32 [B]: frames past
+        them are zero padding for the convolution whatever x holds.  Returns
+        out [T*B, E] (a buffer of this module, reused by its next call, unless
+        given); rows past the lengths are zeros unless zero_padding is False,
+        in which case they hold the last bias."""
+        E, M, st = self.E, T * B, stream or 0
+        lengths = _device_lengths_or_none(lengths)
+        sc = self._scratch
+        n, u, c = sc.get("n", M, E), sc.get("u", M, 2 * E), sc.get("c", M, E)
+        out = sc.get("out", M, E) if out is None else out
+        self.norm.forward(x, T, B, lengths, out=n, stream=st)
+        linear_fwd(n, self.w1, self.b1, u, EPI_BIAS, st)
+        glu_dwconv_fwd(u, self.wd, self.bd, c, T, B, self.desc, lengths=lengths, stream=st)
+        linear_fwd(c, self.w2, self.b2, out, EPI_BIAS, st)
+        if zero_padding and lengths is not None:
+            mask_rows(out, T, B, E, lengths, st)
+        self._keep = lengths
+        return out
+
+
+class ConformerLayer:
+    """One Conformer encoder block for inference, time-major:
+        x + 1/2 FFN1(x) -> attention and convolution module, each with its
+        residual (the convolution first if convolution_first) -> + 1/2 FFN2 ->
+        LayerNorm,
+    each FFN LayerNorm -> Linear -> SiLU -> Linear.  The feed-forwards are
+    asr_linear_fwd with EPI_BIAS_SILU and EPI_BIAS, the 1/2 folded into the second
+    linear's weights and bias when packing (exact: a power of two); attention
+    is MultiheadAttention (with its chunk / left / right window), the
+    convolution module ConformerConv; the residuals are asr_matadd, the last one
+    the fused residual of the final asr_layernorm_fwd.  No arithmetic here;
+    dropout is ignored.  ffn1 / ffn2: (LayerNorm, w1 [E, F], b1 [F], w2 [F, E],
+    b2 [E]) with w2 and b2 already halved (pack_ffn)."""
+
+    def __init__(self, ffn1, attn_norm: LayerNorm, attn: MultiheadAttention, conv: ConformerConv, ffn2,
+                 final_norm: LayerNorm, convolution_first: bool = False):
+        E = attn.E
+        assert conv.E == E and attn_norm.N == E and final_norm.N == E, (E, conv.E, attn_norm.N, final_norm.N)
+        self.E, self.convolution_first = E, bool(convolution_first)
+        self.attn_norm, self.attn, self.conv, self.final_norm = attn_norm, attn, conv, final_norm
+        self.ffn = []
+        for ln, w1, b1, w2, b2 in (ffn1, ffn2):
+            w1, w2 = np.asarray(w1, np.float32), np.asarray(w2, np.float32)
+            F = w1.shape[1]
+            assert ln.N == E and w1.shape == (E, F) and w2.shape == (F, E), (ln.N, w1.shape, w2.shape)
+            self.ffn.append((ln, F, DeviceMatrix.from_numpy(w1),
+                             DeviceMatrix.from_numpy(np.asarray(b1, np.float32).reshape(F, 1)),
+                             DeviceMatrix.from_numpy(w2),
+                             DeviceMatrix.from_numpy(np.asarray(b2, np.float32).reshape(E, 1))))
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_ffn(ln, lin1, lin2):
+        """(w1 [E, F], b1 [F], w2 / 2 [F, E], b2 / 2 [E]) float32 of a
+        feed-forward module LayerNorm -> lin1 -> SiLU -> lin2 whose output the
+        block halves: the 1/2 goes into lin2 (a multiplication by a power of
+        two commutes with every fp32 rounding).  No device call."""
+        w1, b1 = _torch_linear(lin1)
+        w2, b2 = _torch_linear(lin2)
+        if lin2.in_features != lin1.out_features or lin1.in_features != lin2.out_features:
+            raise ValueError("ConformerLayer.pack_ffn: the two linears do not chain E -> F -> E")
+        return w1, b1, np.float32(0.5) * w2, np.float32(0.5) * b2
+
+    @staticmethod
+    def pack_torch(ffn1, attn, conv, ffn2, final_norm, conv_padding=None):
+        """Every packed float32 array of a block, from its torch parts (the
+        arguments of from_torch): a flat dict 'ffn1.w1', ..., 'attn.w_in', ...,
+        'conv.wd', ..., and the LayerNorms' '<part>.norm_weight' / '.norm_bias'
+        / '.norm_eps'.  No device call."""
+        host = lambda p: None if p is None else p.detach().cpu().float().numpy()   # noqa: E731
+        out = {}
+
+        def norm(prefix, ln):
+            if len(tuple(ln.normalized_shape)) != 1:
+                raise ValueError(f"ConformerLayer.pack_torch: {prefix} LayerNorm over {tuple(ln.normalized_shape)}")
+            out[prefix + ".norm_weight"] = host(getattr(ln, "weight", None))
+            out[prefix + ".norm_bias"] = host(getattr(ln, "bias", None))
+            out[prefix + ".norm_eps"] = float(ln.eps)
+
+        for name, (ln, lin1, lin2) in (("ffn1", ffn1), ("ffn2", ffn2)):
+            norm(name, ln)
+            for key, a in zip(("w1", "b1", "w2", "b2"), ConformerLayer.pack_ffn(ln, lin1, lin2)):
+                out[f"{name}.{key}"] = a
+        norm("attn", attn[0])
+        for key, a in zip(("w_in", "b_in", "w_out", "b_out"), MultiheadAttention.pack_torch(attn[1])):
+            out["attn." + key] = a
+        out["attn.heads"] = int(attn[1].num_heads)
+        for key, a in ConformerConv.pack_torch(*conv, padding=conv_padding).items():
+            out["conv." + key] = a
+        norm("final", final_norm)
+        return out
+
+    @classmethod
+    def from_torch(cls, ffn1, attn, conv, ffn2, final_norm, convolution_first: bool = False, chunk: int = 1,
+                   left: int = -1, right: int = -1, conv_padding=None) -> "ConformerLayer":
+        """From explicit torch parts: ffn1 / ffn2 = (LayerNorm, Linear, Linear),
+        attn = (LayerNorm, MultiheadAttention), conv = (LayerNorm, pointwise
+        Conv1d, depthwise Conv1d, BatchNorm1d, pointwise Conv1d), final_norm a
+        LayerNorm; chunk / left / right the attention window; conv_padding as
+        ConformerConv.pack_torch's padding."""
+        p = cls.pack_torch(ffn1, attn, conv, ffn2, final_norm, conv_padding)
+        E = p["attn.w_out"].shape[0]
+        ln = lambda k: LayerNorm(E, p[k + ".norm_eps"], p[k + ".norm_weight"], p[k + ".norm_bias"])   # noqa: E731
+        ffn = lambda k: (ln(k), p[k + ".w1"], p[k + ".b1"], p[k + ".w2"], p[k + ".b2"])   # noqa: E731
+        mha = MultiheadAttention(E, p["attn.heads"], p["attn.w_in"], p["attn.b_in"], p["attn.w_out"],
+                                 p["attn.b_out"], chunk, left, right)
+        conv_m = ConformerConv._from_packed({k[5:]: v for k, v in p.items() if k.startswith("conv.")})
+        return cls(ffn("ffn1"), ln("attn"), mha, conv_m, ffn("ffn2"), ln("final"), convolution_first)
+
+    @staticmethod
+    def torchaudio_parts(layer) -> dict:
+        """The parts of from_torch read off a module laid out like
+        torchaudio.models.conformer.ConformerLayer (see from_torchaudio)."""
+        f1, f2, cm = layer.ffn1.sequential, layer.ffn2.sequential, layer.conv_module
+        return dict(ffn1=(f1[0], f1[1], f1[4]), attn=(layer.self_attn_layer_norm, layer.self_attn),
+                    conv=(cm.layer_norm, cm.sequential[0], cm.sequential[2], cm.sequential[3], cm.sequential[5]),
+                    ffn2=(f2[0], f2[1], f2[4]), final_norm=layer.final_layer_norm,
+                    convolution_first=bool(layer.convolution_first))
+
+    @classmethod
+    def from_torchaudio(cls, layer, chunk: int = 1, left: int = -1, right: int = -1,
+                        conv_padding=None) -> "ConformerLayer":
+        """A thin adapter over from_torch for a module with the attribute
+        layout of torchaudio's ConformerLayer: ffn1.sequential[0, 1, 4]
+        (LayerNorm, Linear, Linear), self_attn_layer_norm, self_attn,
+        conv_module.layer_norm, conv_module.sequential[0, 2, 3, 5] (pointwise,
+        depthwise, BatchNorm1d, pointwise), ffn2, final_layer_norm,
+        convolution_first.  That layout is written from memory: this adapter
+        was never run against torchaudio itself, only against a stand-in
+        module with those attribute names (tests/conformer_reference.py).  A
+        layer built with use_group_norm=True is refused by
+        ConformerConv.pack_torch."""
+        return cls.from_torch(**cls.torchaudio_parts(layer), chunk=chunk, left=left, right=right,
+                              conv_padding=conv_padding)
+
+    def _ffn(self, i: int, x, T: int, B: int, lengths, st: int):
+        """FFN_i(x) / 2 into a scratch buffer."""
+        ln, F, w1, b1, w2, b2 = self.ffn[i]
+        M, sc = T * B, self._scratch
+        n, ff, t = sc.get("n", M, self.E), sc.get("ff", M, F), sc.get("t", M, self.E)
+        ln.forward(x, T, B, lengths, out=n, stream=st)
+        linear_fwd(n, w1, b1, ff, EPI_BIAS_SILU, st)
+        linear_fwd(ff, w2, b2, t, EPI_BIAS, st)
+        return t
+
+    def forward(self, x, T: int, B: int, lengths=None, stream: int = 0) -> DeviceMatrix:
+        """x time-major [T*B, E]; lengths None, a sequence of B counts or a
+        DeviceBytes of int32 [B] (e.g. Conv1d.forward's out_lengths).  Returns a
+        new DeviceMatrix [T*B, E] with zero rows past the lengths; rows of x
+        past them may hold anything."""
+        E, M, st = self.E, T * B, stream or 0
+        lengths = _device_lengths_or_none(lengths)
+        sc = self._scratch
+        h, h2, n = sc.get("h", M, E), sc.get("h2", M, E), sc.get("n", M, E)
+        add = lambda a, b, z: check(lib().asr_matadd(a.ptr, b.ptr, z.ptr, M, E, 1.0, st), "asr_matadd")   # noqa: E731
+        out = DeviceMatrix(M, E)
+        add(x, self._ffn(0, x, T, B, lengths, st), h)
+        for module in ("conv", "attn") if self.convolution_first else ("attn", "conv"):
+            if module == "attn":
+                self.attn_norm.forward(h, T, B, lengths, out=n, stream=st)
+                r = self.attn.forward(n, T, B, lengths, zero_padding=False, stream=st)
+            else:
+                r = self.conv.forward(h, T, B, lengths, zero_padding=False, stream=st)
+            add(h, r, h2)
+            h, h2 = h2, h
+        t = self._ffn(1, h, T, B, lengths, st)
+        self.final_norm.forward(t, T, B, lengths, res=h, out=out, stream=st)
+        self._keep = lengths
+        return out
+
+
+class Conformer:
+    """A stack of ConformerLayers run in turn with the same lengths."""
+
+    def __init__(self, layers: Sequence[ConformerLayer]):
+        self.layers = list(layers)
+        assert self.layers and all(l.E == self.layers[0].E for l in self.layers)
+        self.E = self.layers[0].E
+
+    def forward(self, x, T: int, B: int, lengths=None, stream: int = 0) -> DeviceMatrix:
+        """x time-major [T*B, E]; returns the last layer's new DeviceMatrix
+        [T*B, E] with zero rows past the lengths."""
+        lengths = _device_lengths_or_none(lengths)
+        for layer in self.layers:
+            x = layer.forward(x, T, B, lengths, stream=stream)
+        self._keep = lengths
+        return x
 
 
 # ----------------------------------------------------------------- front end

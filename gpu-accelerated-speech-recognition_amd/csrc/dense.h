@@ -10,8 +10,14 @@ enum GemmEpilogue {
     EPI_BIAS_RELU = 2,   // C = max(A.B + b1, 0)
     EPI_LOGSOFTMAX = 3,  // C = log_softmax(A.B + b1) per row (fused for N <= 64)
     EPI_DUAL_TANH = 4,   // C = tanh((A.B + A2.B2) + (b2 + b1))
-    EPI_ADD_TANH = 5     // C = tanh((D + A.B) + (b2 + b1)); C may alias D
+    EPI_ADD_TANH = 5,    // C = tanh((D + A.B) + (b2 + b1)); C may alias D
+    EPI_BIAS_SILU = 6    // C = silu(A.B + b1)
 };
+
+// SiLU / Swish of a pre-activation, v / (1 + exp(-v)): one expression for every
+// GEMM epilogue and for glu_conv.hip.  v -> -inf: exp overflows to +inf and the
+// quotient is -0; v -> +inf: the quotient is v.
+__device__ __forceinline__ float silu_f32(float v) { return v / (1.f + __expf(-v)); }
 
 struct GemmArgs {
     const float* A;   // A(m,k) = A[m*sam + k*sak]

@@ -181,6 +181,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x4 (&a
                 y = tanhf((y + acc2[nt][j]) + (g.b2[col] + g.b1[col]));
             } else if (EPI == EPI_ADD_TANH) {    // D holds x.W_ih for this step
                 y = tanhf((g.D[(long)row * g.ldc + col] + y) + (g.b2[col] + g.b1[col]));
+            } else if (EPI == EPI_BIAS_SILU) {
+                y = silu_f32(y + g.b1[col]);
             }
             g.C[(long)row * g.ldc + col] = y;
         }
@@ -408,7 +410,7 @@ static bool wide_off() {
 // and in any shard of it: utterance sharding over GPUs relies on that).
 template <int EPI>
 static bool try_gemm_wide(const GemmArgs& g, hipStream_t s, int& rc) {
-    if (EPI != EPI_NONE && EPI != EPI_BIAS && EPI != EPI_BIAS_RELU) return false;
+    if (EPI != EPI_NONE && EPI != EPI_BIAS && EPI != EPI_BIAS_RELU && EPI != EPI_BIAS_SILU) return false;
     const bool va = g.sak == 1 && (g.K % 4) == 0 && (g.sam % 4) == 0 && ((uintptr_t)g.A % 16) == 0;
     if (!va || g.sbn != 1 || g.N < 128 || g.K > 256 || (long)g.M < 1024L * 128 || wide_off()) return false;
     rc = launch_gemm_wide_k<128, 256, EPI>(g, s);
@@ -479,6 +481,7 @@ int gemm_launch(const GemmArgs& g, int epi, hipStream_t s) {
         case EPI_LOGSOFTMAX: return launch_gemm_epi<EPI_LOGSOFTMAX>(g, s);
         case EPI_DUAL_TANH: return launch_gemm_epi<EPI_DUAL_TANH>(g, s);
         case EPI_ADD_TANH: return launch_gemm_epi<EPI_ADD_TANH>(g, s);
+        case EPI_BIAS_SILU: return launch_gemm_epi<EPI_BIAS_SILU>(g, s);
         default: return ASR_ERR_ARG;
     }
 }

@@ -250,7 +250,7 @@ __global__ __launch_bounds__(64 * X3_WAVES) void gemm_x3_kernel(GemmArgs g, int 
             }
     }
     float bias[2] = {0.f, 0.f};
-    if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) {
+    if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_SILU) {
 #pragma unroll
         for (int ct = 0; ct < 2; ct++) bias[ct] = ncol[ct] < g.N ? g.b1[ncol[ct]] : 0.f;
     }
@@ -322,8 +322,9 @@ __global__ __launch_bounds__(64 * X3_WAVES) void gemm_x3_kernel(GemmArgs g, int 
                 for (int ct = 0; ct < 2; ct++) {
                     if (ncol[ct] < g.N) {
                         float y = acc[ct][j];
-                        if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) y = y + bias[ct];
+                        if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_SILU) y = y + bias[ct];
                         if (EPI == EPI_BIAS_RELU && y < 0.f) y = 0.f;
+                        if (EPI == EPI_BIAS_SILU) y = silu_f32(y);
                         bstore(cs, (4 * gq * (int)g.ldc + ncol[ct]) * 4, y);
                     }
                 }
@@ -700,14 +701,15 @@ __global__ __launch_bounds__(64 * XK_WAVES) void gemm_x3k_kernel(GemmArgs g, con
         const int n = n0 + 64 * wn + 16 * ct + c15;
         if (n >= g.N) continue;
         float bias = 0.f;
-        if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) bias = g.b1[n];
+        if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_SILU) bias = g.b1[n];
 #pragma unroll
         for (int rt = 0; rt < 2; rt++)
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 float y = acc[rt][ct][j];
-                if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) y = y + bias;
+                if (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_SILU) y = y + bias;
                 if (EPI == EPI_BIAS_RELU && y < 0.f) y = 0.f;
+                if (EPI == EPI_BIAS_SILU) y = silu_f32(y);
                 bstore(cs, ((32 * wm + 16 * rt + 4 * gq + j) * (int)g.ldc + n) * 4, y);
             }
     }
@@ -766,7 +768,7 @@ static bool x3k_applies(const GemmArgs& g) {
 }
 
 bool gemm_x3_applies(const GemmArgs& g, int epi) {
-    if (epi != EPI_NONE && epi != EPI_BIAS && epi != EPI_BIAS_RELU) return false;
+    if (epi != EPI_NONE && epi != EPI_BIAS && epi != EPI_BIAS_RELU && epi != EPI_BIAS_SILU) return false;
     const bool va = g.sak == 1 && (g.K % 4) == 0 && (g.sam % 4) == 0 && ((uintptr_t)g.A % 16) == 0;
     if (!va) return false;
     if (g.K > 256) return x3k_applies(g);
@@ -794,12 +796,14 @@ int gemm_x3_launch(const GemmArgs& g, int epi, int tpw, hipStream_t s) {
         switch (epi) {
             case EPI_NONE: return launch_gemm_x3k<EPI_NONE>(g, s);
             case EPI_BIAS: return launch_gemm_x3k<EPI_BIAS>(g, s);
+            case EPI_BIAS_SILU: return launch_gemm_x3k<EPI_BIAS_SILU>(g, s);
             default: return launch_gemm_x3k<EPI_BIAS_RELU>(g, s);
         }
     }
     switch (epi) {
         case EPI_NONE: return launch_gemm_x3_epi<EPI_NONE>(g, tpw, s);
         case EPI_BIAS: return launch_gemm_x3_epi<EPI_BIAS>(g, tpw, s);
+        case EPI_BIAS_SILU: return launch_gemm_x3_epi<EPI_BIAS_SILU>(g, tpw, s);
         default: return launch_gemm_x3_epi<EPI_BIAS_RELU>(g, tpw, s);
     }
 }

@@ -167,6 +167,7 @@ int asr_linear_fwd(const float* x, const float* W, const float* b, float* y, int
         case ASR_EPI_BIAS: epi = asr::EPI_BIAS; break;
         case ASR_EPI_BIAS_RELU: epi = asr::EPI_BIAS_RELU; break;
         case ASR_EPI_BIAS_LOGSOFTMAX: epi = asr::EPI_LOGSOFTMAX; break;
+        case ASR_EPI_BIAS_SILU: epi = asr::EPI_BIAS_SILU; break;
         default: return ASR_ERR_ARG;
     }
     return asr::gemm_launch(g, epi, asr_stream(s));

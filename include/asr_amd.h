@@ -89,12 +89,18 @@ typedef enum asr_epilogue {
     ASR_EPI_NONE = 0,            /* y = x.W                                         */
     ASR_EPI_BIAS = 1,            /* y = x.W + b                                     */
     ASR_EPI_BIAS_RELU = 2,       /* y = max(x.W + b, 0)  — Linear.cu:3-10 ReLU      */
-    ASR_EPI_BIAS_LOGSOFTMAX = 3  /* y = log_softmax(x.W + b) per row (model.py:49)  */
+    ASR_EPI_BIAS_LOGSOFTMAX = 3, /* y = log_softmax(x.W + b) per row (model.py:49)  */
+    ASR_EPI_BIAS_SILU = 4        /* y = v / (1 + exp(-v)), v = x.W + b (SiLU / Swish) */
 } asr_epilogue;
 
 /* Linear::forward (Linear.cu:42-49): y[M,N] = epi(x[M,K] . W[K,N] + b[N]).
  * ASR_EPI_BIAS_LOGSOFTMAX is fused into the GEMM for N <= 64 and a row pass
- * after it otherwise. */
+ * after it otherwise.  ASR_EPI_BIAS_SILU (the Conformer's feed-forward
+ * activation; no reference member) is applied where the bias is, in every
+ * kernel and both arithmetics a bias GEMM can land on, so the kernel choice
+ * and a row's independence of M are those of ASR_EPI_BIAS; a pre-activation
+ * of -100 gives -0 (exp overflows to +inf), never NaN.  Every epilogue but
+ * ASR_EPI_NONE needs d_b (NULL: ASR_ERR_ARG). */
 int asr_linear_fwd(const float* d_x, const float* d_W, const float* d_b, float* d_y, int M,
                    int K, int N, int epilogue, asr_stream_t s);
 
@@ -370,6 +376,52 @@ int asr_conv1d_fwd(const asr_conv1d_desc* d, const float* d_x, long ldx, const i
                    const float* d_W, const float* d_b, float* d_out, long ldo,
                    int32_t* d_out_lengths, int T, int B, asr_stream_t s);
 
+/* The middle of a Conformer convolution module in one launch: GLU -> depthwise
+ * convolution over time -> bias (an eval-mode BatchNorm folded into w and b) ->
+ * activation.  The two pointwise convolutions around it are asr_linear_fwd; no
+ * reference member.
+ * d_u: row t*B + b holds >= 2C floats, row stride ldu >= 2C: columns [0, C) the
+ * values, [C, 2C) the gates (torch's GLU over the channels of the first
+ * pointwise convolution's output); other columns are not read.  d_w [kernel][C]
+ * row-major, d_b [C] or NULL for zeros.  d_out: row t*B + b receives C floats,
+ * row stride ldo >= C, columns >= C of a row are not touched.
+ *   g(t, b, c)   = u[t, b, c] / (1 + exp(-u[t, b, C + c]))  for 0 <= t < len[b], exactly 0 outside
+ *   out(t, b, c) = act((sum_{j<k} g(t - pl + j, b, c) w[j][c]) + b[c])
+ * Stride 1, dilation 1, pad_left + pad_right = kernel - 1, so T_out = T: "same"
+ * is ((k-1)/2, k-1 - (k-1)/2), causal (k-1, 0).  One fmaf chain per element
+ * from 0, taps ascending, then the bias, then the activation:
+ * ASR_GLU_ACT_NONE, _RELU max(v, 0) or _SILU v / (1 + exp(-v)).  The sigmoid is
+ * evaluated once per input element.  fp32 always.
+ * d_lengths device int32 [B], clamped to [0, T], NULL = all T.  Frames
+ * t >= len[b] of u are never read (the zero is selected, not multiplied: they
+ * may hold NaN) and rows t >= len[b] of out are zeros.  A gate of -100 gives 0,
+ * one of +100 the value: nothing overflows to NaN.
+ * An output row's bits depend only on the values in its receptive field, the
+ * weights, the bias and the descriptor: never on T, B, the row's position,
+ * other utterances, ldu / ldo or pointer alignment.  So a causal module run
+ * over chunks with their k - 1 history frames prepended (and the first k - 1
+ * output rows of each later chunk dropped) gives the whole call's bits.
+ * One launch, asynchronous on s, no allocation, no workspace, no host sync.
+ * Checks, in this order, all before any HIP call — ASR_ERR_ARG: a NULL
+ * descriptor, d_u, d_w or d_out; non-positive T, B, channels or kernel; a
+ * negative pad; ldu < 2C or ldo < C; an unknown act; d_out == d_u.
+ * ASR_ERR_UNSUPPORTED: pad_left + pad_right != kernel - 1; kernel >
+ * ASR_GLU_DWCONV_MAX_KERNEL; T*B > INT_MAX or T > INT_MAX - 4096;
+ * B * ceil(T / 64) * ceil(C / 64) > INT_MAX (one grid dimension).
+ * Not built: stride or dilation other than 1, GroupNorm / LayerNorm in place of
+ * the BatchNorm, a split-bf16 variant. */
+#define ASR_GLU_DWCONV_MAX_KERNEL 80
+enum { ASR_GLU_ACT_NONE = 0, ASR_GLU_ACT_RELU = 1, ASR_GLU_ACT_SILU = 2 };
+typedef struct asr_glu_dwconv_desc {
+    int channels;             /* C: u rows have 2C floats, out rows C */
+    int kernel;               /* k taps, 1 .. ASR_GLU_DWCONV_MAX_KERNEL */
+    int pad_left, pad_right;  /* >= 0, pad_left + pad_right == kernel - 1 */
+    int act;                  /* ASR_GLU_ACT_* */
+} asr_glu_dwconv_desc;
+int asr_glu_dwconv_fwd(const asr_glu_dwconv_desc* d, const float* d_u, long ldu, const int32_t* d_lengths,
+                       const float* d_w, const float* d_b, float* d_out, long ldo, int T, int B,
+                       asr_stream_t s);
+
 /* Scaled dot-product self-attention over time, all heads in one launch —
  * softmax(Q K^T * scale) V per head with per-utterance lengths and an optional
  * chunked window: the hot path of torch.nn.MultiheadAttention in Transformer /
@@ -442,8 +494,8 @@ int asr_attention_fwd(const asr_attn_desc* d, const float* d_q, long ldq, const 
  * be exactly d_x or d_res (in place).  One wave per row; the sums are a fixed
  * tree (a lane's columns l, l + 64, ... ascending, then the butterfly over the
  * lanes, as asr_lm_score's), so a row's bits never depend on T, B or the
- * row's position.  fp32 always.  GELU / Swish / GLU feed-forward activations
- * are not built (asr_linear_fwd fuses ReLU).
+ * row's position.  fp32 always.  GELU is not built (asr_linear_fwd fuses ReLU
+ * and Swish / SiLU; GLU is in asr_glu_dwconv_fwd: DESIGN.md section 30).
  * One launch, asynchronous on s.  Checks, in this order, before any HIP call —
  * ASR_ERR_ARG: NULL d_x or d_out; non-positive T, B or N; a stride < N; eps not
  * finite or < 0.  ASR_ERR_UNSUPPORTED: N > 4096; T*B > INT_MAX. */
