@@ -1003,6 +1003,24 @@ def attention_fwd(q, k, v, out, Tq: int, Tk: int, B: int, desc: AttnDesc, length
     return out
 
 
+def rel_positional_encoding(max_left: int, max_right: int, E: int) -> np.ndarray:
+    """The sinusoidal table of relative positions [max_left + max_right + 1, E]
+    float32 in the order of ESPnet's / WeNet's / NeMo's pos_emb (flip(positive)
+    followed by negative[1:]): row i is distance delta = max_left - i (query
+    frame - key frame), from max_left down to -max_right, so distance 0 is row
+    max_left.  The row of delta holds sin(delta w_k) at column 2k and
+    cos(delta w_k) at column 2k + 1, w_k = 10000^(-2k / E); computed in float64
+    on the host.  E even.  Host only: the relative-position attention that
+    would read it is not built."""
+    if max_left < 0 or max_right < 0 or E <= 0 or E % 2:
+        raise ValueError(f"rel_positional_encoding: max_left {max_left}, max_right {max_right}, E {E}")
+    delta = np.arange(max_left, -max_right - 1, -1, dtype=np.float64)[:, None]
+    w = np.power(10000.0, -np.arange(0, E, 2, dtype=np.float64) / E)[None, :]
+    out = np.empty((max_left + max_right + 1, E), np.float64)
+    out[:, 0::2], out[:, 1::2] = np.sin(delta * w), np.cos(delta * w)
+    return out.astype(np.float32)
+
+
 def layernorm_fwd(x, out, T: int, B: int, N: int, gamma=None, beta=None, eps: float = 1e-5, res=None,
                   lengths: Optional[DeviceBytes] = None, stream: int = 0):
     """LayerNorm over the first N columns of each row of x (+ res) into out
