@@ -23,6 +23,13 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           torch.nn.Conv1d over time, time-major,
                                           bias and activation fused
                                           (asr_conv1d_fwd); no reference member
+    Conv2d.from_torch(conv, bn, act, feat_in=F).forward
+    Conv2dSubsampling.from_torch(conv, out, feat_in, scale).forward
+                                          torch.nn.Conv2d over (time, frequency),
+                                          time-major with the frequency axis inside
+                                          the row (asr_conv2d_fwd), and the
+                                          Conv2dSubsampling front end of Conformer
+                                          encoders; no reference member
     MultiheadAttention.from_torch(mha, chunk, left, right).forward
     LayerNorm.from_torch(ln).forward / TransformerEncoderLayer.from_torch(layer).forward
                                           torch.nn.MultiheadAttention (self-attention
@@ -114,6 +121,7 @@ EXPORTS = [
     "asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd",
     "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
     "asr_conv1d_out_frames", "asr_conv1d_fwd", "asr_glu_dwconv_fwd",
+    "asr_conv2d_out_frames", "asr_conv2d_out_feats", "asr_conv2d_fwd",
     "asr_attention_fwd", "asr_layernorm_fwd", "asr_mask_rows",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
@@ -236,6 +244,9 @@ def lib() -> ctypes.CDLL:
         "asr_gru_recur_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _i, _vp],
         "asr_conv1d_out_frames": [_vp, _i],
         "asr_conv1d_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i, _vp],
+        "asr_conv2d_out_frames": [_vp, _i],
+        "asr_conv2d_out_feats": [_vp],
+        "asr_conv2d_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i, _vp],
         "asr_glu_dwconv_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _vp],
         "asr_attention_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp,
                               ctypes.c_long, _i, _i, _i, _i, _i, _vp],
@@ -955,6 +966,302 @@ class Conv1d:
         conv1d_fwd(x, self.W, self.b, out, T, B, self.desc, lengths=lengths, out_lengths=oln, stream=stream or 0)
         self._keep = lengths
         return out, T_out, oln
+
+
+# -------------------------------------------------------------------- Conv2d
+class Conv2dDesc(ctypes.Structure):
+    """asr_conv2d_desc (include/asr_amd.h)."""
+    _fields_ = [("c_in", _i), ("c_out", _i), ("feat_in", _i), ("kernel_t", _i), ("kernel_f", _i),
+                ("stride_t", _i), ("stride_f", _i), ("pad_t_lo", _i), ("pad_t_hi", _i), ("pad_f_lo", _i),
+                ("pad_f_hi", _i), ("groups", _i), ("act", _i), ("clip", _f)]
+
+
+def conv2d_desc(c_in: int, c_out: int, feat_in: int, kernel_t: int, kernel_f: int, stride_t: int = 1,
+                stride_f: int = 1, pad_t_lo: int = 0, pad_t_hi: int = 0, pad_f_lo: int = 0, pad_f_hi: int = 0,
+                groups: int = 1, act=None, clip: float = 20.0) -> Conv2dDesc:
+    """A Conv2dDesc from keywords; act: None, "relu", "clip" or an ASR_CONV_ACT_* value."""
+    a = CONV_ACTS[act.lower()] if isinstance(act, str) else CONV_ACT_NONE if act is None else int(act)
+    return Conv2dDesc(c_in, c_out, feat_in, kernel_t, kernel_f, stride_t, stride_f, pad_t_lo, pad_t_hi, pad_f_lo,
+                      pad_f_hi, groups, a, clip)
+
+
+def conv2d_out_frames(desc, n: int) -> int:
+    """asr_conv2d_out_frames: frames out for n frames in (< 0 for a bad
+    descriptor); desc is a Conv2dDesc or the keywords of conv2d_desc."""
+    d = desc if isinstance(desc, Conv2dDesc) else conv2d_desc(**desc)
+    return int(lib().asr_conv2d_out_frames(ctypes.byref(d), int(n)))
+
+
+def conv2d_out_feats(desc) -> int:
+    """asr_conv2d_out_feats: frequency bins out, F_out >= 1 (< 0 for a bad
+    descriptor); desc is a Conv2dDesc or the keywords of conv2d_desc."""
+    d = desc if isinstance(desc, Conv2dDesc) else conv2d_desc(**desc)
+    return int(lib().asr_conv2d_out_feats(ctypes.byref(d)))
+
+
+def conv2d_fwd(x: DeviceMatrix, W: DeviceMatrix, b: Optional[DeviceMatrix], out: DeviceMatrix, T: int, B: int,
+               desc: Conv2dDesc, lengths: Optional[DeviceBytes] = None, out_lengths: Optional[DeviceBytes] = None,
+               col: int = 0, stream: int = 0) -> DeviceMatrix:
+    """One convolution over (time, frequency) (asr_conv2d_fwd): x [T*B, >=
+    feat_in * c_in] time-major, element (f, ci) of a row at f * c_in + ci (the
+    row stride is x.cols), W [kernel_t * kernel_f * c_in / groups, c_out], b
+    [c_out] or None, the result into columns [col, col + F_out * c_out) of out
+    [T_out*B, ...] (the row stride is out.cols); lengths from device_lengths(),
+    out_lengths a DeviceBytes of 4*B bytes."""
+    T_out, F_out = conv2d_out_frames(desc, T), conv2d_out_feats(desc)
+    assert x.rows == T * B and x.cols >= desc.feat_in * desc.c_in, (x.rows, x.cols)
+    assert T_out <= 0 or out.rows == T_out * B, (out.rows, T_out, B)
+    assert F_out <= 0 or (0 <= col and col + F_out * desc.c_out <= out.cols), (out.cols, col, F_out)
+    assert W.rows * W.cols == desc.kernel_t * desc.kernel_f * (desc.c_in // max(desc.groups, 1)) * desc.c_out, \
+        (W.rows, W.cols)
+    assert out_lengths is None or out_lengths.nbytes >= 4 * B
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_conv2d_fwd(ctypes.byref(desc), x.ptr, x.cols, opt(lengths), W.ptr, opt(b), out.ptr + 4 * col,
+                               out.cols, opt(out_lengths), T, B, stream), "asr_conv2d_fwd")
+    return out
+
+
+def _pair(v, what: str) -> Tuple[int, int]:
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"Conv2d: {what} {v!r}")
+        return int(v[0]), int(v[1])
+    return int(v), int(v)
+
+
+class Conv2d:
+    """torch.nn.Conv2d(c_in, c_out, kernel, stride, groups=...) on an input
+    [B][C][T][F] for inference on asr_conv2d_fwd, time-major in and out (row
+    t*B + b holds F * c_in floats, element (f, ci) at f * c_in + ci), bias and
+    activation fused; no arithmetic here.  kernel, stride: an int or (time,
+    frequency); padding: an int, torch's (time, frequency) (both sides of each
+    axis), 'valid', or ((t_lo, t_hi), (f_lo, f_hi)); groups 1 or c_in == c_out
+    == groups; act None, 'relu' or 'clip'; weight [kt][kf][c_in / groups][c_out]
+    and bias [c_out] in this library's layout (zeros if None; pack_torch makes
+    them from a torch module)."""
+
+    def __init__(self, c_in: int, c_out: int, feat_in: int, kernel, stride=1, padding=0, groups: int = 1, act=None,
+                 clip: float = 20.0, weight=None, bias=None):
+        self.desc = self.make_desc(c_in, c_out, feat_in, kernel, stride, padding, groups, act, clip)
+        kt, kf = self.desc.kernel_t, self.desc.kernel_f
+        rc = conv2d_out_feats(self.desc)
+        if rc < 0:
+            raise AsrError(-rc, "asr_conv2d_out_feats")
+        self.feat_out = rc
+        shape = (kt * kf * (c_in // groups), c_out)
+        w = np.zeros(shape, np.float32) if weight is None else np.asarray(weight, np.float32).reshape(shape)
+        b = np.zeros(c_out, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(c_out)
+        self.W, self.b = DeviceMatrix.from_numpy(w), DeviceMatrix.from_numpy(b.reshape(-1, 1))
+        self._keep = None   # the last call's uploaded lengths: alive until its kernel is done
+
+    @staticmethod
+    def make_desc(c_in: int, c_out: int, feat_in: int, kernel, stride=1, padding=0, groups: int = 1, act=None,
+                  clip: float = 20.0) -> Conv2dDesc:
+        """The Conv2dDesc of the constructor's keywords.  No device call."""
+        (kt, kf), (st, sf) = _pair(kernel, "kernel"), _pair(stride, "stride")
+        (ptl, pth), (pfl, pfh) = Conv2d.parse_padding(padding)
+        return conv2d_desc(c_in, c_out, feat_in, kt, kf, st, sf, ptl, pth, pfl, pfh, groups, act, clip)
+
+    @staticmethod
+    def parse_padding(padding) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+        """((pad_t_lo, pad_t_hi), (pad_f_lo, pad_f_hi)) of a padding argument."""
+        if isinstance(padding, str):
+            if padding == "valid":
+                return (0, 0), (0, 0)
+            raise ValueError(f"Conv2d: padding {padding!r} is not supported")
+        if isinstance(padding, (tuple, list)):
+            if len(padding) != 2:
+                raise ValueError(f"Conv2d: padding {padding!r}")
+            if isinstance(padding[0], (tuple, list)) or isinstance(padding[1], (tuple, list)):
+                return _pair(padding[0], "padding"), _pair(padding[1], "padding")
+            return (int(padding[0]),) * 2, (int(padding[1]),) * 2
+        return (int(padding),) * 2, (int(padding),) * 2
+
+    @staticmethod
+    def pack_torch(conv, bn=None):
+        """(W [kt][kf][c_in/g][c_out] float32, b [c_out] float32, keywords of
+        Conv2d without feat_in) from a torch.nn.Conv2d whose input is
+        [B][C][T][F]; with bn an eval-mode torch.nn.BatchNorm2d is folded in
+        float64 (W' = W g / sqrt(var + eps) per output channel, b' = (b - mean) g
+        / sqrt(var + eps) + beta) and the result rounded to fp32 once.  No
+        device call."""
+        if conv.padding_mode != "zeros":
+            raise ValueError(f"Conv2d.pack_torch: padding_mode {conv.padding_mode!r} is not supported")
+        if tuple(conv.dilation) != (1, 1):
+            raise ValueError(f"Conv2d.pack_torch: dilation {tuple(conv.dilation)} is not supported")
+        c_in, c_out, g = conv.in_channels, conv.out_channels, conv.groups
+        if g != 1 and not (g == c_in == c_out):
+            raise ValueError("Conv2d.pack_torch: groups must be 1 or c_in == c_out == groups")
+        w = conv.weight.detach().cpu().double().numpy()                  # [c_out][c_in/g][kt][kf]
+        b = (conv.bias.detach().cpu().double().numpy() if conv.bias is not None else np.zeros(c_out, np.float64))
+        if bn is not None:
+            if bn.training or bn.running_mean is None or bn.running_var is None:
+                raise ValueError("Conv2d.pack_torch: the BatchNorm2d must be in eval() with running statistics")
+            if bn.num_features != c_out:
+                raise ValueError("Conv2d.pack_torch: BatchNorm2d features != c_out")
+            mean = bn.running_mean.detach().cpu().double().numpy()
+            var = bn.running_var.detach().cpu().double().numpy()
+            gamma = bn.weight.detach().cpu().double().numpy() if bn.affine else np.ones(c_out)
+            beta = bn.bias.detach().cpu().double().numpy() if bn.affine else np.zeros(c_out)
+            scale = gamma / np.sqrt(var + bn.eps)
+            w = w * scale[:, None, None, None]
+            b = (b - mean) * scale + beta
+        W = np.ascontiguousarray(w.transpose(2, 3, 1, 0)).astype(np.float32)   # [kt][kf][c_in/g][c_out]
+        pad = conv.padding if isinstance(conv.padding, str) else tuple(int(v) for v in conv.padding)
+        kwargs = dict(c_in=c_in, c_out=c_out, kernel=tuple(int(v) for v in conv.kernel_size),
+                      stride=tuple(int(v) for v in conv.stride), padding=Conv2d.parse_padding(pad), groups=g)
+        return W, b.astype(np.float32), kwargs
+
+    @classmethod
+    def from_torch(cls, conv, bn=None, act=None, clip: float = 20.0, *, feat_in: int) -> "Conv2d":
+        """feat_in: the frequency bins F of the input (a torch.nn.Conv2d does not know them)."""
+        W, b, kw = cls.pack_torch(conv, bn)
+        return cls(feat_in=feat_in, **kw, act=act, clip=clip, weight=W, bias=b)
+
+    def out_frames(self, n: int) -> int:
+        return conv2d_out_frames(self.desc, n)
+
+    def forward(self, x: DeviceMatrix, T: int, B: int, lengths=None, stream: int = 0):
+        """x time-major [T*B, >= feat_in * c_in]; lengths None, a sequence of B
+        counts or a DeviceBytes of int32 [B].  Returns (out DeviceMatrix
+        [T_out*B, F_out * c_out] with zero rows past each utterance's count,
+        T_out, out_lengths): the last a DeviceBytes of int32 [B] that the next
+        layer takes as lengths, or None when no lengths were given.
+        Asynchronous on stream."""
+        T_out = self.out_frames(T)
+        if T_out <= 0:
+            raise AsrError(ASR_ERR_ARG if T_out == 0 else -T_out, "asr_conv2d_out_frames")
+        lengths = _device_lengths_or_none(lengths)
+        out = DeviceMatrix(T_out * B, self.feat_out * self.desc.c_out)
+        oln = None if lengths is None else DeviceBytes(4 * B)
+        conv2d_fwd(x, self.W, self.b, out, T, B, self.desc, lengths=lengths, out_lengths=oln, stream=stream or 0)
+        self._keep = lengths
+        return out, T_out, oln
+
+
+class Conv2dSubsampling:
+    """The module Conformer encoders of ESPnet / WeNet (Conv2dSubsampling4 / 6 /
+    8: .conv, .out[0]) and NeMo (ConvSubsampling 'striding' / 'dw_striding':
+    .conv, .out) begin with, for inference, time-major: strided Conv2d layers
+    over (time, frequency) with their ReLUs fused (asr_conv2d_fwd, the
+    out_lengths of each the lengths of the next), then the Linear over the
+    flattened (channel, frequency) axis (asr_linear_fwd with EPI_BIAS), then
+    asr_mask_rows.  No arithmetic here.  The Linear's input rows are permuted
+    when packing from the toolkits' c * F' + f order to this library's f * C +
+    c, and scale (the toolkits' xscale = sqrt(E), applied after the module) is
+    folded into its weights and bias in float64 before the one rounding to fp32.
+    Tested on stand-in modules written from the toolkits' published
+    definitions only (tests/conv2d_reference.py), never on the toolkits
+    themselves or their checkpoints."""
+
+    def __init__(self, layers: Sequence[Conv2d], w_out, b_out):
+        self.layers = list(layers)
+        assert self.layers
+        for a, b in zip(self.layers, self.layers[1:]):
+            assert b.desc.c_in == a.desc.c_out and b.desc.feat_in == a.feat_out, "the layers do not chain"
+        self.feat_in, self.c_in = self.layers[0].desc.feat_in, self.layers[0].desc.c_in
+        last = self.layers[-1]
+        w = np.asarray(w_out, np.float32)
+        assert w.ndim == 2 and w.shape[0] == last.feat_out * last.desc.c_out, w.shape
+        self.E = w.shape[1]
+        self.w_out = DeviceMatrix.from_numpy(w)
+        self.b_out = DeviceMatrix.from_numpy(np.asarray(b_out, np.float32).reshape(self.E, 1))
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_linear(out, c_out: int, feat_out: int, scale: float = 1.0):
+        """(W [feat_out * c_out, E], b [E]) float32 of the module's Linear: row
+        f * c_out + c of W is column c * feat_out + f of out.weight, both times
+        scale in float64, rounded once.  No device call."""
+        if out.in_features != c_out * feat_out:
+            raise ValueError(f"Conv2dSubsampling: the Linear takes {out.in_features} inputs, the convolutions make "
+                             f"{c_out} channels x {feat_out} bins")
+        w = out.weight.detach().cpu().double().numpy() * float(scale)              # [E][c * F' + f]
+        b = (out.bias.detach().cpu().double().numpy() if out.bias is not None
+             else np.zeros(out.out_features)) * float(scale)
+        E = out.out_features
+        w = w.reshape(E, c_out, feat_out).transpose(2, 1, 0).reshape(feat_out * c_out, E)
+        return np.ascontiguousarray(w).astype(np.float32), b.astype(np.float32)
+
+    @staticmethod
+    def pack_torch(conv, out, feat_in: int, scale: float = 1.0, causal: bool = False):
+        """(layers, w_out, b_out) on the host: layers a list of the keywords of
+        Conv2d (feat_in, act, weight and bias included) of every Conv2d of the
+        Sequential, w_out / b_out as pack_linear makes them.  The arguments are
+        from_torch's; every refusal is decided here.  No device call."""
+        import torch
+        mods, layers, F = list(conv), [], int(feat_in)
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if not isinstance(m, torch.nn.Conv2d):
+                raise ValueError(f"Conv2dSubsampling: module {i} of the Sequential is a {type(m).__name__}, not a "
+                                 "Conv2d (optionally followed by a ReLU)")
+            act = None
+            if i + 1 < len(mods) and isinstance(mods[i + 1], torch.nn.ReLU):
+                act, i = "relu", i + 1
+            W, b, kw = Conv2d.pack_torch(m)
+            if layers and kw["c_in"] != layers[-1]["c_out"]:
+                raise ValueError(f"Conv2dSubsampling: module {i} takes {kw['c_in']} channels, the layer before it "
+                                 f"makes {layers[-1]['c_out']}")
+            if causal:
+                kw["padding"] = ((kw["kernel"][0] - 1, 0), kw["padding"][1])
+            kw.update(feat_in=F, act=act, weight=W, bias=b)
+            F = conv2d_out_feats(Conv2d.make_desc(**{k: v for k, v in kw.items() if k not in ("weight", "bias")}))
+            if F < 0:
+                raise AsrError(-F, "asr_conv2d_out_feats")
+            layers.append(kw)
+            i += 1
+        if not layers:
+            raise ValueError("Conv2dSubsampling: no Conv2d in the Sequential")
+        w, b = Conv2dSubsampling.pack_linear(out, layers[-1]["c_out"], F, scale)
+        return layers, w, b
+
+    @classmethod
+    def from_torch(cls, conv, out, feat_in: int, scale: float = 1.0, causal: bool = False) -> "Conv2dSubsampling":
+        """conv: a torch.nn.Sequential of Conv2d modules on [B][C][T][F], each
+        optionally followed by a ReLU (fused into that layer); any other module
+        is refused.  out: the torch.nn.Linear over the flattened (c, f) axis.
+        causal: every layer's time padding becomes (kernel_t - 1, 0), the
+        streamable form (a module that pads that way by hand before each
+        unpadded-in-time convolution); the frequency padding stays."""
+        layers, w, b = cls.pack_torch(conv, out, feat_in, scale, causal)
+        return cls([Conv2d(**kw) for kw in layers], w, b)
+
+    def frames(self, n: int) -> int:
+        """Frames out for n frames in: the layers' out_frames chained."""
+        for layer in self.layers:
+            n = layer.out_frames(n)
+        return n
+
+    def forward(self, x, T: int, B: int, lengths=None, zero_padding: bool = True, stream: int = 0):
+        """x time-major [T*B, >= feat_in * c_in] (a log-mel matrix as it stands
+        for c_in = 1); lengths None, a sequence of B counts or a DeviceBytes of
+        int32 [B].  Returns (out, T_out, out_lengths): a new DeviceMatrix
+        [T_out*B, E], rows past each utterance's count zero when zero_padding
+        (else the Linear's bias), and the DeviceBytes of int32 [B] that the
+        encoder layers take as lengths (None when no lengths were given)."""
+        if x.rows != T * B or x.cols < self.feat_in * self.c_in:
+            raise ValueError(f"Conv2dSubsampling.forward: x is [{x.rows}, {x.cols}], expected [{T * B}, >= "
+                             f"{self.feat_in * self.c_in}]")
+        st = stream or 0
+        lengths = _device_lengths_or_none(lengths)
+        keep, h, t, ln = [lengths], x, T, lengths
+        for i, layer in enumerate(self.layers):
+            t_out = layer.out_frames(t)
+            if t_out <= 0:
+                raise AsrError(ASR_ERR_ARG if t_out == 0 else -t_out, "asr_conv2d_out_frames")
+            o = self._scratch.get(f"h{i}", t_out * B, layer.feat_out * layer.desc.c_out)
+            oln = None if ln is None else DeviceBytes(4 * B)
+            conv2d_fwd(h, layer.W, layer.b, o, t, B, layer.desc, lengths=ln, out_lengths=oln, stream=st)
+            keep.append(oln)
+            h, t, ln = o, t_out, oln
+        out = DeviceMatrix(t * B, self.E)
+        linear_fwd(h, self.w_out, self.b_out, out, EPI_BIAS, st)
+        if zero_padding and ln is not None:
+            mask_rows(out, t, B, self.E, ln, st)
+        self._keep = keep
+        return out, t, ln
 
 
 # ------------------------------------------------- attention and LayerNorm

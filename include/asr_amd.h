@@ -376,6 +376,87 @@ int asr_conv1d_fwd(const asr_conv1d_desc* d, const float* d_x, long ldx, const i
                    const float* d_W, const float* d_b, float* d_out, long ldo,
                    int32_t* d_out_lengths, int T, int B, asr_stream_t s);
 
+/* One convolution layer over the (time, frequency) plane — torch.nn.Conv2d
+ * semantics on an input [B][C][T][F], in this library's time-major layout,
+ * with bias and activation fused: the layers of the Conv2dSubsampling module
+ * that ESPnet, WeNet, NeMo and icefall encoders begin with; no reference
+ * member.  The frequency axis lives inside the row, channels innermost:
+ * d_x: row t*B + b holds F * c_in floats (F = feat_in), element (f, ci) at
+ * f*c_in + ci, row stride ldx >= F * c_in.  d_out: row t'*B + b receives
+ * F_out * c_out floats, element (f', co) at f'*c_out + co, row stride
+ * ldo >= F_out * c_out; columns past that of a row are not touched.  So a
+ * log-mel matrix from asr_fbank_fwd is the c_in = 1 input as it stands, and an
+ * output is the next layer's input, or asr_linear_fwd's, as it stands.
+ * d_W [kernel_t][kernel_f][c_in / groups][c_out] row-major (depthwise:
+ * [kernel_t][kernel_f][C]); d_b [c_out] or NULL for zeros.
+ * Counts, with k, s, lo, hi the kernel, stride and pads of an axis (dilation 1):
+ *   count(n) = 0                                   if n <= 0 or n + lo + hi < k
+ *            = floor((n + lo + hi - k) / s) + 1    otherwise
+ * (torch's output size, asr_conv1d_out_frames' formula); out_frames(n) is
+ * count(n) on the time axis, T_out = out_frames(T), F_out = out_feats() =
+ * count(feat_in) on the frequency axis.  For an unpadded k 3 / s 2 layer
+ * out_frames(n) is the number of entries the toolkits' mask[:, :, :-2:2] keeps.
+ *   out(t', b, f', co) = act((sum_{jt} sum_{jf} sum_{ci}
+ *       xh(t' s_t - pad_t_lo + jt, b, f' s_f - pad_f_lo + jf, ci) W[jt][jf][ci][co]) + b[co])
+ * where xh is x inside the utterance's [0, len[b]) x [0, F) and exactly 0
+ * outside it.  The zero is selected where x is fetched, never multiplied in:
+ * frames t >= len[b] of x (and columns >= F * c_in of a row) may hold NaN.
+ * The order of every output element is fixed: from a zero accumulator, jt
+ * ascending; within jt the run of kernel_f * c_in consecutive input floats that
+ * starts at column (f' s_f - pad_f_lo) * c_in ascending (jf-major, ci-minor) —
+ * dense: on fp32 MFMA in groups of 4 counted from the run's start, with a
+ * zero-filled tail, groups wholly past the run not issued; depthwise: one
+ * fmaf chain, jt ascending, jf ascending — then the bias is added, then the
+ * activation (ASR_CONV_ACT_*, as asr_conv1d_fwd).  Always fp32 arithmetic,
+ * whatever asr_set_dense_arith says.  Nothing else enters an element's bits:
+ * not T, B, the row's position, other utterances, ldx / ldo, pointer
+ * alignment (16-byte loads of aligned rows with c_in % 4 == 0 give the scalar
+ * path's bits), or whether a zero came from padding, a length or data.  So
+ * with feat_in = 1, kernel_f = 1 and no frequency padding the result is
+ * asr_conv1d_fwd's bit for bit, and a layer with pad_t_lo = kernel_t - 1,
+ * pad_t_hi = 0 run over chunks with their kernel_t - 1 history frames
+ * prepended and pad_t_lo = 0 gives the whole call's bits.
+ * Lengths as in asr_conv1d_fwd: d_lengths device int32 [B], clamped to [0, T],
+ * NULL = all T.  Output rows t' >= out_frames(len[b]) are all zeros;
+ * d_out_lengths (device int32 [B], may be NULL, must not overlap d_lengths)
+ * receives out_frames(len[b]) and can be passed unchanged as d_lengths of the
+ * next layer.  For t' below that count the result is
+ * torch.nn.functional.conv2d on the utterance's own len[b] frames, alone, with
+ * zero padding.
+ * One launch, asynchronous on s, no allocation, no workspace, no host sync;
+ * d_out must not overlap d_x.  Checks, in this order, all before any HIP call —
+ * ASR_ERR_ARG: a NULL descriptor, d_x, d_W or d_out; non-positive c_in, c_out,
+ * feat_in, kernel_t, kernel_f, stride_t or stride_f; a negative pad; an unknown
+ * act; ASR_CONV_ACT_CLIP with a clip that is not finite or <= 0; F_out = 0
+ * (feat_in + pad_f_lo + pad_f_hi < kernel_f); non-positive T or B;
+ * ldx < feat_in * c_in or ldo < F_out * c_out; T_out = 0.
+ * ASR_ERR_UNSUPPORTED: groups other than 1 or c_in == c_out == groups;
+ * kernel_t or kernel_f > 16; stride_t or stride_f > 16; c_in, c_out or
+ * feat_in > 4096; pad_f_lo or pad_f_hi > 4096; T + pad_t_lo + pad_t_hi >
+ * INT_MAX - 4096; T*B or T_out*B > INT_MAX; T_out*B*F_out > INT_MAX - 128 (the
+ * flat output rows; with these limits every grid dimension fits: at most
+ * 2^26 x 64 workgroups).
+ * asr_conv2d_out_frames and asr_conv2d_out_feats are host only, no HIP call:
+ * the count, or minus the status asr_conv2d_fwd would refuse the descriptor
+ * with (< 0; asr_conv2d_out_feats is therefore never 0). */
+typedef struct asr_conv2d_desc {
+    int c_in, c_out;              /* channels, 1 .. 4096 each */
+    int feat_in;                  /* F: frequency bins of the input, 1 .. 4096 */
+    int kernel_t, kernel_f;       /* 1 .. 16 each */
+    int stride_t, stride_f;       /* 1 .. 16 each */
+    int pad_t_lo, pad_t_hi;       /* zero frames before / after the utterance, >= 0
+                                     (causal: pad_t_lo = kernel_t - 1, pad_t_hi = 0) */
+    int pad_f_lo, pad_f_hi;       /* zero bins below / above, 0 .. 4096 each */
+    int groups;                   /* 1, or c_in == c_out == groups (depthwise) */
+    int act;                      /* ASR_CONV_ACT_* */
+    float clip;                   /* ASR_CONV_ACT_CLIP: min(max(v, 0), clip), clip > 0 */
+} asr_conv2d_desc;
+int asr_conv2d_out_frames(const asr_conv2d_desc* d, int n_frames);
+int asr_conv2d_out_feats(const asr_conv2d_desc* d);
+int asr_conv2d_fwd(const asr_conv2d_desc* d, const float* d_x, long ldx, const int32_t* d_lengths,
+                   const float* d_W, const float* d_b, float* d_out, long ldo,
+                   int32_t* d_out_lengths, int T, int B, asr_stream_t s);
+
 /* The middle of a Conformer convolution module in one launch: GLU -> depthwise
  * convolution over time -> bias (an eval-mode BatchNorm folded into w and b) ->
  * activation.  The two pointwise convolutions around it are asr_linear_fwd; no
