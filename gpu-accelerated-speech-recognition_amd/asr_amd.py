@@ -45,6 +45,15 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           with GLU -> depthwise -> BatchNorm ->
                                           SiLU in one launch (asr_glu_dwconv_fwd);
                                           no reference member
+    TransformerDecoder.from_torch(embedding, decoder, output).score(hyps, utt, memory, T, B)
+    attention_rescore(nbest, decoder, memory, T, B) / CTCDecoder.attention_rescore(...)
+                                          attention-decoder rescoring of an n-best:
+                                          causal self-attention, grouped
+                                          cross-attention over each hypothesis's own
+                                          utterance (asr_cross_attention_fwd) and
+                                          the token scores (asr_token_score); the
+                                          embedding is gathered on the host; no
+                                          reference member
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
                                           waveform -> log-mel / MFCC features
                                           (asr_fbank_*); no reference member
@@ -123,6 +132,7 @@ EXPORTS = [
     "asr_conv1d_out_frames", "asr_conv1d_fwd", "asr_glu_dwconv_fwd",
     "asr_conv2d_out_frames", "asr_conv2d_out_feats", "asr_conv2d_fwd",
     "asr_attention_fwd", "asr_layernorm_fwd", "asr_mask_rows",
+    "asr_cross_attention_fwd", "asr_token_score",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
     "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
@@ -253,6 +263,9 @@ def lib() -> ctypes.CDLL:
         "asr_layernorm_fwd": [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _f, _vp, _vp, ctypes.c_long,
                               _i, _i, _i, _vp],
         "asr_mask_rows": [_vp, ctypes.c_long, _vp, _i, _i, _i, _vp],
+        "asr_cross_attention_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp,
+                                    _i, _vp, ctypes.c_long, _i, _i, _i, _i, _vp],
+        "asr_token_score": [_vp, ctypes.c_long, _vp, _vp, _vp, _i, _i, _i, _vp],
         "asr_fbank_num_frames": [_vp, _i],
         "asr_fbank_feature_dim": [_vp],
         "asr_fbank_host_tables": [_vp, _vp, _vp, _vp],
@@ -1287,6 +1300,7 @@ class ColumnView:
     def __init__(self, m, col: int):
         assert 0 <= col < m.cols, (col, m.cols)
         self.ptr, self.rows, self.cols, self._keep = m.ptr + 4 * col, m.rows, m.cols, m
+        self.col = col + int(getattr(m, "col", 0))
 
 
 def _device_lengths_or_none(lengths):
@@ -1533,6 +1547,489 @@ class TransformerEncoderLayer:
             self.norm2.forward(f2, T, B, lengths, res=h, out=out, stream=st)
         self._keep = lengths
         return out
+
+
+# ------------------------------------- attention decoder (n-best rescoring)
+class XAttnDesc(ctypes.Structure):
+    """asr_xattn_desc (include/asr_amd.h)."""
+    _fields_ = [("heads", _i), ("head_dim", _i), ("scale", _f)]
+
+
+def xattn_desc(heads: int, head_dim: int, scale: float = 0.0) -> XAttnDesc:
+    """An XAttnDesc: scale 0 = 1/sqrt(head_dim)."""
+    return XAttnDesc(heads, head_dim, scale)
+
+
+def _need_matrix(what: str, m, rows: int, cols: int, ld: Optional[int] = None) -> None:
+    """ValueError unless the device matrix (or view) m holds the rows x cols
+    floats a call will touch at row stride ld (default m.cols)."""
+    stride = int(m.cols if ld is None else ld)
+    col = int(getattr(m, "col", 0)) if ld is None else 0
+    if rows < 1 or cols < 1 or stride < col + cols or (rows - 1) * stride + col + cols > int(m.rows) * int(m.cols):
+        raise ValueError(f"{what}: needs {rows} rows x {cols} columns at row stride {stride}, got a buffer of "
+                         f"{m.rows} x {m.cols}" + (f" from column {col}" if col else ""))
+
+
+def _need_int32(what: str, d, n: int) -> None:
+    if d is not None and d.nbytes < 4 * n:
+        raise ValueError(f"{what}: needs {n} int32, got {d.nbytes} bytes")
+
+
+def _device_int32_exact(what: str, a, n: int):
+    """a device int32 [n] array from None, a DeviceBytes or a host sequence of exactly n values."""
+    if a is None or isinstance(a, DeviceBytes):
+        _need_int32(what, a, n)
+        return a
+    if len(a) != n:
+        raise ValueError(f"{what}: {len(a)} values, not {n}")
+    return device_lengths(a)
+
+
+def cross_attention_fwd(q, k, v, out, U: int, N: int, T: int, B: int, desc: XAttnDesc, hyp_offsets, max_hyps: int,
+                        q_lengths=None, k_lengths=None, ldq: Optional[int] = None, ldk: Optional[int] = None,
+                        ldv: Optional[int] = None, ldo: Optional[int] = None, stream: int = 0):
+    """Grouped cross-attention (asr_cross_attention_fwd): q, out [U*N, >= E]
+    (row u*N + n: token u of hypothesis n), k, v [T*B, >= E] (row j*B + b:
+    frame j of utterance b), E = heads*head_dim; anything with .ptr, .rows and
+    .cols (the row stride unless ld* is given), so k and v may be ColumnViews
+    of one [T*B, 2E] projection.  hyp_offsets: B + 1 values (a sequence or a
+    DeviceBytes of int32), hypotheses off[b] .. off[b+1] - 1 belong to
+    utterance b; max_hyps bounds their count per utterance.  q_lengths [N],
+    k_lengths [B]: None, sequences or DeviceBytes.  Raises ValueError before
+    any device call if a buffer is smaller than the rows and columns the call
+    will touch."""
+    U, N, T, B = int(U), int(N), int(T), int(B)
+    E = int(desc.heads) * int(desc.head_dim)
+    _need_matrix("cross_attention_fwd: q", q, U * N, E, ldq)
+    _need_matrix("cross_attention_fwd: k", k, T * B, E, ldk)
+    _need_matrix("cross_attention_fwd: v", v, T * B, E, ldv)
+    _need_matrix("cross_attention_fwd: out", out, U * N, E, ldo)
+    if hyp_offsets is None:
+        raise ValueError("cross_attention_fwd: hyp_offsets is required")
+    off = _device_int32_exact("cross_attention_fwd: hyp_offsets", hyp_offsets, B + 1)
+    ql = _device_int32_exact("cross_attention_fwd: q_lengths", q_lengths, N)
+    kl = _device_int32_exact("cross_attention_fwd: k_lengths", k_lengths, B)
+    ld = lambda m, given: int(m.cols if given is None else given)   # noqa: E731
+    opt = lambda d: d.ptr if d is not None else None   # noqa: E731
+    check(lib().asr_cross_attention_fwd(ctypes.byref(desc), q.ptr, ld(q, ldq), k.ptr, ld(k, ldk), v.ptr, ld(v, ldv),
+                                        opt(ql), opt(kl), off.ptr, int(max_hyps), out.ptr, ld(out, ldo), U, N, T, B,
+                                        stream), "asr_cross_attention_fwd")
+    out._xattn_keep = (off, ql, kl)      # host sequences were uploaded here: keep them until out goes
+    return out
+
+
+def token_score(logp, tokens, lengths, U: int, N: int, V: int, ld: Optional[int] = None,
+                stream: int = 0) -> np.ndarray:
+    """fp64 [N]: sum over u < lengths[n] of logp[u*N + n][tokens[u][n]]
+    (asr_token_score), logp a device [U*N, >= V] log-softmax buffer that stays
+    on the device; tokens int [U][N] on the host; lengths [N] or None (= U).
+    A token outside [0, V) gives -inf.  Only the N doubles are copied back."""
+    U, N, V = int(U), int(N), int(V)
+    _need_matrix("token_score: logp", logp, U * N, V, ld)
+    tok = np.ascontiguousarray(tokens, dtype=np.int32)
+    if tok.size != U * N:
+        raise ValueError(f"token_score: {tok.size} tokens, not U*N = {U * N}")
+    if lengths is not None and len(lengths) != N:
+        raise ValueError(f"token_score: {len(lengths)} lengths, not N = {N}")
+    d_tok = _upload(tok, stream)
+    d_len = None if lengths is None else _upload(np.ascontiguousarray(lengths, dtype=np.int32), stream)
+    d_out = DeviceBytes(8 * N)
+    check(lib().asr_token_score(logp.ptr, int(logp.cols if ld is None else ld), d_tok.ptr,
+                                d_len.ptr if d_len is not None else None, d_out.ptr, U, N, V, stream),
+          "asr_token_score")
+    return _download(d_out, N, np.float64, stream)
+
+
+class CrossAttention:
+    """torch.nn.MultiheadAttention(E, heads) as the encoder-decoder attention
+    of a rescoring decoder: N hypotheses (the queries' batch) attend to the
+    memories of B utterances through asr_cross_attention_fwd, so the memory's
+    K / V projection runs once per utterance (project_memory) and not once per
+    hypothesis.  w_q [E, E], w_kv [E, 2E] (K columns first) and w_out [E, E] in
+    this library's [in][out] layout, b_q [E], b_kv [2E], b_out [E] (zeros if
+    None).  No arithmetic here; dropout is ignored."""
+
+    def __init__(self, embed_dim: int, heads: int, w_q=None, b_q=None, w_kv=None, b_kv=None, w_out=None,
+                 b_out=None):
+        E = int(embed_dim)
+        if heads <= 0 or E <= 0 or E % heads:
+            raise ValueError(f"CrossAttention: embed_dim {E} is not a multiple of heads {heads}")
+        hd = E // heads
+        if hd % 4 or hd > 128 or E > 4096:
+            raise ValueError(f"CrossAttention: head_dim {hd} (% 4 == 0, <= 128) / embed_dim {E} (<= 4096) "
+                             "outside what asr_cross_attention_fwd takes")
+        self.E, self.heads = E, heads
+        self.desc = xattn_desc(heads, hd, 0.0)
+        arr = lambda a, shape: (np.zeros(shape, np.float32) if a is None   # noqa: E731
+                                else np.asarray(a, np.float32).reshape(shape))
+        up = lambda a, shape: DeviceMatrix.from_numpy(arr(a, shape))   # noqa: E731
+        self.w_q, self.b_q = up(w_q, (E, E)), up(b_q, (E, 1))
+        self.w_kv, self.b_kv = up(w_kv, (E, 2 * E)), up(b_kv, (2 * E, 1))
+        self.w_out, self.b_out = up(w_out, (E, E)), up(b_out, (E, 1))
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_torch(mha):
+        """(w_q [E, E], b_q [E], w_kv [E, 2E], b_kv [2E], w_out [E, E], b_out
+        [E]) float32 from a torch.nn.MultiheadAttention: MultiheadAttention.
+        pack_torch's arrays (and its refusals) with in_proj split into the
+        query's columns and the memory's.  No device call."""
+        w_in, b_in, w_out, b_out = MultiheadAttention.pack_torch(mha)
+        E = mha.embed_dim
+        return (np.ascontiguousarray(w_in[:, :E]), np.ascontiguousarray(b_in[:E]),
+                np.ascontiguousarray(w_in[:, E:]), np.ascontiguousarray(b_in[E:]), w_out, b_out)
+
+    @staticmethod
+    def pack_linears(linear_q, linear_k, linear_v, linear_out):
+        """The same six arrays from the four torch.nn.Linear modules of a
+        toolkit attention (ESPnet's / WeNet's MultiHeadedAttention: linear_q,
+        linear_k, linear_v, linear_out).  No device call."""
+        (wq, bq), (wk, bk), (wv, bv), (wo, bo) = (_torch_linear(m) for m in (linear_q, linear_k, linear_v,
+                                                                             linear_out))
+        E = wq.shape[0]
+        if any(w.shape != (E, E) for w in (wq, wk, wv, wo)):
+            raise ValueError("CrossAttention.pack_linears: the four linears are not all E -> E")
+        return (wq, bq, np.ascontiguousarray(np.concatenate([wk, wv], axis=1)), np.concatenate([bk, bv]), wo, bo)
+
+    @classmethod
+    def from_torch(cls, mha) -> "CrossAttention":
+        return cls(mha.embed_dim, mha.num_heads, *cls.pack_torch(mha))
+
+    def project_memory(self, memory, T: int, B: int, out=None, stream: int = 0):
+        """K and V of the encoder output memory [T*B, E] (row j*B + b: frame j
+        of utterance b) as one [T*B, 2E] buffer, computed once per batch of
+        utterances and passed to forward() as kv."""
+        E, M = self.E, int(T) * int(B)
+        _need_matrix("CrossAttention.project_memory: memory", memory, M, E)
+        if memory.rows != M or memory.cols != E:
+            raise ValueError(f"CrossAttention.project_memory: memory is {memory.rows} x {memory.cols}, not "
+                             f"T*B x E = {M} x {E}")
+        out = DeviceMatrix(M, 2 * E) if out is None else out
+        _need_matrix("CrossAttention.project_memory: out", out, M, 2 * E)
+        return linear_fwd(memory, self.w_kv, self.b_kv, out, EPI_BIAS, stream or 0)
+
+    def forward(self, x, U: int, N: int, kv, T: int, B: int, q_lengths=None, k_lengths=None, hyp_offsets=None,
+                max_hyps: Optional[int] = None, out=None, zero_padding: bool = True, stream: int = 0):
+        """Attention of the hypotheses' x [U*N, E] (row u*N + n) over kv =
+        project_memory(...) [T*B, 2E]; q_lengths [N], k_lengths [B] and
+        hyp_offsets [B + 1] as cross_attention_fwd's; max_hyps defaults to N.
+        Returns out [U*N, E] (a buffer of this layer, reused by its next call,
+        unless given); rows past q_lengths are zeros unless zero_padding is
+        False, in which case they hold the output bias."""
+        E, M, st = self.E, int(U) * int(N), stream or 0
+        _need_matrix("CrossAttention.forward: x", x, M, E)
+        if x.rows != M or x.cols != E:
+            raise ValueError(f"CrossAttention.forward: x is {x.rows} x {x.cols}, not U*N x E = {M} x {E}")
+        _need_matrix("CrossAttention.forward: kv", kv, int(T) * int(B), 2 * E)
+        if kv.cols != 2 * E:
+            raise ValueError(f"CrossAttention.forward: kv has {kv.cols} columns, not 2E = {2 * E}")
+        q_lengths = _device_int32_exact("CrossAttention.forward: q_lengths", q_lengths, N)
+        k_lengths = _device_int32_exact("CrossAttention.forward: k_lengths", k_lengths, B)
+        hyp_offsets = _device_int32_exact("CrossAttention.forward: hyp_offsets", hyp_offsets, B + 1)
+        qp, ctx = self._scratch.get("q", M, E), self._scratch.get("ctx", M, E)
+        out = self._scratch.get("out", M, E) if out is None else out
+        _need_matrix("CrossAttention.forward: out", out, M, E)
+        linear_fwd(x, self.w_q, self.b_q, qp, EPI_BIAS, st)
+        cross_attention_fwd(qp, ColumnView(kv, 0), ColumnView(kv, E), ctx, U, N, T, B, self.desc, hyp_offsets,
+                            N if max_hyps is None else max_hyps, q_lengths, k_lengths, stream=st)
+        linear_fwd(ctx, self.w_out, self.b_out, out, EPI_BIAS, st)
+        if zero_padding and q_lengths is not None:
+            mask_rows(out, U, N, E, q_lengths, st)
+        self._keep = (q_lengths, k_lengths, hyp_offsets)
+        return out
+
+
+class TransformerDecoderLayer:
+    """torch.nn.TransformerDecoderLayer (ReLU feed-forward, norm_first either
+    way) for teacher-forced scoring, time-major with the hypotheses as the
+    batch: causal MultiheadAttention over the tokens -> CrossAttention over
+    the utterance's memory -> feed-forward, three LayerNorms; it mirrors
+    TransformerEncoderLayer (post-norm uses the fused residual of
+    asr_layernorm_fwd, pre-norm asr_matadd).  The plain constructor takes the
+    packed parts, so an ESPnet / WeNet DecoderLayer (normalize_before =
+    norm_first, concat_after False) loads through from_linears.  GELU is not
+    built; dropout is ignored."""
+
+    def __init__(self, self_attn: MultiheadAttention, cross_attn: CrossAttention, norm1: LayerNorm,
+                 norm2: LayerNorm, norm3: LayerNorm, w1, b1, w2, b2, norm_first: bool = False):
+        E = self_attn.E
+        w1, w2 = np.asarray(w1, np.float32), np.asarray(w2, np.float32)
+        F = w1.shape[1]
+        if cross_attn.E != E or any(n.N != E for n in (norm1, norm2, norm3)):
+            raise ValueError("TransformerDecoderLayer: the attentions and norms are not all over the same E")
+        if w1.shape != (E, F) or w2.shape != (F, E):
+            raise ValueError(f"TransformerDecoderLayer: feed-forward shapes {w1.shape}, {w2.shape}")
+        d = self_attn.desc
+        if (d.chunk, d.left, d.right) != (1, -1, 0):
+            raise ValueError("TransformerDecoderLayer: self_attn must be causal (chunk 1, left -1, right 0)")
+        self.E, self.F, self.norm_first = E, F, bool(norm_first)
+        self.self_attn, self.cross_attn = self_attn, cross_attn
+        self.norm1, self.norm2, self.norm3 = norm1, norm2, norm3
+        self.w1, self.w2 = DeviceMatrix.from_numpy(w1), DeviceMatrix.from_numpy(w2)
+        self.b1 = DeviceMatrix.from_numpy(np.asarray(b1, np.float32).reshape(F, 1))
+        self.b2 = DeviceMatrix.from_numpy(np.asarray(b2, np.float32).reshape(E, 1))
+        self._scratch, self._keep = _Scratch(), None
+
+    @classmethod
+    def from_torch(cls, layer) -> "TransformerDecoderLayer":
+        """From a torch.nn.TransformerDecoderLayer; ReLU only (ValueError
+        otherwise), norm_first either way, the refusals of
+        MultiheadAttention.pack_torch for both attentions."""
+        w1, b1, w2, b2 = TransformerEncoderLayer.pack_torch(layer)
+        return cls(MultiheadAttention.from_torch(layer.self_attn, 1, -1, 0),
+                   CrossAttention.from_torch(layer.multihead_attn), LayerNorm.from_torch(layer.norm1),
+                   LayerNorm.from_torch(layer.norm2), LayerNorm.from_torch(layer.norm3), w1, b1, w2, b2,
+                   layer.norm_first)
+
+    @classmethod
+    def from_linears(cls, heads: int, self_attn, src_attn, norm1, norm2, norm3, w_1, w_2,
+                     normalize_before: bool = True) -> "TransformerDecoderLayer":
+        """From the parts of a toolkit DecoderLayer (ESPnet / WeNet): self_attn
+        and src_attn each (linear_q, linear_k, linear_v, linear_out) torch
+        Linears, three LayerNorms, the feed-forward's two Linears (ReLU between
+        them).  That layout follows the toolkits' published forward; it is
+        tested on a stand-in module (tests/attention_decoder_reference.py),
+        never on the toolkits themselves."""
+        wq, bq, wkv, bkv, wo, bo = CrossAttention.pack_linears(*self_attn)
+        E = wq.shape[0]
+        sa = MultiheadAttention(E, heads, np.concatenate([wq, wkv], axis=1), np.concatenate([bq, bkv]), wo, bo,
+                                1, -1, 0)
+        ca = CrossAttention(E, heads, *CrossAttention.pack_linears(*src_attn))
+        (w1, b1), (w2, b2) = _torch_linear(w_1), _torch_linear(w_2)
+        return cls(sa, ca, LayerNorm.from_torch(norm1), LayerNorm.from_torch(norm2), LayerNorm.from_torch(norm3),
+                   w1, b1, w2, b2, normalize_before)
+
+    def forward(self, x, U: int, N: int, kv, T: int, B: int, q_lengths=None, k_lengths=None, hyp_offsets=None,
+                max_hyps: Optional[int] = None, out=None, stream: int = 0) -> DeviceMatrix:
+        """x [U*N, E] (row u*N + n: token u of hypothesis n), kv =
+        cross_attn.project_memory(memory, T, B); q_lengths [N], k_lengths [B],
+        hyp_offsets [B + 1] as cross_attention_fwd's.  Returns out (a new
+        DeviceMatrix [U*N, E] unless given; not x) with zero rows past
+        q_lengths."""
+        E, F, M, st = self.E, self.F, int(U) * int(N), stream or 0
+        _need_matrix("TransformerDecoderLayer.forward: x", x, M, E)
+        if x.rows != M or x.cols != E:
+            raise ValueError(f"TransformerDecoderLayer.forward: x is {x.rows} x {x.cols}, not U*N x E = {M} x {E}")
+        _need_matrix("TransformerDecoderLayer.forward: kv", kv, int(T) * int(B), 2 * E)
+        ql = _device_int32_exact("TransformerDecoderLayer.forward: q_lengths", q_lengths, N)
+        kl = _device_int32_exact("TransformerDecoderLayer.forward: k_lengths", k_lengths, B)
+        off = _device_int32_exact("TransformerDecoderLayer.forward: hyp_offsets", hyp_offsets, B + 1)
+        sc = self._scratch
+        h, h2, ff = sc.get("h", M, E), sc.get("h2", M, E), sc.get("ff", M, F)
+        add = lambda a, b, z: check(lib().asr_matadd(a.ptr, b.ptr, z.ptr, M, E, 1.0, st), "asr_matadd")   # noqa: E731
+        cross = lambda q: self.cross_attn.forward(q, U, N, kv, T, B, ql, kl, off, max_hyps,   # noqa: E731
+                                                  zero_padding=False, stream=st)
+        out = DeviceMatrix(M, E) if out is None else out
+        _need_matrix("TransformerDecoderLayer.forward: out", out, M, E)
+        if out is x:
+            raise ValueError("TransformerDecoderLayer.forward: out must not be x")
+        if self.norm_first:
+            n = sc.get("n", M, E)
+            self.norm1.forward(x, U, N, ql, out=n, stream=st)
+            add(x, self.self_attn.forward(n, U, N, ql, zero_padding=False, stream=st), h)
+            self.norm2.forward(h, U, N, ql, out=n, stream=st)
+            add(h, cross(n), h2)
+            self.norm3.forward(h2, U, N, ql, out=n, stream=st)
+            linear_fwd(n, self.w1, self.b1, ff, EPI_BIAS_RELU, st)
+            linear_fwd(ff, self.w2, self.b2, n, EPI_BIAS, st)
+            add(h2, n, out)
+            if ql is not None:
+                mask_rows(out, U, N, E, ql, st)
+        else:
+            a = self.self_attn.forward(x, U, N, ql, zero_padding=False, stream=st)
+            self.norm1.forward(a, U, N, ql, res=x, out=h, stream=st)
+            self.norm2.forward(cross(h), U, N, ql, res=h, out=h2, stream=st)
+            f2 = sc.get("f2", M, E)
+            linear_fwd(h2, self.w1, self.b1, ff, EPI_BIAS_RELU, st)
+            linear_fwd(ff, self.w2, self.b2, f2, EPI_BIAS, st)
+            self.norm3.forward(f2, U, N, ql, res=h2, out=out, stream=st)
+        self._keep = (ql, kl, off)
+        return out
+
+
+def sinusoidal_positional_encoding(length: int, E: int) -> np.ndarray:
+    """The toolkits' absolute PositionalEncoding table [length, E] float64:
+    sin(pos w_k) at column 2k, cos(pos w_k) at column 2k + 1, w_k =
+    10000^(-2k / E).  E even."""
+    if length < 0 or E <= 0 or E % 2:
+        raise ValueError(f"sinusoidal_positional_encoding: length {length}, E {E}")
+    pos = np.arange(length, dtype=np.float64)[:, None]
+    w = np.exp(np.arange(0, E, 2, dtype=np.float64) * -(np.log(10000.0) / E))[None, :]
+    pe = np.empty((length, E), np.float64)
+    pe[:, 0::2], pe[:, 1::2] = np.sin(pos * w), np.cos(pos * w)
+    return pe
+
+
+class TransformerDecoder:
+    """The attention decoder of a hybrid CTC / attention model, for
+    teacher-forced scoring of n-best lists (not for autoregressive decoding:
+    there is no K/V cache): embedding -> x * sqrt(E) + sinusoidal positional
+    encoding (the toolkits' PositionalEncoding) -> TransformerDecoderLayers ->
+    optional final LayerNorm (the toolkits' after_norm) -> Linear with
+    log-softmax (asr_linear_fwd, EPI_BIAS_LOGSOFTMAX) -> asr_token_score.
+    The embedding rows are gathered, scaled and offset ON THE HOST (float64,
+    rounded to fp32 once) and uploaded as [U*N, E]: there is no kernel for
+    that.  embedding [V, E]; w_out [E, V] in the [in][out] layout, b_out [V].
+    A right-to-left decoder (reverse_weight) is not built."""
+
+    def __init__(self, embedding, layers: Sequence[TransformerDecoderLayer], w_out, b_out=None,
+                 final_norm: Optional[LayerNorm] = None, scale_embedding: bool = True,
+                 positional_encoding: bool = True):
+        self.emb = np.ascontiguousarray(embedding, dtype=np.float32)
+        self.V, self.E = self.emb.shape
+        self.layers = list(layers)
+        if not self.layers or any(l.E != self.E for l in self.layers):
+            raise ValueError("TransformerDecoder: needs at least one layer, all over the embedding's E")
+        if final_norm is not None and final_norm.N != self.E:
+            raise ValueError("TransformerDecoder: final_norm is not over E")
+        w_out = np.asarray(w_out, np.float32)
+        if w_out.shape[0] != self.E:
+            raise ValueError(f"TransformerDecoder: w_out {w_out.shape} is not [E, V_out]")
+        self.V_out = w_out.shape[1]
+        self.w_out = DeviceMatrix.from_numpy(w_out)
+        self.b_out = DeviceMatrix.from_numpy((np.zeros(self.V_out, np.float32) if b_out is None
+                                              else np.asarray(b_out, np.float32)).reshape(self.V_out, 1))
+        self.final_norm = final_norm
+        self.emb_scale = float(np.sqrt(self.E)) if scale_embedding else 1.0
+        self._emb64 = self.emb.astype(np.float64) * self.emb_scale
+        self.positional_encoding = bool(positional_encoding)
+        self._scratch, self._keep = _Scratch(), None
+
+    @classmethod
+    def from_torch(cls, embedding, decoder, output, scale_embedding: bool = True,
+                   positional_encoding: bool = True) -> "TransformerDecoder":
+        """embedding a torch.nn.Embedding, decoder a torch.nn.TransformerDecoder
+        (its .layers and optional .norm), output the torch.nn.Linear to the
+        vocabulary."""
+        w, b = _torch_linear(output)
+        norm = getattr(decoder, "norm", None)
+        return cls(embedding.weight.detach().cpu().float().numpy(),
+                   [TransformerDecoderLayer.from_torch(l) for l in decoder.layers], w, b,
+                   None if norm is None else LayerNorm.from_torch(norm), scale_embedding, positional_encoding)
+
+    def embed(self, tokens: np.ndarray) -> np.ndarray:
+        """float32 [U*N, E] of int tokens [U][N]: emb[token] * sqrt(E) + PE[u], on the host."""
+        tokens = np.asarray(tokens)
+        U, N = tokens.shape
+        if tokens.size and (tokens.min() < 0 or tokens.max() >= self.V):
+            raise ValueError(f"TransformerDecoder: a token outside [0, {self.V})")
+        pe = (sinusoidal_positional_encoding(U, self.E) if self.positional_encoding
+              else np.zeros((U, self.E), np.float64))
+        x = np.empty((U, N, self.E), np.float32)
+        for u in range(U):                  # one token position at a time: the float64 rows stay in cache
+            x[u] = self._emb64[tokens[u]] + pe[u]
+        return x.reshape(U * N, self.E)
+
+    @staticmethod
+    def _group(utt, B: int):
+        """(hyp_offsets [B + 1], max_hyps) of a non-decreasing utt [N] in [0, B)."""
+        ut = np.asarray(utt, np.int64)
+        if ut.size and (ut.min() < 0 or ut.max() >= B or np.any(np.diff(ut) < 0)):
+            raise ValueError("TransformerDecoder: utt must be non-decreasing with every value in [0, B)")
+        cnt = np.bincount(ut, minlength=B)
+        return np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32), int(max(cnt.max(), 1))
+
+    def log_probs(self, tokens_in, lengths, utt, memory, T: int, B: int, enc_lengths=None, stream: int = 0):
+        """(logp DeviceMatrix [U*N, V_out], U, N): the log-softmax outputs for
+        decoder input tokens_in int [U][N] (token u of hypothesis n), of which
+        lengths[n] are real; hypothesis n reads the memory [T*B, E] of utterance
+        utt[n] (non-decreasing), enc_lengths[b] frames of it (None: T).  Rows
+        past lengths[n] hold the log-softmax of the output bias.  logp is a
+        buffer of this decoder, reused by its next call."""
+        tokens_in = np.asarray(tokens_in)
+        U, N = tokens_in.shape
+        E, st = self.E, stream or 0
+        if len(lengths) != N or len(utt) != N:
+            raise ValueError(f"TransformerDecoder: {len(lengths)} lengths / {len(utt)} utt for N = {N} hypotheses")
+        _need_matrix("TransformerDecoder: memory", memory, int(T) * int(B), E)
+        if memory.rows != T * B or memory.cols != E:
+            raise ValueError(f"TransformerDecoder: memory is {memory.rows} x {memory.cols}, not T*B x E = "
+                             f"{T * B} x {E}")
+        off, max_hyps = self._group(utt, B)
+        ql = device_lengths(np.minimum(np.maximum(np.asarray(lengths, np.int64), 0), U))
+        kl = _device_int32_exact("TransformerDecoder: enc_lengths", enc_lengths, B)
+        d_off = device_lengths(off)
+        sc = self._scratch                  # buffers of this decoder, reused by its next call of the same shape
+        x, y, kv = sc.get("x", U * N, E), sc.get("y", U * N, E), sc.get("kv", T * B, 2 * E)
+        x.toGpu(self.embed(tokens_in), st)
+        for layer in self.layers:
+            layer.cross_attn.project_memory(memory, T, B, out=kv, stream=st)
+            layer.forward(x, U, N, kv, T, B, ql, kl, d_off, max_hyps, out=y, stream=st)
+            x, y = y, x
+        if self.final_norm is not None:
+            self.final_norm.forward(x, U, N, ql, out=x, stream=st)
+        logp = sc.get("logp", U * N, self.V_out)
+        linear_fwd(x, self.w_out, self.b_out, logp, EPI_BIAS_LOGSOFTMAX, st)
+        self._keep = (ql, kl, d_off)
+        return logp, U, N
+
+    @staticmethod
+    def teacher_forcing(hyps: Sequence[Sequence[int]], sos: int, eos: int):
+        """(tokens_in [U][N], targets [U][N], lengths [N]) int32 for hypotheses
+        y: the input is sos + y, the target y + eos, U = max len(y) + 1; past a
+        hypothesis's len(y) + 1 tokens both hold eos."""
+        N = len(hyps)
+        U = max([len(y) for y in hyps] + [0]) + 1
+        tin, tgt = np.full((U, N), eos, np.int32), np.full((U, N), eos, np.int32)
+        for n, y in enumerate(hyps):
+            tin[0, n] = sos
+            tin[1:len(y) + 1, n] = y
+            tgt[:len(y), n] = y
+        return tin, tgt, np.array([len(y) + 1 for y in hyps], np.int32)
+
+    def score(self, hyps: Sequence[Sequence[int]], utt: Sequence[int], memory, T: int, B: int, enc_lengths=None,
+              sos: Optional[int] = None, eos: Optional[int] = None, stream: int = 0) -> np.ndarray:
+        """The attention log-likelihood of every hypothesis, fp64 [N]: the sum of
+        log p(y_u | sos, y_<u, memory of utt[n]) over y + eos (len(y) + 1 terms).
+        utt non-decreasing; sos / eos default to V - 1 (the toolkits' shared
+        <sos/eos>).  The [U*N, V] log-probs stay on the device."""
+        sos = self.V - 1 if sos is None else int(sos)
+        eos = self.V - 1 if eos is None else int(eos)
+        if not len(hyps):
+            return np.zeros(0, np.float64)
+        tin, tgt, ln = self.teacher_forcing(hyps, sos, eos)
+        logp, U, N = self.log_probs(tin, ln, utt, memory, T, B, enc_lengths, stream)
+        return token_score(logp, tgt, ln, U, N, self.V_out, stream=stream or 0)
+
+
+def attention_combine(nbest, att, ctc, ctc_weight: float):
+    """Per utterance [(labels, total, att, exact_ctc)] with total = att +
+    ctc_weight * exact_ctc, total descending, equal totals in their beam order
+    (a stable sort); att and ctc are flat over the hypotheses in nbest's order.
+    Host only."""
+    out, k = [], 0
+    for u in nbest:
+        rows = [(list(h[0]), float(att[k + j]) + ctc_weight * float(ctc[k + j]), float(att[k + j]),
+                 float(ctc[k + j])) for j, h in enumerate(u)]
+        k += len(u)
+        out.append(sorted(rows, key=lambda r: -r[1]))
+    return out
+
+
+def attention_rescore(nbest, decoder: TransformerDecoder, memory, T: int, B: int, enc_lengths=None,
+                      ctc_scores=None, ctc_weight: float = 0.5, sos: Optional[int] = None,
+                      eos: Optional[int] = None, stream: int = 0):
+    """Attention-decoder rescoring of an n-best (WeNet's attention_rescoring,
+    ESPnet's joint CTC / attention score): per utterance [(labels, total, att,
+    exact_ctc)], total = att + ctc_weight * exact_ctc descending, equal totals
+    in their beam order; an utterance with an empty beam gives [].  nbest: per
+    utterance a list of hypotheses whose first element is the label list
+    (CTCDecoder.beams / rescore, TransducerDecoder.beam_search); ctc_scores:
+    per utterance the first-pass score of each hypothesis (None: each
+    hypothesis's own second element).  memory [T*B, E] is the encoder output on
+    the device, enc_lengths its frames per utterance."""
+    if len(nbest) != B:
+        raise ValueError(f"attention_rescore: {len(nbest)} n-best lists for B = {B} utterances")
+    if ctc_scores is None:
+        ctc_scores = [[h[1] for h in u] for u in nbest]
+    if len(ctc_scores) != B or any(len(c) != len(u) for c, u in zip(ctc_scores, nbest)):
+        raise ValueError("attention_rescore: ctc_scores does not match the n-best")
+    hyps = [list(h[0]) for u in nbest for h in u]
+    if not hyps:
+        return [[] for _ in nbest]
+    utt = [b for b, u in enumerate(nbest) for _ in u]
+    att = decoder.score(hyps, utt, memory, T, B, enc_lengths, sos, eos, stream)
+    return attention_combine(nbest, att, [c for u in ctc_scores for c in u], ctc_weight)
 
 
 # ------------------------------------------------------------------ Conformer
@@ -2164,6 +2661,31 @@ class CTCDecoder:
             k += len(u)
             out.append(sorted(rows, key=lambda r: -r[1]))
         return out
+
+    def attention_rescore(self, max_hyps: int, decoder: "TransformerDecoder", memory, T: int, enc_lengths=None,
+                          ctc_weight: float = 0.5, sos: Optional[int] = None, eos: Optional[int] = None,
+                          stream: int = 0) -> List[List[Tuple[List[int], float, float, float]]]:
+        """The final beam re-ranked by an attention decoder: per utterance
+        [(labels, total, att, exact_ctc)], total = att + ctc_weight * exact_ctc
+        descending (equal totals keep their beam order).  exact_ctc is
+        rescore()'s exact score (ctc_score, one call for the batch); att is
+        decoder.score() of the hypothesis teacher-forced against the encoder
+        output memory [T*B, E] (device, T its frames, enc_lengths its frames
+        per utterance) — one grouped cross-attention launch per decoder layer
+        for the whole batch, the memory projected once per utterance.  After
+        decode() / decode_device() of whole utterances, as rescore()."""
+        if self._last is None:
+            raise AsrError(ASR_ERR_STATE, "CTCDecoder.attention_rescore: no whole-utterance decode yet")
+        d_emis, fs, us, ln, is_log = self._last
+        hyps = self.beams(max_hyps)
+        targets = [lab for u in hyps for lab, _ in u]
+        utt = [b for b, u in enumerate(hyps) for _ in u]
+        if not targets:
+            return [[] for _ in hyps]
+        exact = ctc_score(d_emis, targets, lengths=ln, utt=utt, is_log=is_log, blank=self.blank,
+                          shape=(self.T, self.B, self.V), frame_stride=fs, utt_stride=us, stream=stream)
+        att = decoder.score(targets, utt, memory, T, self.B, enc_lengths, sos, eos, stream)
+        return attention_combine(hyps, att, exact, ctc_weight)
 
     def mbr_rescore(self, max_hyps: int, scale: float = 1.0, lm: Optional["NGramLM"] = None, alpha: float = 0.0,
                     beta: float = 0.0, mapper=None, tokens=None,

@@ -548,8 +548,8 @@ int asr_glu_dwconv_fwd(const asr_glu_dwconv_desc* d, const float* d_u, long ldu,
  * heads*head_dim > 4096; heads or B > 65535 (grid dimensions); q_pos0 + Tq or
  * k_pos0 + Tk > INT_MAX - 64; Tq*B or Tk*B > INT_MAX.
  * Not built: relative-position or rotary terms and additive score biases;
- * the attention probabilities as an output; cross-attention with different
- * batch sizes; a split-bf16 variant; training. */
+ * the attention probabilities as an output; a split-bf16 variant; training.
+ * (Cross-attention with different batch sizes is asr_cross_attention_fwd.) */
 #define ASR_ATTN_KEY_BLOCK 64
 typedef struct asr_attn_desc {
     int heads, head_dim;   /* head_dim % 4 == 0, 4 .. 128; heads*head_dim <= 4096 */
@@ -561,6 +561,75 @@ typedef struct asr_attn_desc {
 int asr_attention_fwd(const asr_attn_desc* d, const float* d_q, long ldq, const float* d_k, long ldk,
                       const float* d_v, long ldv, const int32_t* d_lengths, float* d_out, long ldo,
                       int Tq, int q_pos0, int Tk, int k_pos0, int B, asr_stream_t s);
+
+/* Grouped cross-attention, the hot path of attention-decoder rescoring (WeNet's
+ * attention_rescoring, ESPnet's joint CTC / attention scoring): N = sum n_b
+ * hypotheses attend to the memories of B utterances, hypothesis n to its own
+ * utterance's only; no reference member.  The memory is not repeated per
+ * hypothesis: the kernel takes the map from utterance to hypotheses instead,
+ * d_hyp_offsets device int32 [B + 1], hypotheses off[b] .. off[b+1] - 1 belong
+ * to utterance b (so the hypotheses are ordered by utterance).
+ * Layout: row u*N + n of d_q and d_out is token u of hypothesis n (time-major
+ * with the hypotheses as the batch, as asr_attention_fwd lays out a causal
+ * self-attention over them), row j*B + b of d_k and d_v is frame j of utterance
+ * b; heads*head_dim floats per row, head h at columns [h*head_dim,
+ * (h+1)*head_dim), row strides ldq, ldk, ldv, ldo; columns >= heads*head_dim of
+ * a row of d_out are not touched.  K and V may be two column ranges of one
+ * [T*B, 2E] projection buffer.  d_out must not overlap Q, K or V.
+ *   out(u, n, h, :) = sum_j softmax_j(scale * q(u,n,h).k(j,b,h)) v(j,b,h)
+ * over j < klen[b], b the utterance of n.  No window: cross-attention is full.
+ * d_q_lengths device int32 [N] (tokens per hypothesis, clamped to [0, U], NULL =
+ * U), d_k_lengths device int32 [B] (frames per utterance, clamped to [0, T],
+ * NULL = T).  A row is exactly zero when u >= qlen[n] and when klen[b] = 0.  K
+ * and V past the length and Q past the length may hold NaN: zeros are selected
+ * there, never multiplied.  scale = 0 means 1 / sqrt(head_dim).
+ * Grid (ceil(U * max_hyps / 64), heads, B): max_hyps bounds off[b+1] - off[b]
+ * and only sizes the grid.  The queries of utterance b are numbered
+ * token-major, flat query f = u * cnt_b + j being token u of its j-th
+ * hypothesis; workgroup x owns f in [64 x, 64 x + 64), a wave 16 of them, a
+ * lane one, and workgroups with 64 x >= U * cnt_b exit at once.  The hypotheses
+ * of an utterance so share query tiles and every K / V block a tile stages.
+ * The kernel clamps what it reads from d_hyp_offsets: cnt_b into [0, max_hyps],
+ * the first hypothesis into [0, N - cnt_b].  A wrong map gives wrong numbers,
+ * never an access outside the buffers.  Rows of hypotheses that no utterance
+ * covers (after the clamps) are NOT written.
+ * Arithmetic: asr_attention_fwd's, unchanged (64-key blocks from frame 0
+ * ascending, both products on v_mfma_f32_16x16x4_f32, online softmax in fp32).
+ * A row's bits depend only on its query, its utterance's keys and values and
+ * the descriptor: never on which hypotheses share its tile, on N, B, U, T,
+ * max_hyps, strides or pointer alignment; they equal asr_attention_fwd's bits
+ * for that hypothesis alone (B = 1, Tq = qlen, Tk = klen, no window).
+ * One launch, asynchronous on s, no allocation, no workspace, no host sync.
+ * Checks, in this order, all before any HIP call — ASR_ERR_ARG: a NULL
+ * descriptor, d_q, d_k, d_v, d_out or d_hyp_offsets; non-positive U, N, T, B,
+ * heads or head_dim; max_hyps outside [1, N]; a stride below heads*head_dim; a
+ * scale that is not finite or < 0.  ASR_ERR_UNSUPPORTED: head_dim % 4 != 0 or
+ * > 128; heads*head_dim > 4096; heads or B > 65535 (grid dimensions); U*N or
+ * T*B > INT_MAX; U*max_hyps > INT_MAX - 64.
+ * Not built: a right-to-left decoder (reverse_weight); autoregressive decoding
+ * with a K/V cache; a compaction of dead query lanes (a lane past qlen[n] stays
+ * in its tile); GELU in the decoder's feed-forward. */
+typedef struct asr_xattn_desc {
+    int heads, head_dim;   /* limits of asr_attn_desc */
+    float scale;           /* 0 = 1/sqrt(head_dim); else finite, > 0 */
+} asr_xattn_desc;
+int asr_cross_attention_fwd(const asr_xattn_desc* d, const float* d_q, long ldq, const float* d_k, long ldk,
+                            const float* d_v, long ldv, const int32_t* d_q_lengths, const int32_t* d_k_lengths,
+                            const int32_t* d_hyp_offsets, int max_hyps, float* d_out, long ldo, int U, int N,
+                            int T, int B, asr_stream_t s);
+
+/* The teacher-forced score of N hypotheses from a log-softmax buffer that stays
+ * on the device:  d_scores[n] = sum over u < len[n] of
+ * d_logp[(u*N + n)*ld + d_tokens[u*N + n]], in fp64, tokens in ascending u (one
+ * thread per hypothesis, so the sum's order is fixed).  d_logp [U*N, V] fp32 with
+ * row stride ld >= V, d_tokens device int32 [U*N], d_lengths device int32 [N]
+ * clamped to [0, U] (NULL = U), d_scores device fp64 [N].  A token outside
+ * [0, V) contributes -inf and nothing is read for it; len[n] = 0 gives 0.
+ * One launch, asynchronous on s.  Checks, in this order, before any HIP call —
+ * ASR_ERR_ARG: NULL d_logp, d_tokens or d_scores; non-positive U, N or V;
+ * ld < V.  ASR_ERR_UNSUPPORTED: U*N > INT_MAX. */
+int asr_token_score(const float* d_logp, long ld, const int32_t* d_tokens, const int32_t* d_lengths,
+                    double* d_scores, int U, int N, int V, asr_stream_t s);
 
 /* LayerNorm over the N columns of each row of a time-major [T*B, N] buffer,
  * with an optional fused residual (torch.nn.LayerNorm semantics):
