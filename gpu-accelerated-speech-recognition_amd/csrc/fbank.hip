@@ -42,6 +42,7 @@
 // F = D (2C + 1) consecutive floats from base frame t - C of utterance b with
 // the blocks outside [0, frames_b) zeroed: one wave copies one row.
 #include "asr_internal.h"
+#include "fbank_tables.h"
 
 #include <climits>
 #include <cmath>
@@ -402,6 +403,61 @@ static void fb_dct(const asr_fbank_config* c, float* dct) {
     }
 }
 
+// The mel work items, the packed weights and the layout of the blob and of the
+// kernel's LDS (fbank_tables.h).
+void fb_build_tables(const asr_fbank_config* cfg, const float* mel, int wpb, FbTables* t) {
+    const int N = cfg->n_fft, M = N / 2, nb = M + 1, nm = cfg->n_mels, D = fb_dim(cfg);
+    // each filter's own bin range, weights packed; then work items: one per
+    // filter, the widest split in two until every lane of the mel stage has one
+    // (a filter's items stay adjacent and in bin order, so its sum has one order)
+    typedef FbMelItem Item;
+    std::vector<Item>& items = t->items;
+    std::vector<float>& packed = t->packed;
+    items.clear();
+    packed.clear();
+    for (int m = 0; m < nm; m++) {
+        int first = -1, last = -2;
+        for (int k = 0; k < nb; k++)
+            if (mel[(size_t)m * nb + k] != 0.f) {
+                if (first < 0) first = k;
+                last = k;
+            }
+        items.push_back({first < 0 ? 0 : first, first < 0 ? 0 : last - first + 1, (int)packed.size(), m});
+        for (int k = first; first >= 0 && k <= last; k++) packed.push_back(mel[(size_t)m * nb + k]);
+    }
+    const size_t cap = 64 * (size_t)((nm + 63) / 64);
+    while (items.size() < cap) {
+        size_t w = 0;
+        for (size_t i = 1; i < items.size(); i++)
+            if (items[i].c > items[w].c) w = i;
+        if (items[w].c < asr::FB_MEL_SPLIT_MIN) break;
+        const Item it = items[w];
+        const int c0 = (it.c + 1) / 2;
+        items[w].c = c0;
+        items.insert(items.begin() + w + 1, Item{it.s + c0, it.c - c0, it.o + c0, it.f});
+    }
+    std::vector<int>& idx = t->idx;
+    std::vector<int>& filt = t->filt;
+    idx.assign(3 * items.size(), 0);
+    filt.assign(2 * nm, 0);
+    for (size_t i = 0; i < items.size(); i++) {
+        idx[3 * i] = items[i].s; idx[3 * i + 1] = items[i].c; idx[3 * i + 2] = items[i].o;
+        if (filt[2 * items[i].f + 1]++ == 0) filt[2 * items[i].f] = (int)i;
+    }
+    t->n_items = (int)items.size();
+    t->nnz = (int)packed.size();
+    t->dct_lds = cfg->n_mfcc > 0 && nm * D <= asr::FB_DCT_LDS_FLOATS;
+    auto up4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
+    const size_t wave_floats = 2 * (size_t)(M + (M >> 4) + 1);
+    t->smem = (2 * (size_t)N + up4(t->nnz) + (t->dct_lds ? up4((size_t)nm * D) : 0) + wpb * wave_floats) * 4;
+    t->o_tw = up4(cfg->win_length);
+    t->o_melw = t->o_tw + 2 * (size_t)N;
+    t->o_melidx = t->o_melw + up4(t->nnz);
+    t->o_melfilt = t->o_melidx + up4(idx.size());
+    t->o_dct = t->o_melfilt + up4(filt.size());
+    t->total = t->o_dct + up4((size_t)nm * D);
+}
+
 }  // namespace asr
 
 struct asr_fbank {
@@ -450,54 +506,24 @@ int asr_fbank_create(const asr_fbank_config* cfg, asr_fbank_t** out) {
     asr::fb_window(cfg, win.data());
     asr::fb_mel(cfg, mel.data());
     if (cfg->n_mfcc > 0) asr::fb_dct(cfg, dct.data());
-    // each filter's own bin range, weights packed; then work items: one per
-    // filter, the widest split in two until every lane of the mel stage has one
-    // (a filter's items stay adjacent and in bin order, so its sum has one order)
-    struct Item { int s, c, o, f; };
-    std::vector<Item> items;
-    std::vector<float> packed;
-    for (int m = 0; m < nm; m++) {
-        int first = -1, last = -2;
-        for (int k = 0; k < nb; k++)
-            if (mel[(size_t)m * nb + k] != 0.f) {
-                if (first < 0) first = k;
-                last = k;
-            }
-        items.push_back({first < 0 ? 0 : first, first < 0 ? 0 : last - first + 1, (int)packed.size(), m});
-        for (int k = first; first >= 0 && k <= last; k++) packed.push_back(mel[(size_t)m * nb + k]);
-    }
-    const size_t cap = 64 * (size_t)((nm + 63) / 64);
-    while (items.size() < cap) {
-        size_t w = 0;
-        for (size_t i = 1; i < items.size(); i++)
-            if (items[i].c > items[w].c) w = i;
-        if (items[w].c < asr::FB_MEL_SPLIT_MIN) break;
-        const Item it = items[w];
-        const int c0 = (it.c + 1) / 2;
-        items[w].c = c0;
-        items.insert(items.begin() + w + 1, Item{it.s + c0, it.c - c0, it.o + c0, it.f});
-    }
-    std::vector<int> idx(3 * items.size()), filt(2 * nm, 0);
-    for (size_t i = 0; i < items.size(); i++) {
-        idx[3 * i] = items[i].s; idx[3 * i + 1] = items[i].c; idx[3 * i + 2] = items[i].o;
-        if (filt[2 * items[i].f + 1]++ == 0) filt[2 * items[i].f] = (int)i;
-    }
-    h->n_items = (int)items.size();
-    h->nnz = (int)packed.size();
-    h->dct_lds = cfg->n_mfcc > 0 && nm * D <= asr::FB_DCT_LDS_FLOATS;
-    auto up4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
-    const size_t wave_floats = 2 * (size_t)(M + (M >> 4) + 1);
-    h->smem = (2 * (size_t)N + up4(h->nnz) + (h->dct_lds ? up4((size_t)nm * D) : 0) + h->wpb * wave_floats) * 4;
+    asr::FbTables tb;
+    asr::fb_build_tables(cfg, mel.data(), h->wpb, &tb);
+    const std::vector<float>& packed = tb.packed;
+    const std::vector<int>&idx = tb.idx, &filt = tb.filt;
+    h->n_items = tb.n_items;
+    h->nnz = tb.nnz;
+    h->dct_lds = tb.dct_lds;
+    h->smem = tb.smem;
     if (h->smem > 65536) {   // cannot happen with the limits above; never launch past the static budget
         delete h;
         return ASR_ERR_UNSUPPORTED;
     }
-    h->o_tw = up4(cfg->win_length);
-    h->o_melw = h->o_tw + 2 * (size_t)N;
-    h->o_melidx = h->o_melw + up4(h->nnz);
-    h->o_melfilt = h->o_melidx + up4(idx.size());
-    h->o_dct = h->o_melfilt + up4(filt.size());
-    const size_t total = h->o_dct + up4((size_t)nm * D);
+    h->o_tw = tb.o_tw;
+    h->o_melw = tb.o_melw;
+    h->o_melidx = tb.o_melidx;
+    h->o_melfilt = tb.o_melfilt;
+    h->o_dct = tb.o_dct;
+    const size_t total = tb.total;
     std::vector<float> blob(total, 0.f);
     std::copy(win.begin(), win.end(), blob.begin());
     const double pi = 3.14159265358979323846;

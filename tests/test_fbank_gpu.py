@@ -1,6 +1,6 @@
 """GPU numerics of the audio front end (asr_fbank_fwd / asr.FeatureFrontend).
 
-Reference: features() below, float64 numpy written from the semantics in
+Reference: features() of fbank_cases.py, float64 numpy written from the semantics in
 include/asr_amd.h (np.fft.rfft per frame, the float64 tables of
 test_fbank_cpu.py); its STFT piece is cross-checked against torch.stft
 (center=False) in float64 at win == n_fft, where the two conventions coincide.
@@ -14,7 +14,6 @@ mel band is far above log_floor.  Shapes: the smallest at which each part can
 go wrong (CASES).
 """
 import copy
-import ctypes
 import functools
 
 import numpy as np
@@ -22,18 +21,10 @@ import pytest
 import torch
 
 from conftest import asr, oracle
-from test_fbank_cpu import BASE, ref_dct, ref_mel, ref_window
+from fbank_cases import (ATOL, SENT, cfg, check_padding, features, features_fp32, num_frames, poisoned, preemphasis,
+                         ref_stft, ref_window, run, waves)
 
 pytestmark = pytest.mark.gpu
-ATOL = 2e-5
-SENT = -12345.0
-POISON = 1e30
-
-
-def cfg(sr, win, hop, n_fft, mels, mfcc, C, **kw):
-    return dict(BASE, sample_rate=float(sr), win_length=win, hop_length=hop, n_fft=n_fft, n_mels=mels,
-                f_max=sr / 2.0, n_mfcc=mfcc, n_context=C, **kw)
-
 
 # name -> (config, B, S, nsamples)
 CASES = {
@@ -54,135 +45,6 @@ CASES = {
 }
 
 
-def synth(sr, S, seed):
-    t = np.arange(S, dtype=np.float64) / sr
-    x = np.random.default_rng(seed).uniform(-0.5, 0.5, S)
-    x = x + 0.3 * np.sin(2 * np.pi * 440 * t) + 0.2 * np.sin(2 * np.pi * (1000 + 1500 * t) * t)
-    return x.astype(np.float32)
-
-
-@functools.lru_cache(maxsize=None)
-def waves(sr, B, S, seed0=0):
-    w = np.stack([synth(sr, S, seed0 + b) for b in range(B)])
-    w.setflags(write=False)
-    return w
-
-
-def num_frames(n, win, hop):
-    return 0 if n < win else 1 + (n - win) // hop
-
-
-def stack_context(base, frames, C):
-    """base [T, B, D] -> [T, B, D (2C+1)]: frames t-C .. t+C, zeros outside
-    [0, frames_b) and in rows t >= frames_b."""
-    T, B, D = base.shape
-    out = np.zeros((T, B, D * (2 * C + 1)), base.dtype)
-    for b in range(B):
-        for t in range(frames[b]):
-            for c in range(-C, C + 1):
-                if 0 <= t + c < frames[b]:
-                    out[t, b, (c + C) * D:(c + C + 1) * D] = base[t + c, b]
-    return out
-
-
-def ref_stft(y, c):
-    """Frames of the (pre-emphasised) float64 signal y: [frames, n_fft/2 + 1] complex."""
-    win, hop, n_fft = c["win_length"], c["hop_length"], c["n_fft"]
-    w = ref_window(c["window"], win)
-    nf = num_frames(len(y), win, hop)
-    return np.stack([np.fft.rfft(y[t * hop:t * hop + win] * w, n=n_fft) for t in range(nf)]) if nf else \
-        np.zeros((0, n_fft // 2 + 1), complex)
-
-
-def preemphasis(x, a):
-    y = np.asarray(x, np.float64).copy()
-    y[1:] -= a * np.asarray(x, np.float64)[:-1]
-    return y
-
-
-def features(c, wave, nsamples, T):
-    """The float64 reference: (out [T, B, F], frames [B])."""
-    B, S = wave.shape
-    ns = [S] * B if nsamples is None else list(nsamples)
-    mel = ref_mel(c["sample_rate"], c["n_fft"], c["n_mels"], c["f_min"], c["f_max"])
-    D = c["n_mfcc"] or c["n_mels"]
-    base = np.zeros((T, B, D))
-    frames = []
-    for b in range(B):
-        X = ref_stft(preemphasis(wave[b, :ns[b]], c["preemph"]), c)
-        P = X.real ** 2 + X.imag ** 2
-        e = np.log(np.maximum(P @ mel.T, c["log_floor"]))
-        if c["n_mfcc"]:
-            e = e @ ref_dct(c["n_mfcc"], c["n_mels"]).T
-        base[:len(e), b] = e
-        frames.append(len(e))
-    return stack_context(base, frames, c["n_context"]), np.asarray(frames, np.int32)
-
-
-def features_fp32(c, wave, nsamples, T):
-    """The same chain in fp32 on the CPU: torch.fft.rfft float32, the library's
-    fp32 tables, fp32 sums."""
-    fe = asr.FeatureFrontend(**c)
-    win, mel, dct = (None if a is None else torch.from_numpy(a) for a in fe.host_tables())
-    fe.close()
-    B, S = wave.shape
-    ns = [S] * B if nsamples is None else list(nsamples)
-    D = c["n_mfcc"] or c["n_mels"]
-    base = np.zeros((T, B, D), np.float32)
-    frames = []
-    x = torch.from_numpy(np.array(wave))
-    for b in range(B):
-        nf = num_frames(ns[b], c["win_length"], c["hop_length"])
-        frames.append(nf)
-        if not nf:
-            continue
-        y = x[b, :ns[b]].clone()
-        y[1:] -= np.float32(c["preemph"]) * x[b, :ns[b] - 1]
-        fr = y.unfold(0, c["win_length"], c["hop_length"])[:nf] * win
-        X = torch.fft.rfft(fr, n=c["n_fft"])
-        e = torch.log(torch.clamp((X.real ** 2 + X.imag ** 2) @ mel.T, min=c["log_floor"]))
-        if c["n_mfcc"]:
-            e = e @ dct.T
-        base[:nf, b] = e.numpy()
-    return stack_context(base, frames, c["n_context"]), np.asarray(frames, np.int32)
-
-
-def poisoned(wave, nsamples, ldw):
-    """wave in a [B, ldw] buffer; everything an utterance does not own is 1e30."""
-    B, S = wave.shape
-    buf = np.full((B, ldw), POISON, np.float32)
-    for b in range(B):
-        n = S if nsamples is None else nsamples[b]
-        buf[b, :n] = wave[b, :n]
-    return buf
-
-
-def run(c, wave, nsamples=None, T=None, ldw=None, ldo=None, stream=0, fe=None, bufs=None):
-    """asr_fbank_fwd on a sentinel-filled output: (out [T, B, ldo], frames [B])."""
-    own = fe is None
-    fe = fe or asr.FeatureFrontend(**c)
-    B, S = wave.shape
-    ldw = ldw or S
-    T = T or max(1, fe.num_frames(S))
-    F = fe.feature_dim
-    ldo = ldo or F
-    if bufs is None:
-        dw = asr.DeviceMatrix.from_numpy(poisoned(wave, nsamples, ldw))
-        dn = None if nsamples is None else asr.device_lengths(nsamples)
-        out = asr.DeviceMatrix.from_numpy(np.full((T * B, ldo), SENT, np.float32))
-        frames = asr.DeviceBytes(4 * B)
-        work = asr.DeviceBytes(max(16, fe.workspace_bytes(T, B)))
-        bufs = (dw, dn, out, frames, work)
-    dw, dn, out, frames, work = bufs
-    asr.check(asr.lib().asr_fbank_fwd(fe.h, dw.ptr, ldw, dn.ptr if dn else None, B, S, out.ptr, ldo, frames.ptr,
-                                      work.ptr, T, stream), "asr_fbank_fwd")
-    asr.synchronize()
-    got = out.toCpu().reshape(T, B, ldo), asr.device_int32(frames, B)
-    if own:
-        fe.close()
-    return got
-
-
 def close(got, ref, what=""):
     err = np.abs(np.asarray(got, np.float64) - ref)
     print(f"{what} max err {err.max():.3e} (max err / (1 + |ref|) {(err / (1 + np.abs(ref))).max():.3e})")
@@ -198,19 +60,6 @@ def case(name):
     ref, frames = features(c, wave, ns, T)
     ref.setflags(write=False)
     return c, wave, ns, T, ref, frames
-
-
-def check_padding(got, frames, c):
-    """Rows t >= frames_b and context blocks outside the utterance are zero bits."""
-    D, C = c["n_mfcc"] or c["n_mels"], c["n_context"]
-    bits = np.ascontiguousarray(got).view(np.uint32)
-    T, B, _ = got.shape
-    for b in range(B):
-        assert not bits[frames[b]:, b].any(), b
-        for t in range(frames[b]):
-            for k in range(-C, C + 1):
-                if not 0 <= t + k < frames[b]:
-                    assert not bits[t, b, (k + C) * D:(k + C + 1) * D].any(), (t, b, k)
 
 
 def test_reference_stft_matches_torch_stft():
