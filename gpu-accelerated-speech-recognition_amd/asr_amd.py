@@ -52,8 +52,17 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           cross-attention over each hypothesis's own
                                           utterance (asr_cross_attention_fwd) and
                                           the token scores (asr_token_score); the
-                                          embedding is gathered on the host; no
-                                          reference member
+                                          embedding is gathered on the device
+                                          (asr_embed_fwd); no reference member
+    TransformerDecoder.beam_search(memory, T, B, enc_lengths, beam=10) / .greedy(...)
+    TransformerDecoder.begin(...) / .step(state) / .prune(state, logp)
+                                          attention-decoder beam search on a K/V
+                                          cache read through an ancestry table
+                                          (asr_decode_attention_fwd), the exact
+                                          top-K prune and reorder in one launch
+                                          (asr_attn_beam_step, host twin
+                                          asr_attn_beam_step_host); no reference
+                                          member
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
                                           waveform -> log-mel / MFCC features
                                           (asr_fbank_*); no reference member
@@ -133,6 +142,7 @@ EXPORTS = [
     "asr_conv2d_out_frames", "asr_conv2d_out_feats", "asr_conv2d_fwd",
     "asr_attention_fwd", "asr_layernorm_fwd", "asr_mask_rows",
     "asr_cross_attention_fwd", "asr_token_score",
+    "asr_decode_attention_fwd", "asr_embed_fwd", "asr_attn_beam_step", "asr_attn_beam_step_host",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
     "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
@@ -266,6 +276,12 @@ def lib() -> ctypes.CDLL:
         "asr_cross_attention_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp,
                                     _i, _vp, ctypes.c_long, _i, _i, _i, _i, _vp],
         "asr_token_score": [_vp, ctypes.c_long, _vp, _vp, _vp, _i, _i, _i, _vp],
+        "asr_decode_attention_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp,
+                                     ctypes.c_long, _vp, _vp, ctypes.c_long, _i, _i, _i, _vp],
+        "asr_embed_fwd": [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, ctypes.c_double, _vp, ctypes.c_long,
+                          _i, _i, _i, _i, _vp],
+        "asr_attn_beam_step": [_vp, _vp, ctypes.c_long] + [_vp] * 12,
+        "asr_attn_beam_step_host": [_vp, _vp, ctypes.c_long] + [_vp] * 11,
         "asr_fbank_num_frames": [_vp, _i],
         "asr_fbank_feature_dim": [_vp],
         "asr_fbank_host_tables": [_vp, _vp, _vp, _vp],
@@ -1425,6 +1441,7 @@ class MultiheadAttention:
             raise ValueError(f"MultiheadAttention: window chunk {chunk}, left {left}, right {right}")
         self.E, self.heads = E, heads
         self.desc = attn_desc(heads, hd, 0.0, chunk, left, right)
+        self._xdesc = XAttnDesc(heads, hd, 0.0)      # the same heads and scale, for step()
         arr = lambda a, shape: (np.zeros(shape, np.float32) if a is None   # noqa: E731
                                 else np.asarray(a, np.float32).reshape(shape))
         self.w_in, self.b_in = DeviceMatrix.from_numpy(arr(w_in, (E, 3 * E))), DeviceMatrix.from_numpy(
@@ -1473,6 +1490,43 @@ class MultiheadAttention:
         if zero_padding and lengths is not None:
             mask_rows(out, T, B, E, lengths, st)
         self._keep = lengths
+        return out
+
+    def step(self, x, N: int, cache, step: int, anc, out=None, stream: int = 0):
+        """One autoregressive step of causal self-attention: x [N, E] is the
+        row of step `step` of N hypotheses.  One fused QKV GEMM writes the row
+        in place at rows step*N .. step*N + N - 1 of cache [max_len*N, 3E] (Q,
+        K and V columns: no copy appends K / V), then asr_decode_attention_fwd
+        over keys 0 .. step through the ancestry table anc (device int32
+        [max_len][N], or a host table that is validated): entry [j][n] is the
+        slot whose row j holds hypothesis n's key, so a beam reorder never
+        moves the cache.  The layer must be causal over its whole history
+        (chunk 1, left -1, right 0: ValueError otherwise).  Returns out [N, E]
+        (a buffer of this layer unless given)."""
+        E, N, step, st = self.E, int(N), int(step), stream or 0
+        if (self.desc.chunk, self.desc.left, self.desc.right) != (1, -1, 0):
+            raise ValueError("MultiheadAttention.step: the layer must be causal over its whole history (chunk 1, "
+                             "left -1, right 0); a limited window is not built for the cache")
+        _need_matrix("MultiheadAttention.step: x", x, N, E)
+        if x.rows != N or x.cols != E:
+            raise ValueError(f"MultiheadAttention.step: x is {x.rows} x {x.cols}, not N x E = {N} x {E}")
+        if cache.cols != 3 * E or step < 0 or (step + 1) * N > cache.rows:
+            raise ValueError(f"MultiheadAttention.step: cache is {cache.rows} x {cache.cols}; step {step} needs "
+                             f"{(step + 1) * N} x {3 * E}")
+        if _is_device(anc):
+            _need_int32("MultiheadAttention.step: anc", anc, (step + 1) * N)
+        else:                                # a host table is validated before the first device call
+            anc = np.asarray(anc)[:step + 1]
+            _host_table("MultiheadAttention.step: anc", anc, step + 1, N, 0, N)
+        if out is not None:
+            _need_matrix("MultiheadAttention.step: out", out, N, E)
+        ctx = self._scratch.get("sctx", N, E)
+        out = self._scratch.get("sout", N, E) if out is None else out
+        row = RowView(cache, step * N, N)
+        linear_fwd(x, self.w_in, self.b_in, row, EPI_BIAS, st)
+        decode_attention_fwd(ColumnView(row, 0), ColumnView(cache, E), ColumnView(cache, 2 * E), ctx, N, step + 1, N,
+                             self._xdesc, anc, ldc=N, stream=st)
+        linear_fwd(ctx, self.w_out, self.b_out, out, EPI_BIAS, st)
         return out
 
 
@@ -1640,6 +1694,180 @@ def token_score(logp, tokens, lengths, U: int, N: int, V: int, ld: Optional[int]
     return _download(d_out, N, np.float64, stream)
 
 
+# ----------------------------------- attention decoder (autoregressive step)
+ATTN_BEAM_MAX_K = 16   # ASR_ATTN_BEAM_MAX_K
+
+
+class AttnBeamDesc(ctypes.Structure):
+    """asr_attn_beam_desc (include/asr_amd.h)."""
+    _fields_ = [("B", _i), ("K", _i), ("V", _i), ("max_len", _i), ("step", _i), ("eos", _i)]
+
+
+def attn_beam_desc(B: int, K: int, V: int, max_len: int, step: int, eos: int) -> AttnBeamDesc:
+    return AttnBeamDesc(B, K, V, max_len, step, eos)
+
+
+class RowView:
+    """Rows [row0, row0 + rows) of a device matrix, without owning them."""
+
+    def __init__(self, m, row0: int, rows: int):
+        if row0 < 0 or rows < 1 or row0 + rows > m.rows:
+            raise ValueError(f"RowView: rows [{row0}, {row0 + rows}) of a buffer of {m.rows}")
+        self.ptr, self.rows, self.cols, self._keep = m.ptr + 4 * row0 * m.cols, int(rows), m.cols, m
+        self.nbytes = 4 * self.rows * self.cols
+
+
+class Int32View:
+    """n int32 of a device buffer from element first on, without owning them."""
+
+    def __init__(self, d, first: int, n: int):
+        if first < 0 or n < 0 or 4 * (first + n) > d.nbytes:
+            raise ValueError(f"Int32View: elements [{first}, {first + n}) of a buffer of {d.nbytes} bytes")
+        self.ptr, self.nbytes, self._keep = d.ptr + 4 * first, 4 * n, d
+
+
+def _is_device(a) -> bool:
+    return hasattr(a, "ptr") and hasattr(a, "nbytes")
+
+
+def _host_table(what: str, a, rows: int, cols: int, lo: int, hi: int):
+    """None for a device buffer (its size checked); a host table validated
+    (shape, every value in [lo, hi)) as a contiguous int32 array to upload."""
+    if _is_device(a):
+        _need_int32(what, a, rows * cols)
+        return None
+    t = np.asarray(a)
+    if t.shape != (rows, cols) and not (rows == 1 and t.shape == (cols,)):
+        raise ValueError(f"{what}: shape {t.shape}, not ({rows}, {cols})")
+    if t.size and (t.min() < lo or t.max() >= hi):
+        raise ValueError(f"{what}: a value outside [{lo}, {hi})")
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def decode_attention_fwd(q, k, v, out, N: int, Tk: int, S: int, desc: XAttnDesc, cols, ldc: int = 0, lengths=None,
+                         ldq: Optional[int] = None, ldk: Optional[int] = None, ldv: Optional[int] = None,
+                         ldo: Optional[int] = None, stream: int = 0):
+    """One query per hypothesis over a K/V cache (asr_decode_attention_fwd):
+    q, out [N, >= E], k, v [Tk*S, >= E] (key j of column c: row j*S + c); E =
+    heads*head_dim; anything with .ptr, .rows and .cols (the row stride unless
+    ld* is given).  cols: with ldc = 0 the column of each hypothesis, [N]; with
+    ldc >= N the [Tk][ldc] table whose entry [j][n] is the column of hypothesis
+    n's key j.  A host table is validated (every value in [0, S)) and uploaded;
+    a device buffer (DeviceBytes, Int32View) is used as it is and clamped by
+    the kernel.  lengths [N]: None (= Tk), a host sequence or a device buffer.
+    Raises ValueError before any device call if a buffer is smaller than what
+    the call will touch."""
+    N, Tk, S, ldc = int(N), int(Tk), int(S), int(ldc)
+    E = int(desc.heads) * int(desc.head_dim)
+    if N < 1 or Tk < 1 or S < 1:
+        raise ValueError(f"decode_attention_fwd: N {N}, Tk {Tk}, S {S}")
+    if ldc != 0 and ldc < N:
+        raise ValueError(f"decode_attention_fwd: ldc {ldc} is neither 0 nor >= N = {N}")
+    _need_matrix("decode_attention_fwd: q", q, N, E, ldq)
+    _need_matrix("decode_attention_fwd: k", k, Tk * S, E, ldk)
+    _need_matrix("decode_attention_fwd: v", v, Tk * S, E, ldv)
+    _need_matrix("decode_attention_fwd: out", out, N, E, ldo)
+    if cols is None:
+        raise ValueError("decode_attention_fwd: cols is required")
+    if ldc != 0 and _is_device(cols):
+        _need_int32("decode_attention_fwd: cols", cols, (Tk - 1) * ldc + N)
+        host_cols = None
+    else:
+        host_cols = _host_table("decode_attention_fwd: cols", cols, Tk if ldc else 1, ldc if ldc else N, 0, S)
+    if lengths is not None and not _is_device(lengths) and len(lengths) != N:
+        raise ValueError(f"decode_attention_fwd: {len(lengths)} lengths, not N = {N}")
+    _need_int32("decode_attention_fwd: lengths", lengths if _is_device(lengths) else None, N)
+    d_cols = cols if host_cols is None else _upload(host_cols, stream)
+    ln = lengths if lengths is None or _is_device(lengths) else device_lengths(lengths)
+    ld = lambda m, given: int(m.cols if given is None else given)   # noqa: E731
+    check(lib().asr_decode_attention_fwd(ctypes.byref(desc), q.ptr, ld(q, ldq), k.ptr, ld(k, ldk), v.ptr, ld(v, ldv),
+                                         d_cols.ptr, ldc, ln.ptr if ln is not None else None, out.ptr, ld(out, ldo),
+                                         N, Tk, S, stream), "asr_decode_attention_fwd")
+    out._dattn_keep = (d_cols, ln)       # host tables were uploaded here: keep them until out goes
+    return out
+
+
+def embed_fwd(emb, pe, tokens, pos, out, R: int, E: int, V: int, P: int = 0, scale: float = 1.0,
+              ldo: Optional[int] = None, stream: int = 0):
+    """out[r] = fp32(float64(emb[tokens[r]]) * scale + pe[pos[r]]) on the
+    device (asr_embed_fwd): emb a device fp32 [V, E] matrix, pe a device fp64
+    [P, E] buffer (DeviceBytes) or None (0), tokens / pos device int32 [R] or
+    host sequences (uploaded as they are: a token outside [0, V) or a position
+    outside [0, P) gives a zero row), out [R, >= E]."""
+    R, E, V, P = int(R), int(E), int(V), int(P)
+    if R < 1 or E < 1 or V < 1:
+        raise ValueError(f"embed_fwd: R {R}, E {E}, V {V}")
+    _need_matrix("embed_fwd: emb", emb, V, E)
+    _need_matrix("embed_fwd: out", out, R, E, ldo)
+    if pe is not None and (P < 1 or pe.nbytes < 8 * P * E):
+        raise ValueError(f"embed_fwd: pe needs {P} x {E} float64, got {pe.nbytes} bytes")
+    if pe is not None and pos is None:
+        raise ValueError("embed_fwd: pe needs pos")
+    if tokens is None:
+        raise ValueError("embed_fwd: tokens is required")
+    for what, a in (("tokens", tokens), ("pos", pos)):
+        if _is_device(a):
+            _need_int32(f"embed_fwd: {what}", a, R)
+        elif a is not None and len(a) != R:
+            raise ValueError(f"embed_fwd: {len(a)} {what}, not R = {R}")
+    up = lambda a: a if a is None or _is_device(a) else device_lengths(a)   # noqa: E731
+    tk, ps = up(tokens), up(pos)
+    check(lib().asr_embed_fwd(emb.ptr, emb.cols, pe.ptr if pe is not None else None, E, tk.ptr,
+                              ps.ptr if ps is not None else None, float(scale), out.ptr,
+                              int(out.cols if ldo is None else ldo), R, E, V, P, stream), "asr_embed_fwd")
+    out._embed_keep = (tk, ps)
+    return out
+
+
+def attn_beam_step(desc: AttnBeamDesc, logp, scores, finished, tokens_in, anc_in, scores_out, finished_out, parent,
+                   token, tokens_out, anc_out, all_finished, ld: Optional[int] = None, stream: int = 0) -> None:
+    """One prune of the attention beam search on the device
+    (asr_attn_beam_step): every argument a device buffer (logp a matrix [N, >=
+    V], the rest anything with .ptr and .nbytes), sizes checked here."""
+    N, rows = desc.B * desc.K, desc.max_len * desc.B * desc.K
+    if N < 1 or rows < 1:
+        raise ValueError(f"attn_beam_step: B {desc.B}, K {desc.K}, max_len {desc.max_len}")
+    _need_matrix("attn_beam_step: logp", logp, N, max(int(desc.V), 1), ld)
+    for what, d, n, width in (("scores", scores, N, 8), ("finished", finished, N, 4), ("tokens_in", tokens_in, rows, 4),
+                              ("anc_in", anc_in, rows, 4), ("scores_out", scores_out, N, 8),
+                              ("finished_out", finished_out, N, 4), ("parent", parent, N, 4), ("token", token, N, 4),
+                              ("tokens_out", tokens_out, rows, 4), ("anc_out", anc_out, rows, 4),
+                              ("all_finished", all_finished, 1, 4)):
+        if d is None or d.nbytes < width * n:
+            raise ValueError(f"attn_beam_step: {what} needs {width * n} bytes")
+    check(lib().asr_attn_beam_step(ctypes.byref(desc), logp.ptr, int(logp.cols if ld is None else ld), scores.ptr,
+                                   finished.ptr, tokens_in.ptr, anc_in.ptr, scores_out.ptr, finished_out.ptr,
+                                   parent.ptr, token.ptr, tokens_out.ptr, anc_out.ptr, all_finished.ptr, stream),
+          "asr_attn_beam_step")
+
+
+def attn_beam_step_host(desc: AttnBeamDesc, logp, scores, finished, tokens_in, anc_in):
+    """The same prune on the host (asr_attn_beam_step_host), the CPU path:
+    logp float32 [N, V], scores float64 [N], finished int [N], tokens_in /
+    anc_in int [max_len][N].  Returns (scores, finished, parent, token,
+    tokens_out, anc_out, live): the out tables start as copies of the in tables
+    (rows past step + 1 keep them), live = the live unfinished slots."""
+    N, L = desc.B * desc.K, desc.max_len
+    logp = np.ascontiguousarray(logp, dtype=np.float32)
+    if logp.ndim != 2 or logp.shape[0] != N or logp.shape[1] < max(desc.V, 1):
+        raise ValueError(f"attn_beam_step_host: logp {logp.shape}, not [{N}, >= {desc.V}]")
+    scores = np.ascontiguousarray(scores, dtype=np.float64)
+    finished = np.ascontiguousarray(finished, dtype=np.int32)
+    tokens_in = np.ascontiguousarray(tokens_in, dtype=np.int32)
+    anc_in = np.ascontiguousarray(anc_in, dtype=np.int32)
+    if scores.shape != (N,) or finished.shape != (N,):
+        raise ValueError(f"attn_beam_step_host: scores {scores.shape} / finished {finished.shape}, not ({N},)")
+    if tokens_in.shape != (L, N) or anc_in.shape != (L, N):
+        raise ValueError(f"attn_beam_step_host: tables {tokens_in.shape} / {anc_in.shape}, not ({L}, {N})")
+    so, fo = np.empty(N, np.float64), np.empty(N, np.int32)
+    par, tok = np.empty(N, np.int32), np.empty(N, np.int32)
+    tout, aout, live = tokens_in.copy(), anc_in.copy(), np.zeros(1, np.int32)
+    check(lib().asr_attn_beam_step_host(ctypes.byref(desc), _ptr(logp), logp.shape[1], _ptr(scores), _ptr(finished),
+                                        _ptr(tokens_in), _ptr(anc_in), _ptr(so), _ptr(fo), _ptr(par), _ptr(tok),
+                                        _ptr(tout), _ptr(aout), _ptr(live)), "asr_attn_beam_step_host")
+    return so, fo, par, tok, tout, aout, int(live[0])
+
+
 class CrossAttention:
     """torch.nn.MultiheadAttention(E, heads) as the encoder-decoder attention
     of a rescoring decoder: N hypotheses (the queries' batch) attend to the
@@ -1736,6 +1964,45 @@ class CrossAttention:
         if zero_padding and q_lengths is not None:
             mask_rows(out, U, N, E, q_lengths, st)
         self._keep = (q_lengths, k_lengths, hyp_offsets)
+        return out
+
+    def step(self, x, N: int, kv, T: int, B: int, hyp_offsets, max_hyps: Optional[int] = None, k_lengths=None,
+             out=None, stream: int = 0):
+        """One autoregressive step: the single rows x [N, E] of N hypotheses
+        (ordered by utterance) attend to kv = project_memory(...) [T*B, 2E],
+        computed once per search; hyp_offsets [B + 1] and k_lengths [B] as
+        forward()'s.  This is forward() at U = 1 without q_lengths and without
+        the row mask: asr_cross_attention_fwd, which stages an utterance's K /
+        V once for all of its hypotheses, measured 2.4 to 5 times faster here
+        than asr_decode_attention_fwd with ldc = 0, which re-reads them per
+        hypothesis.  Returns out [N, E] (a buffer of
+        this layer unless given); a hypothesis of an utterance with no frames
+        gets the output bias."""
+        E, N, st = self.E, int(N), stream or 0
+        _need_matrix("CrossAttention.step: x", x, N, E)
+        if x.rows != N or x.cols != E:
+            raise ValueError(f"CrossAttention.step: x is {x.rows} x {x.cols}, not N x E = {N} x {E}")
+        _need_matrix("CrossAttention.step: kv", kv, int(T) * int(B), 2 * E)
+        if kv.cols != 2 * E:
+            raise ValueError(f"CrossAttention.step: kv has {kv.cols} columns, not 2E = {2 * E}")
+        if out is not None:
+            _need_matrix("CrossAttention.step: out", out, N, E)
+        if hyp_offsets is None:
+            raise ValueError("CrossAttention.step: hyp_offsets is required")
+        for what, a, n in (("hyp_offsets", hyp_offsets, int(B) + 1), ("k_lengths", k_lengths, int(B))):
+            if _is_device(a):
+                _need_int32(f"CrossAttention.step: {what}", a, n)
+            elif a is not None and len(a) != n:
+                raise ValueError(f"CrossAttention.step: {len(a)} {what}, not {n}")
+        off = hyp_offsets if _is_device(hyp_offsets) else device_lengths(hyp_offsets)
+        kl = k_lengths if k_lengths is None or _is_device(k_lengths) else device_lengths(k_lengths)
+        qp, ctx = self._scratch.get("sq", N, E), self._scratch.get("sctx", N, E)
+        out = self._scratch.get("sout", N, E) if out is None else out
+        linear_fwd(x, self.w_q, self.b_q, qp, EPI_BIAS, st)
+        cross_attention_fwd(qp, ColumnView(kv, 0), ColumnView(kv, E), ctx, 1, N, T, B, self.desc, off,
+                            N if max_hyps is None else max_hyps, None, kl, stream=st)
+        linear_fwd(ctx, self.w_out, self.b_out, out, EPI_BIAS, st)
+        self._keep = (off, kl)
         return out
 
 
@@ -1846,6 +2113,51 @@ class TransformerDecoderLayer:
         self._keep = (ql, kl, off)
         return out
 
+    def step(self, x, N: int, cache, step: int, anc, kv, T: int, B: int, hyp_offsets, max_hyps: Optional[int] = None,
+             k_lengths=None, out=None, stream: int = 0) -> DeviceMatrix:
+        """forward() for the single row of step `step` of N hypotheses, on the
+        K/V cache: MultiheadAttention.step over cache [max_len*N, 3E] through
+        the ancestry table anc, CrossAttention.step over kv with hyp_offsets
+        [B + 1] and the utterances' frames k_lengths [B], the feed-forward.
+        Returns out (a new DeviceMatrix [N, E] unless given; not x)."""
+        E, F, M, st = self.E, self.F, int(N), stream or 0
+        _need_matrix("TransformerDecoderLayer.step: x", x, M, E)
+        if x.rows != M or x.cols != E:
+            raise ValueError(f"TransformerDecoderLayer.step: x is {x.rows} x {x.cols}, not N x E = {M} x {E}")
+        _need_matrix("TransformerDecoderLayer.step: kv", kv, int(T) * int(B), 2 * E)
+        if cache.cols != 3 * E or step < 0 or (int(step) + 1) * M > cache.rows:
+            raise ValueError(f"TransformerDecoderLayer.step: cache is {cache.rows} x {cache.cols}; step {step} needs "
+                             f"{(int(step) + 1) * M} x {3 * E}")
+        if out is not None:
+            _need_matrix("TransformerDecoderLayer.step: out", out, M, E)
+        if out is x:
+            raise ValueError("TransformerDecoderLayer.step: out must not be x")
+        sc = self._scratch
+        h, h2, ff = sc.get("sh", M, E), sc.get("sh2", M, E), sc.get("sff", M, F)
+        add = lambda a, b, z: check(lib().asr_matadd(a.ptr, b.ptr, z.ptr, M, E, 1.0, st), "asr_matadd")   # noqa: E731
+        own = lambda q: self.self_attn.step(q, M, cache, step, anc, stream=st)   # noqa: E731
+        cross = lambda q: self.cross_attn.step(q, M, kv, T, B, hyp_offsets, max_hyps, k_lengths,   # noqa: E731
+                                               stream=st)
+        out = DeviceMatrix(M, E) if out is None else out
+        if self.norm_first:
+            n = sc.get("sn", M, E)
+            self.norm1.forward(x, 1, M, None, out=n, stream=st)
+            add(x, own(n), h)
+            self.norm2.forward(h, 1, M, None, out=n, stream=st)
+            add(h, cross(n), h2)
+            self.norm3.forward(h2, 1, M, None, out=n, stream=st)
+            linear_fwd(n, self.w1, self.b1, ff, EPI_BIAS_RELU, st)
+            linear_fwd(ff, self.w2, self.b2, n, EPI_BIAS, st)
+            add(h2, n, out)
+        else:
+            self.norm1.forward(own(x), 1, M, None, res=x, out=h, stream=st)
+            self.norm2.forward(cross(h), 1, M, None, res=h, out=h2, stream=st)
+            f2 = sc.get("sf2", M, E)
+            linear_fwd(h2, self.w1, self.b1, ff, EPI_BIAS_RELU, st)
+            linear_fwd(ff, self.w2, self.b2, f2, EPI_BIAS, st)
+            self.norm3.forward(f2, 1, M, None, res=h2, out=out, stream=st)
+        return out
+
 
 def sinusoidal_positional_encoding(length: int, E: int) -> np.ndarray:
     """The toolkits' absolute PositionalEncoding table [length, E] float64:
@@ -1861,16 +2173,18 @@ def sinusoidal_positional_encoding(length: int, E: int) -> np.ndarray:
 
 
 class TransformerDecoder:
-    """The attention decoder of a hybrid CTC / attention model, for
-    teacher-forced scoring of n-best lists (not for autoregressive decoding:
-    there is no K/V cache): embedding -> x * sqrt(E) + sinusoidal positional
-    encoding (the toolkits' PositionalEncoding) -> TransformerDecoderLayers ->
-    optional final LayerNorm (the toolkits' after_norm) -> Linear with
-    log-softmax (asr_linear_fwd, EPI_BIAS_LOGSOFTMAX) -> asr_token_score.
-    The embedding rows are gathered, scaled and offset ON THE HOST (float64,
-    rounded to fp32 once) and uploaded as [U*N, E]: there is no kernel for
-    that.  embedding [V, E]; w_out [E, V] in the [in][out] layout, b_out [V].
-    A right-to-left decoder (reverse_weight) is not built."""
+    """The attention decoder of a hybrid CTC / attention model: embedding ->
+    x * sqrt(E) + sinusoidal positional encoding (the toolkits'
+    PositionalEncoding; asr_embed_fwd, whose rows equal embed()'s float64 host
+    gather bit for bit) -> TransformerDecoderLayers -> optional final LayerNorm
+    (the toolkits' after_norm) -> Linear with log-softmax (asr_linear_fwd,
+    EPI_BIAS_LOGSOFTMAX).  Teacher-forced scoring of n-best lists: log_probs /
+    score (asr_token_score).  Autoregressive decoding on a K/V cache: begin /
+    step / prune, and beam_search / greedy on top of them
+    (asr_decode_attention_fwd, asr_attn_beam_step).  embedding [V, E]; w_out
+    [E, V] in the [in][out] layout, b_out [V].  A right-to-left decoder
+    (reverse_weight), joint CTC / attention decoding and length penalties are
+    not built."""
 
     def __init__(self, embedding, layers: Sequence[TransformerDecoderLayer], w_out, b_out=None,
                  final_norm: Optional[LayerNorm] = None, scale_embedding: bool = True,
@@ -1894,6 +2208,22 @@ class TransformerDecoder:
         self._emb64 = self.emb.astype(np.float64) * self.emb_scale
         self.positional_encoding = bool(positional_encoding)
         self._scratch, self._keep = _Scratch(), None
+        self._emb_d, self._pe_d = None, {}
+
+    def _emb_dev(self) -> DeviceMatrix:
+        if self._emb_d is None:
+            self._emb_d = DeviceMatrix.from_numpy(self.emb)
+        return self._emb_d
+
+    def _pe_dev(self, length: int):
+        """The float64 positional table [length, E] on the device (None without positional encoding)."""
+        if not self.positional_encoding:
+            return None
+        if length not in self._pe_d:
+            if len(self._pe_d) >= 8:
+                self._pe_d.clear()
+            self._pe_d[length] = _upload(sinusoidal_positional_encoding(length, self.E))
+        return self._pe_d[length]
 
     @classmethod
     def from_torch(cls, embedding, decoder, output, scale_embedding: bool = True,
@@ -1951,7 +2281,11 @@ class TransformerDecoder:
         d_off = device_lengths(off)
         sc = self._scratch                  # buffers of this decoder, reused by its next call of the same shape
         x, y, kv = sc.get("x", U * N, E), sc.get("y", U * N, E), sc.get("kv", T * B, 2 * E)
-        x.toGpu(self.embed(tokens_in), st)
+        if tokens_in.size and (tokens_in.min() < 0 or tokens_in.max() >= self.V):
+            raise ValueError(f"TransformerDecoder: a token outside [0, {self.V})")
+        pos = np.repeat(np.arange(U, dtype=np.int32), N) if self.positional_encoding else None
+        embed_fwd(self._emb_dev(), self._pe_dev(U), np.ascontiguousarray(tokens_in, dtype=np.int32).reshape(-1), pos,
+                  x, U * N, E, self.V, U, self.emb_scale, stream=st)       # embed()'s bits, gathered on the device
         for layer in self.layers:
             layer.cross_attn.project_memory(memory, T, B, out=kv, stream=st)
             layer.forward(x, U, N, kv, T, B, ql, kl, d_off, max_hyps, out=y, stream=st)
@@ -1990,6 +2324,240 @@ class TransformerDecoder:
         tin, tgt, ln = self.teacher_forcing(hyps, sos, eos)
         logp, U, N = self.log_probs(tin, ln, utt, memory, T, B, enc_lengths, stream)
         return token_score(logp, tgt, ln, U, N, self.V_out, stream=stream or 0)
+
+    # ------------------------------------------------ autoregressive decoding
+    def begin(self, memory, T: int, B: int, enc_lengths=None, beam: int = 10, max_len: Optional[int] = None,
+              sos: Optional[int] = None, stream: int = 0) -> "DecoderState":
+        """Start a search over memory [T*B, E] (row j*B + b: frame j of
+        utterance b; enc_lengths[b] frames of it, None: T) with beam slots per
+        utterance, slot n = b*beam + k, and at most max_len (default T) steps:
+        the DecoderState with the per-layer K/V caches [max_len*N, 3E], the
+        per-layer projected memory (project_memory runs here, once per
+        search), the ancestry and token tables, the scores (slot k = 0 of each
+        utterance 0, the others -inf) and flags, and the utterances' slot
+        offsets and encoder lengths."""
+        T, B, K, E = int(T), int(B), int(beam), self.E
+        max_len = T if max_len is None else int(max_len)
+        sos = self.V - 1 if sos is None else int(sos)
+        if T < 1 or B < 1 or max_len < 1:
+            raise ValueError(f"TransformerDecoder.begin: T {T}, B {B}, max_len {max_len}")
+        if K < 1 or K > ATTN_BEAM_MAX_K:
+            raise ValueError(f"TransformerDecoder.begin: beam {K} outside [1, {ATTN_BEAM_MAX_K}]")
+        if sos < 0 or sos >= self.V:
+            raise ValueError(f"TransformerDecoder.begin: sos {sos} outside [0, {self.V})")
+        if self.V_out > self.V:
+            raise ValueError(f"TransformerDecoder.begin: {self.V_out} outputs cannot be fed back into an embedding "
+                             f"of {self.V} rows")
+        _need_matrix("TransformerDecoder.begin: memory", memory, T * B, E)
+        if memory.rows != T * B or memory.cols != E:
+            raise ValueError(f"TransformerDecoder.begin: memory is {memory.rows} x {memory.cols}, not T*B x E = "
+                             f"{T * B} x {E}")
+        if enc_lengths is None:
+            enc = np.full(B, T, np.int32)
+        elif isinstance(enc_lengths, DeviceBytes):
+            _need_int32("TransformerDecoder.begin: enc_lengths", enc_lengths, B)
+            enc = None
+        else:
+            if len(enc_lengths) != B:
+                raise ValueError(f"TransformerDecoder.begin: {len(enc_lengths)} enc_lengths, not B = {B}")
+            enc = np.asarray(enc_lengths, np.int64)
+        if enc is None:
+            enc = device_int32(enc_lengths, B, stream or 0)
+        enc = np.minimum(np.maximum(enc, 0), T).astype(np.int32)
+        return DecoderState(self, memory, T, B, K, max_len, sos, enc, stream or 0)
+
+    def step(self, state: "DecoderState", tokens=None, parents=None, stream: int = 0) -> DeviceMatrix:
+        """One decoder step for every slot from the state's current tokens (sos
+        at step 0): the log-probs [N, V_out] on the device (a buffer of the
+        state, reused by the next step).  After step s the caller decides the
+        tokens of step s: prune() on the device, or tokens [N] and parents [N]
+        given to the NEXT step() call (slot n then continues slot parents[n],
+        a slot of its own utterance, with tokens[n]): the caller drives the
+        reorder, and the tables are permuted on the host."""
+        N, E, st = state.N, self.E, stream or 0
+        s = state.steps
+        if state.decoder is not self:
+            raise ValueError("TransformerDecoder.step: the state belongs to another decoder")
+        if s >= state.max_len:
+            raise ValueError(f"TransformerDecoder.step: the state's max_len = {state.max_len} steps are used up")
+        if (tokens is None) != (parents is None):
+            raise ValueError("TransformerDecoder.step: tokens and parents come together")
+        if tokens is not None:
+            if s == 0 or state.decided != s - 1:
+                raise ValueError("TransformerDecoder.step: tokens / parents decide a step that has run and has "
+                                 "not been decided")
+            tk, pa = np.asarray(tokens), np.asarray(parents)
+            if tk.shape != (N,) or pa.shape != (N,):
+                raise ValueError(f"TransformerDecoder.step: tokens {tk.shape} / parents {pa.shape}, not ({N},)")
+            if tk.min() < 0 or tk.max() >= self.V:
+                raise ValueError(f"TransformerDecoder.step: a token outside [0, {self.V})")
+            if pa.min() < 0 or pa.max() >= N or np.any(pa // state.K != np.arange(N) // state.K):
+                raise ValueError("TransformerDecoder.step: a parent outside its slot's utterance")
+            state._reorder_host(tk.astype(np.int32), pa.astype(np.int64), st)
+        elif state.decided != s:
+            raise ValueError(f"TransformerDecoder.step: the tokens of step {s - 1} are not decided: prune() or give "
+                             "tokens / parents")
+        tok = state.sos if s == 0 else Int32View(state.tok[state.cur], (s - 1) * N, N)
+        pos = Int32View(state.pos, s * N, N) if self.positional_encoding else None
+        x, y = state.x, state.y
+        embed_fwd(self._emb_dev(), state.pe, tok, pos, x, N, E, self.V, state.max_len, self.emb_scale, stream=st)
+        for layer, cache, kv in zip(self.layers, state.caches, state.kvs):
+            layer.step(x, N, cache, s, state.anc[state.cur], kv, state.T, state.B, state.off, state.K, state.klen,
+                       out=y, stream=st)
+            x, y = y, x
+        if self.final_norm is not None:
+            self.final_norm.forward(x, 1, N, None, out=x, stream=st)
+        linear_fwd(x, self.w_out, self.b_out, state.logp, EPI_BIAS_LOGSOFTMAX, st)
+        state.steps = s + 1
+        return state.logp
+
+    def prune(self, state: "DecoderState", logp=None, eos: Optional[int] = None, stream: int = 0) -> int:
+        """Decide the step that has just run on the device (asr_attn_beam_step
+        on logp, default the state's): scores, flags, tokens and both tables.
+        Returns the number of live unfinished slots, one 4-byte read, EVERY
+        step: the read costs one synchronisation of a loop that is otherwise
+        queued ahead, and ends the search at the step the last hypothesis
+        ends."""
+        eos = self.V - 1 if eos is None else int(eos)
+        s, st = state.steps - 1, stream or 0
+        if s < 0 or state.decided != s:
+            raise ValueError("TransformerDecoder.prune: no step has run that is not decided")
+        if eos < 0 or eos >= self.V_out:
+            raise ValueError(f"TransformerDecoder.prune: eos {eos} outside [0, {self.V_out})")
+        logp = state.logp if logp is None else logp
+        c, o = state.cur, 1 - state.cur
+        attn_beam_step(attn_beam_desc(state.B, state.K, self.V_out, state.max_len, s, eos), logp, state.scores[c],
+                       state.fin[c], state.tok[c], state.anc[c], state.scores[o], state.fin[o], state.parent,
+                       state.token, state.tok[o], state.anc[o], state.live, stream=st)
+        state.cur, state.decided, state.eos = o, s + 1, eos
+        return int(device_int32(state.live, 1, st)[0])
+
+    def beam_search(self, memory, T: int, B: int, enc_lengths=None, beam: int = 10, max_len: Optional[int] = None,
+                    sos: Optional[int] = None, eos: Optional[int] = None, nbest: Optional[int] = None,
+                    stream: int = 0):
+        """Attention-decoder beam search (the toolkits' `attention` decode
+        mode): per utterance [(tokens, score)], score descending (equal scores
+        in slot order), tokens without sos / eos, at most nbest (default beam)
+        of them; score is the float64 sum of the chosen tokens' fp32 log-probs,
+        eos included.  A finished hypothesis stays in the beam with its score
+        (WeNet's masking); the loop ends when no live unfinished slot is left
+        (prune()'s count, read every step) or after max_len (default T) steps,
+        and hypotheses that have not ended by then are returned as they stand.
+        An utterance with no encoder frames returns [([], score)], score the
+        log-prob of eos after sos over an all-zero context.  The result plugs
+        into attention_combine, nbest_mbr and edit_distance as the other
+        searches' n-bests do."""
+        eos = self.V - 1 if eos is None else int(eos)
+        if eos < 0 or eos >= self.V_out:
+            raise ValueError(f"TransformerDecoder.beam_search: eos {eos} outside [0, {self.V_out})")
+        if nbest is not None and nbest < 1:
+            raise ValueError(f"TransformerDecoder.beam_search: nbest {nbest}")
+        state = self.begin(memory, T, B, enc_lengths, beam, max_len, sos, stream)
+        empty, none = {}, np.flatnonzero(state.enc == 0)
+        for s in range(state.max_len):
+            logp = self.step(state, stream=stream)
+            if s == 0:                       # an utterance without frames: its result is this step's eos
+                one = np.empty(1, np.float32)
+                for b in none:
+                    check(lib().asr_memcpy_d2h(_ptr(one), logp.ptr + 4 * (int(b) * state.K * logp.cols + eos), 4,
+                                               stream or 0), "asr_memcpy_d2h")
+                    empty[int(b)] = float(np.float64(one[0]))
+            live = self.prune(state, logp, eos, stream)
+            if s == 0 and len(none):         # ... and its slots leave the search: they hold no one up
+                state.drop_utterances(none, stream or 0)
+                live = 1
+            if live == 0:
+                break
+        out = state.results(nbest)
+        for b, sc in empty.items():
+            out[b] = [([], sc)]
+        return out
+
+    def greedy(self, memory, T: int, B: int, enc_lengths=None, max_len: Optional[int] = None,
+               sos: Optional[int] = None, eos: Optional[int] = None, stream: int = 0):
+        """beam_search with one slot per utterance."""
+        return self.beam_search(memory, T, B, enc_lengths, 1, max_len, sos, eos, None, stream)
+
+
+class DecoderState:
+    """The state of one autoregressive search of a TransformerDecoder
+    (TransformerDecoder.begin): N = B*K slots, slot n = b*K + k.  On the
+    device: caches[l] [max_len*N, 3E] (row j*N + n: the Q / K / V row slot n
+    wrote at step j), kvs[l] [T*B, 2E] the projected memory of layer l, the
+    ancestry and token tables anc / tok (int32 [max_len][N], two copies each:
+    a prune gathers from one into the other), scores (fp64 [N]) and fin (int32
+    [N]) likewise, off / klen (the slots of each utterance, [B + 1], and its encoder frames, [B]),
+    parent / token of the last prune and the live count.  steps: decoder steps
+    run; decided: steps whose tokens are decided."""
+
+    def __init__(self, decoder, memory, T, B, K, max_len, sos, enc, stream=0):
+        N, E = B * K, decoder.E
+        self.decoder, self.T, self.B, self.K, self.N, self.max_len = decoder, T, B, K, N, max_len
+        self.steps, self.decided, self.cur, self.eos, self.enc = 0, 0, 0, None, enc
+        self.caches = [DeviceMatrix(max_len * N, 3 * E) for _ in decoder.layers]
+        self.kvs = [l.cross_attn.project_memory(memory, T, B, stream=stream) for l in decoder.layers]
+        ident = np.tile(np.arange(N, dtype=np.int32), (max_len, 1))
+        self.anc = [_upload(ident, stream), _upload(ident, stream)]
+        zeros = np.zeros((max_len, N), np.int32)
+        self.tok = [_upload(zeros, stream), _upload(zeros, stream)]
+        sc = np.full(N, -np.inf, np.float64)
+        sc[::K] = 0.0
+        self.scores = [_upload(sc, stream), _upload(sc, stream)]
+        self.fin = [_upload(np.zeros(N, np.int32), stream), _upload(np.zeros(N, np.int32), stream)]
+        self.off = _upload(np.arange(B + 1, dtype=np.int32) * K, stream)
+        self.klen = _upload(enc.astype(np.int32), stream)
+        self.pos = _upload(np.repeat(np.arange(max_len, dtype=np.int32), N), stream)
+        self.sos = _upload(np.full(N, sos, np.int32), stream)
+        self.pe = decoder._pe_dev(max_len)
+        self.parent, self.token, self.live = DeviceBytes(4 * N), DeviceBytes(4 * N), DeviceBytes(16)
+        self.x, self.y = DeviceMatrix(N, E), DeviceMatrix(N, E)
+        self.logp = DeviceMatrix(N, decoder.V_out)
+
+    def _reorder_host(self, tokens, parents, stream=0):
+        """The caller's decision of step steps - 1: both tables through parents, on the host."""
+        N, L, s, c = self.N, self.max_len, self.steps - 1, self.cur
+        tok = _download(self.tok[c], (L, N), np.int32, stream)
+        anc = _download(self.anc[c], (L, N), np.int32, stream)
+        tok[:s] = tok[:s, parents]
+        tok[s] = tokens
+        anc[:s + 1] = anc[:s + 1, parents]
+        if s + 1 < L:
+            anc[s + 1] = np.arange(N, dtype=np.int32)
+        for d, a in ((self.tok[c], tok), (self.anc[c], anc)):
+            check(lib().asr_memcpy_h2d(d.ptr, _ptr(a), a.nbytes, stream), "asr_memcpy_h2d")
+        self.decided = s + 1
+
+    def drop_utterances(self, utts, stream=0):
+        """Empty every slot of the given utterances (score -inf): the next prune finds no candidate there."""
+        gone = np.full(self.K, -np.inf, np.float64)
+        for b in utts:
+            check(lib().asr_memcpy_h2d(self.scores[self.cur].ptr + 8 * int(b) * self.K, _ptr(gone), gone.nbytes,
+                                       stream), "asr_memcpy_h2d")
+
+    def tables(self, stream=0):
+        """(tokens [decided][N], ancestry [steps..][N], scores [N], finished [N]) on the host."""
+        N, L, c = self.N, self.max_len, self.cur
+        return (_download(self.tok[c], (L, N), np.int32, stream)[:self.decided],
+                _download(self.anc[c], (L, N), np.int32, stream)[:min(self.decided + 1, L)],
+                _download(self.scores[c], N, np.float64, stream), _download(self.fin[c], N, np.int32, stream))
+
+    def results(self, nbest=None, stream=0):
+        """Per utterance [(tokens, score)] of the live slots, score descending,
+        tokens cut before the first eos of the last prune."""
+        tok, _anc, sc, _fin = self.tables(stream)
+        out = []
+        for b in range(self.B):
+            rows = []
+            for n in range(b * self.K, (b + 1) * self.K):
+                if not sc[n] > -np.inf:
+                    continue
+                y = tok[:, n].tolist()
+                if self.eos is not None and self.eos in y:
+                    y = y[:y.index(self.eos)]
+                rows.append((y, float(sc[n])))
+            rows.sort(key=lambda r: -r[1])
+            out.append(rows[:nbest] if nbest is not None else rows)
+        return out
 
 
 def attention_combine(nbest, att, ctc, ctc_weight: float):

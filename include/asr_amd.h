@@ -606,9 +606,10 @@ int asr_attention_fwd(const asr_attn_desc* d, const float* d_q, long ldq, const 
  * scale that is not finite or < 0.  ASR_ERR_UNSUPPORTED: head_dim % 4 != 0 or
  * > 128; heads*head_dim > 4096; heads or B > 65535 (grid dimensions); U*N or
  * T*B > INT_MAX; U*max_hyps > INT_MAX - 64.
- * Not built: a right-to-left decoder (reverse_weight); autoregressive decoding
- * with a K/V cache; a compaction of dead query lanes (a lane past qlen[n] stays
- * in its tile); GELU in the decoder's feed-forward. */
+ * (Autoregressive decoding with a K/V cache is asr_decode_attention_fwd below.)
+ * Not built: a right-to-left decoder (reverse_weight); a compaction of dead
+ * query lanes (a lane past qlen[n] stays in its tile); GELU in the decoder's
+ * feed-forward. */
 typedef struct asr_xattn_desc {
     int heads, head_dim;   /* limits of asr_attn_desc */
     float scale;           /* 0 = 1/sqrt(head_dim); else finite, > 0 */
@@ -630,6 +631,116 @@ int asr_cross_attention_fwd(const asr_xattn_desc* d, const float* d_q, long ldq,
  * ld < V.  ASR_ERR_UNSUPPORTED: U*N > INT_MAX. */
 int asr_token_score(const float* d_logp, long ld, const int32_t* d_tokens, const int32_t* d_lengths,
                     double* d_scores, int U, int N, int V, asr_stream_t s);
+
+/* Attention over a K/V cache with ONE query per hypothesis: the attention of an
+ * autoregressive decoder step (attention-decoder beam search: WeNet's and
+ * ESPnet's `attention` decode mode); no reference member.  Hypothesis n of N
+ * attends to keys j < len[n]:
+ *   out(n, h, :) = sum_j softmax_j(scale * q(n,h).k(j, col(j,n), h)) v(j, col(j,n), h)
+ * Layout: d_q and d_out have N rows of heads*head_dim floats (row strides ldq,
+ * ldo; head h at columns [h*head_dim, (h+1)*head_dim)); d_k and d_v are
+ * time-major [Tk*S, >= E], key j of column c being row j*S + c, as everywhere in
+ * this library.  d_cols device int32 with row stride ldc: col(j, n) =
+ * d_cols[j*ldc + n].  ldc = 0: one column d_cols[n] for every j; that is
+ * cross-attention, col the hypothesis's utterance, S = B, Tk = T.  ldc >= N:
+ * self-attention over the cache of a beam search, the table being the ancestry
+ * (which slot wrote this hypothesis's key at step j), Tk rows of it; a beam
+ * reorder permutes that small table and never moves K / V.  d_lengths device
+ * int32 [N] clamped to [0, Tk], NULL = Tk.
+ * A row with len 0 is exact zeros.  K / V rows that no live (j, n) names may
+ * hold NaN: they are never read.  Columns >= heads*head_dim of a row of d_out
+ * are not touched.  K and V may be column ranges of one buffer.  scale = 0 means
+ * 1 / sqrt(head_dim).  d_out must not overlap Q, K or V.
+ * The kernel clamps every col into [0, S - 1]: a wrong table gives wrong numbers
+ * and never an access outside the buffers.
+ * Arithmetic: fp32, online softmax over 64-key blocks from key 0 ascending, a
+ * lane per key for q.k (one fmaf per dimension, ascending), a lane per four
+ * output dimensions and half block for p.v; no MFMA: the work is one query
+ * against a few hundred keys, bound by latency and bandwidth.  Grid (N, heads),
+ * one 64-lane workgroup per (hypothesis, head).  A row's bits depend only on its
+ * query, the keys and values it sees in order and the descriptor: never on N, S,
+ * the row's slot, other hypotheses, ldc, the column numbers, strides or pointer
+ * alignment.  They are NOT asr_attention_fwd's bits (another product order).
+ * One launch, asynchronous on s, no allocation, no workspace, no host sync.
+ * Checks, in this order, all before any HIP call — ASR_ERR_ARG: a NULL
+ * descriptor, d_q, d_k, d_v, d_out or d_cols; non-positive N, Tk, S, heads or
+ * head_dim; ldc outside {0} and [N, inf); a stride below heads*head_dim; a scale
+ * that is not finite or < 0.  ASR_ERR_UNSUPPORTED: head_dim % 4 != 0 or > 128;
+ * heads*head_dim > 4096; heads > 65535; Tk*S > INT_MAX.
+ * Measured: through an ancestry table the call takes 0.31
+ * to 0.39 of a physical gather of the cache followed by asr_attention_fwd; with
+ * ldc = 0 it takes 2.4 to 5 times asr_cross_attention_fwd at U = 1, which stages
+ * an utterance's K / V once for all of its hypotheses, so a decoder step's
+ * cross-attention should call that.
+ * Not built: several queries per hypothesis (speculative or chunked decoding);
+ * K / V staged once in LDS for the hypotheses of one utterance. */
+int asr_decode_attention_fwd(const asr_xattn_desc* d, const float* d_q, long ldq, const float* d_k, long ldk,
+                             const float* d_v, long ldv, const int32_t* d_cols, long ldc, const int32_t* d_lengths,
+                             float* d_out, long ldo, int N, int Tk, int S, asr_stream_t s);
+
+/* Embedding gather on the device:
+ *   d_out[r][e] = fp32( (double)d_emb[tok[r]][e] * scale + d_pe[pos[r]][e] ),  r < R, e < E,
+ * the product and the sum two separately rounded fp64 operations (no FMA), so
+ * the result equals a float64 host gather rounded once.  d_emb fp32 [V, E] (row
+ * stride lde), d_pe fp64 [P, E] (row stride ldp; NULL = 0, and d_pos, ldp and P
+ * are then ignored), d_tokens and d_pos device int32 [R], d_out fp32 [R, >= E]
+ * (row stride ldo).  A token outside [0, V) or a position outside [0, P) gives a
+ * zero row and nothing is read for it.  One launch, asynchronous on s.
+ * Checks, in this order, before any HIP call — ASR_ERR_ARG: NULL d_emb, d_tokens
+ * or d_out, or d_pe without d_pos; non-positive R, E, V (P with d_pe); lde, ldo
+ * (ldp with d_pe) below E; a scale that is not finite.  ASR_ERR_UNSUPPORTED:
+ * R*E > INT_MAX. */
+int asr_embed_fwd(const float* d_emb, long lde, const double* d_pe, long ldp, const int32_t* d_tokens,
+                  const int32_t* d_pos, double scale, float* d_out, long ldo, int R, int E, int V, int P,
+                  asr_stream_t s);
+
+/* One prune of an attention-decoder beam search.  B utterances have K slots
+ * each, slot n = b*K + k, N = B*K.  d_logp fp32 [N, V] (row stride ld) are the
+ * decoder's log-probs of this step, d_scores fp64 [N] the hypotheses' scores
+ * (-inf: an empty slot; at step 0 only slot k = 0 of each utterance is live),
+ * d_finished int32 [N], and d_tokens_in / d_anc_in the int32 history tables
+ * [max_len][N]: the token chosen at step j, and the slot that wrote the
+ * hypothesis's self-attention key at step j (asr_decode_attention_fwd's d_cols).
+ * Candidates: a live, unfinished slot gives V of them, token v scoring
+ * score + (double)logp[v] (one that comes out -inf or NaN is dropped); a
+ * finished slot exactly one, itself, score unchanged, token eos (WeNet's masking
+ * of ended hypotheses); an empty slot none.  Kept: the exact top K per
+ * utterance, by score descending, ties by parent slot ascending, then by token
+ * ascending; slot k of the utterance gets the k-th.  Remaining slots are empty:
+ * score -inf, finished 0, parent the slot itself, token eos.
+ * Outputs: d_scores_out, d_finished_out (the parent's flag, or token == eos),
+ * d_parent [N] (a slot of the same utterance), d_token [N]; the tables through
+ * parent, tokens_out[j][n] = tokens_in[j][parent[n]] for j < step,
+ * tokens_out[step][n] = token[n], anc_out[j][n] = anc_in[j][parent[n]] for
+ * j <= step, anc_out[step + 1][n] = n when step + 1 < max_len (later rows are
+ * not touched; the out tables must not be the in tables); d_all_finished, one
+ * int32: the number of live unfinished slots after the prune (0: the search is
+ * over).  asr_attn_beam_step: device pointers, one kernel launch (one workgroup
+ * per utterance; K rounds, each taking the best candidate after the last) behind
+ * a 4-byte memset, asynchronous on s, no host sync.  asr_attn_beam_step_host:
+ * the same rule on host pointers (a partial sort), the CPU path; the two agree
+ * exactly.
+ * Checks, in this order, before any HIP call — ASR_ERR_ARG: a NULL pointer; B or
+ * V or max_len <= 0; K outside [1, ASR_ATTN_BEAM_MAX_K]; step outside
+ * [0, max_len); eos outside [0, V); ld < V; an out table that is its in table.
+ * ASR_ERR_UNSUPPORTED: B*K*max_len > INT_MAX.
+ * Not built: joint CTC / attention decoding with a CTC prefix scorer; length
+ * penalties. */
+#define ASR_ATTN_BEAM_MAX_K 16
+typedef struct asr_attn_beam_desc {
+    int B, K, V;           /* utterances, slots per utterance, vocabulary */
+    int max_len;           /* rows of the history tables */
+    int step;              /* this prune's step, 0 .. max_len - 1 */
+    int eos;
+} asr_attn_beam_desc;
+int asr_attn_beam_step(const asr_attn_beam_desc* d, const float* d_logp, long ld, const double* d_scores,
+                       const int32_t* d_finished, const int32_t* d_tokens_in, const int32_t* d_anc_in,
+                       double* d_scores_out, int32_t* d_finished_out, int32_t* d_parent, int32_t* d_token,
+                       int32_t* d_tokens_out, int32_t* d_anc_out, int32_t* d_all_finished, asr_stream_t s);
+int asr_attn_beam_step_host(const asr_attn_beam_desc* d, const float* logp, long ld, const double* scores,
+                            const int32_t* finished, const int32_t* tokens_in, const int32_t* anc_in,
+                            double* scores_out, int32_t* finished_out, int32_t* parent, int32_t* token,
+                            int32_t* tokens_out, int32_t* anc_out, int32_t* all_finished);
 
 /* LayerNorm over the N columns of each row of a time-major [T*B, N] buffer,
  * with an optional fused residual (torch.nn.LayerNorm semantics):
