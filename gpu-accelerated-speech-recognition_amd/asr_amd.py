@@ -657,7 +657,10 @@ def lstm_fwd(x: DeviceMatrix, W_ih: DeviceMatrix, W_hh: DeviceMatrix, b_ih: Devi
              col: int = 0, stream: int = 0) -> DeviceMatrix:
     """One LSTM layer and direction (asr_lstm_fwd): W_ih [in, 4H], W_hh [H, 4H]
     (gates i, f, g, o), h_t into columns [col, col + H) of hid [T*B, >= H]
-    (the row stride is hid.cols); lengths from device_lengths()."""
+    (the row stride is hid.cols); lengths from device_lengths().  hT may be h0
+    itself (in-place streaming) for H <= 128 only: for H > 128, and for any
+    partial overlap of the two, the library returns ASR_ERR_ARG (asr_amd.h);
+    cT may be c0."""
     inp, H = W_ih.rows, W_hh.rows
     assert x.rows == T * B and x.cols == inp and W_ih.cols == 4 * H and W_hh.cols == 4 * H
     out, ldh, pht, pct, pln, pwk = _gated_tail("LSTM", hid, col, H, T, B, work, True, hT, cT, lengths, work)
@@ -674,7 +677,9 @@ def lstm_recur_fwd(P: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh
                    lengths: Optional[DeviceBytes] = None, reverse: bool = False, col: int = 0,
                    stream: int = 0) -> DeviceMatrix:
     """The recurrence stage alone (asr_lstm_recur_fwd): P [T*B, 4H] holds x.W_ih
-    (read only); work is needed for H > 128."""
+    (read only); work is needed for H > 128.  hT may be h0 itself (in-place
+    streaming) for H <= 128 only: for H > 128, and for any partial overlap of
+    the two, the library returns ASR_ERR_ARG (asr_amd.h); cT may be c0."""
     H = W_hh.rows
     assert P.rows == T * B and P.cols == 4 * H and W_hh.cols == 4 * H
     out, ldh, pht, pct, pln, pwk = _gated_tail("LSTM", hid, col, H, T, B, work, H > 128, hT, cT, lengths, work)
@@ -690,7 +695,9 @@ def gru_fwd(x: DeviceMatrix, W_ih: DeviceMatrix, W_hh: DeviceMatrix, b_ih: Devic
             col: int = 0, stream: int = 0) -> DeviceMatrix:
     """One GRU layer and direction (asr_gru_fwd): W_ih [in, 3H], W_hh [H, 3H]
     (gates r, z, n), h_t into columns [col, col + H) of hid [T*B, >= H] (the
-    row stride is hid.cols); lengths from device_lengths()."""
+    row stride is hid.cols); lengths from device_lengths().  hT may be h0
+    itself (in-place streaming) for H <= 128 only: for H > 128, and for any
+    partial overlap of the two, the library returns ASR_ERR_ARG (asr_amd.h)."""
     inp, H = W_ih.rows, W_hh.rows
     assert x.rows == T * B and x.cols == inp and W_ih.cols == 3 * H and W_hh.cols == 3 * H
     out, ldh, pht, pln, pwk = _gated_tail("GRU", hid, col, H, T, B, work, True, hT, lengths, work)
@@ -704,7 +711,9 @@ def gru_recur_fwd(P: DeviceMatrix, W_hh: DeviceMatrix, b_ih: DeviceMatrix, b_hh:
                   lengths: Optional[DeviceBytes] = None, reverse: bool = False, col: int = 0,
                   stream: int = 0) -> DeviceMatrix:
     """The recurrence stage alone (asr_gru_recur_fwd): P [T*B, 3H] holds x.W_ih
-    (read only); no workspace."""
+    (read only); no workspace.  hT may be h0 itself (in-place streaming) for
+    H <= 128 only: for H > 128, and for any partial overlap of the two, the
+    library returns ASR_ERR_ARG (asr_amd.h)."""
     H = W_hh.rows
     assert P.rows == T * B and P.cols == 3 * H and W_hh.cols == 3 * H
     out, ldh, pht, pln = _gated_tail("GRU", hid, col, H, T, B, None, False, hT, lengths)
@@ -779,6 +788,11 @@ class _GatedRNN:
                 setattr(self, name, DeviceMatrix(self.L * D * B, H))
             self._shape = (T, B)
         assert h0 is None or (h0.rows == self.L * D * B and h0.cols == H), (h0.rows, h0.cols)
+        if h0 is not None and h0.ptr < self.h_n.ptr + self.h_n.nbytes and self.h_n.ptr < h0.ptr + h0.nbytes:
+            # h0 is (part of) the state matrix about to be written, e.g. h0=net.h_n: the step form cannot
+            # write d_hT over d_h0 (asr_amd.h), so the new state goes to a second matrix; no device copy,
+            # and the caller's h0 keeps its contents
+            self.h_n = DeviceMatrix(self.L * D * B, H)
         ln = lengths if lengths is None or isinstance(lengths, DeviceBytes) else device_lengths(lengths)
         for l, dirs in enumerate(self.layers):
             for d, weights in enumerate(dirs):
@@ -843,7 +857,10 @@ class GRU(_GatedRNN):
         (DeviceBytes, e.g. Conv1d.forward's out_lengths); returns the last
         layer's [T*B, H or 2H] (zeros past each utterance's length); h_n holds
         the final states.  The two directions of a layer write the two halves
-        of one buffer."""
+        of one buffer.  h0=net.h_n streams: the kernels cannot write the new
+        state over the one they read for H > 128 (asr_amd.h), so when h0 shares
+        memory with h_n the new state is written to a second matrix, which
+        becomes h_n; the caller's h0 keeps its contents and nothing is copied."""
         return self._forward(x, T, B, lengths, h0, stream or 0)
 
 

@@ -436,7 +436,8 @@ static int gated_launch(const float* P, const float* h0, const float* c0, const 
 
 // The shape checks of the entry points, ahead of any HIP call.
 template <class Cell>
-static int gated_check(const void* work, long ldh, int T, int B, int H, const float* hid, const float* h0) {
+static int gated_check(const void* work, long ldh, int T, int B, int H, const float* hid, const float* h0,
+                       const float* hT) {
     if (T <= 0 || B <= 0 || H <= 0 || ldh < H) return ASR_ERR_ARG;
     if (!gated_shape_ok(H)) return ASR_ERR_UNSUPPORTED;
     if ((long)B * Cell::NG * H * 4 > (long)GR_OOB) return ASR_ERR_UNSUPPORTED;   // one frame of P per buffer resource
@@ -446,6 +447,22 @@ static int gated_check(const void* work, long ldh, int T, int B, int H, const fl
         // the step form reads h_{t-1} rows with 16-byte loads
         if ((ldh & 3) != 0 || ((uintptr_t)hid & 15) != 0 || ((uintptr_t)h0 & 15) != 0) return ASR_ERR_UNSUPPORTED;
     }
+    // hT over h0: the step form's workgroups read whole h0 rows for the
+    // contraction while the owners of other columns store hT in the same
+    // launch, so it takes no overlap at all; the resident form's lanes read
+    // their own h0 element first and write that element last, so hT == h0
+    // exactly is in-place streaming there, and any other overlap is refused.
+    if (hT && h0) {
+        const uintptr_t a = (uintptr_t)hT, b = (uintptr_t)h0, n = (uintptr_t)B * H * sizeof(float);
+        if ((a > b ? a - b : b - a) < n && !(a == b && H <= GR_RHMAX)) return ASR_ERR_ARG;
+    }
+    // hT == h0 (in-place streaming).  A lane of the resident form reads its own
+    // h0 element first and writes that element last: legal.  The step form's
+    // workgroups read whole h0 rows for the contraction while the owners of
+    // other columns store hT in the same launch (T = 1, or a length-1
+    // utterance in reverse): refused.  (c0 / cT: the owning lane reads before
+    // it writes in both forms.)
+    if (hT && hT == h0 && H > GR_RHMAX) return ASR_ERR_ARG;
     return ASR_OK;
 }
 
@@ -464,7 +481,7 @@ static int gated_recur_fwd(const float* P, const float* h0, const float* c0, con
                            const float* b_hh, float* hid, long ldh, float* hT, float* cT, const int32_t* lengths,
                            void* work, int T, int B, int H, int reverse, asr_stream_t s) {
     if (!P || !W_hh || !b_ih || !b_hh || !hid) return ASR_ERR_ARG;
-    if (int rc = gated_check<Cell>(work, ldh, T, B, H, hid, h0)) return rc;
+    if (int rc = gated_check<Cell>(work, ldh, T, B, H, hid, h0, hT)) return rc;
     float* cwork = Cell::HAS_C && work ? (float*)work + (size_t)T * B * Cell::NG * H : nullptr;
     return gated_launch<Cell>(P, h0, c0, W_hh, b_ih, b_hh, hid, ldh, hT, cT, lengths, cwork, T, B, H,
                               reverse ? 1 : 0, asr_stream(s));
@@ -475,7 +492,7 @@ static int gated_fwd(const float* x, const float* h0, const float* c0, const flo
                      const float* b_ih, const float* b_hh, float* hid, long ldh, float* hT, float* cT,
                      const int32_t* lengths, void* work, int T, int B, int in, int H, int reverse, asr_stream_t s) {
     if (!x || !W_ih || !W_hh || !b_ih || !b_hh || !hid || !work || in <= 0) return ASR_ERR_ARG;
-    if (int rc = gated_check<Cell>(work, ldh, T, B, H, hid, h0)) return rc;
+    if (int rc = gated_check<Cell>(work, ldh, T, B, H, hid, h0, hT)) return rc;
     // P = x.W_ih for all T frames: asr_linear_fwd(x, W_ih, NULL, P, T*B, in, NG*H, ASR_EPI_NONE)
     const int HG = Cell::NG * H;
     GemmArgs g{};

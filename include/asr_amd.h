@@ -233,7 +233,12 @@ int asr_rnn_bidir_fwd(const float* d_x, const float* d_h0, const float* const d_
  * are carried unchanged and its output row is zeros, i.e. pack_padded_sequence
  * / pad_packed_sequence; in reverse the utterance starts from h0 / c0 at its
  * own last frame.  d_hT, d_cT [B,H] (NULL = not wanted) receive the state
- * after each utterance's last valid frame (in reverse: after frame 0).
+ * after each utterance's last valid frame (in reverse: after frame 0); pass
+ * them as the next call's d_h0 / d_c0 to stream.  In place: d_cT may be d_c0.
+ * d_hT may be d_h0 (the same pointer) for H <= 128 only; for H > 128 the
+ * per-frame launch reads whole h0 rows while it stores d_hT, so d_hT == d_h0
+ * is ASR_ERR_ARG there (alternate two buffers), and a d_hT that overlaps the
+ * [B,H] floats of d_h0 without being equal to it is ASR_ERR_ARG for every H.
  * d_work: asr_lstm_workspace_bytes(T,B,H) bytes, 16-B aligned (the input
  * projection for all T, one GEMM that follows asr_set_dense_arith like
  * asr_linear_fwd, then the cell state); the size is 0 for an invalid shape.
@@ -282,7 +287,11 @@ int asr_lstm_recur_fwd(const float* d_P, const float* d_h0, const float* d_c0, c
  * utterance b's h is carried unchanged and its output row is zeros, in
  * reverse the utterance starts from h0 at its own last frame; d_hT [B,H]
  * (NULL = not wanted) receives the state after each utterance's last valid
- * frame, h0 for length 0 — pass it as the next call's d_h0 to stream.
+ * frame, h0 for length 0 — pass it as the next call's d_h0 to stream.  In
+ * place: d_hT may be d_h0 (the same pointer) for H <= 128 only; for H > 128
+ * the per-frame launch reads whole h0 rows while it stores d_hT, so d_hT ==
+ * d_h0 is ASR_ERR_ARG there (alternate two buffers), and a d_hT that overlaps
+ * the [B,H] floats of d_h0 without being equal to it is ASR_ERR_ARG for every H.
  * d_work: asr_gru_workspace_bytes(T,B,H) bytes, 16-B aligned: the input
  * projection P [T*B, 3H] for all T, one GEMM that follows asr_set_dense_arith
  * like asr_linear_fwd; the size is 0 for an invalid shape.

@@ -103,3 +103,26 @@ def test_err_unsupported_step_form_alignment():
     p = [FAKE] * 8
     p[1] = FAKE + 8   # h0 not 16-byte aligned
     assert asr.lib().asr_gru_recur_fwd(*p[:6], 256, *p[6:], 4, 4, 256, 0, None) == asr.ASR_ERR_UNSUPPORTED
+
+
+def state_overlap(H, h0, hT, B=4):
+    """asr_gru_recur_fwd and asr_gru_fwd on an otherwise valid call with the given d_h0 / d_hT."""
+    p, L = FAKE, asr.lib()
+    return (L.asr_gru_recur_fwd(p, h0, p, p, p, p, H, hT, p, 4, B, H, 0, None),
+            L.asr_gru_fwd(p, h0, p, p, p, p, p, H, hT, p, p, 4, B, 8, H, 0, None))
+
+
+def test_err_arg_hT_over_h0():
+    """d_hT over d_h0 ([B*H] floats each): the step form (H > 128) reads whole h0 rows while it
+    stores hT, so even d_hT == d_h0 is refused there; a partial overlap is refused for every H."""
+    B = 4
+    assert state_overlap(256, FAKE, FAKE) == (asr.ASR_ERR_ARG,) * 2             # equal pointers, step form
+    for H in (16, 256):
+        n = B * H * 4
+        for h0, hT in ((FAKE, FAKE + 16), (FAKE + 16, FAKE), (FAKE, FAKE + n - 16), (FAKE + n - 16, FAKE)):
+            assert state_overlap(H, h0, hT, B) == (asr.ASR_ERR_ARG,) * 2, (H, h0, hT)
+    # the H limits answer first: an unsupported shape stays ASR_ERR_UNSUPPORTED.  (d_hT == d_h0 at
+    # H <= 128 is legal and cannot be shown with fake pointers, since the call would launch:
+    # test_gated_rnn_edges_gpu.py's in-place tests run it at H = 48.)
+    assert state_overlap(2064, FAKE, FAKE) == (asr.ASR_ERR_UNSUPPORTED,) * 2
+    assert state_overlap(24, FAKE, FAKE) == (asr.ASR_ERR_UNSUPPORTED,) * 2

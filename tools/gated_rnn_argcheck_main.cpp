@@ -63,6 +63,12 @@ static void gru() {
     EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 16, F, L, 4, 0, 16, 0, nullptr), ASR_ERR_ARG);
     EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 255, F, L, 4, 4, 256, 0, nullptr), ASR_ERR_ARG);
     EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, -1, F, L, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    // d_hT over d_h0: equal pointers in the step form, a partial overlap in either form
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 256, F, L, 4, 4, 256, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 256, F, L, W, 4, 4, 8, 256, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F, F, F, F, F, 256, F + 4 * 256 - 4, L, 4, 4, 256, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_recur_fwd(F, F + 4, F, F, F, F, 16, F, L, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 16, F + 4 * 16 - 1, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
 
     // ASR_ERR_UNSUPPORTED
     EXPECT(asr_gru_fwd(F, F, F, F, F, F, F, 20, F, L, W, 4, 4, 8, 20, 0, nullptr), ASR_ERR_UNSUPPORTED);
@@ -125,6 +131,12 @@ static void lstm() {
     // the step form keeps c in the workspace; the resident form needs none
     EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 144, F, F, L, nullptr, 4, 4, 144, 0, nullptr), ASR_ERR_ARG);
     EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 2048, F, F, L, nullptr, 4, 4, 2048, 0, nullptr), ASR_ERR_ARG);
+    // d_hT over d_h0: equal pointers in the step form, a partial overlap in either form
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 256, F, F, L, W, 4, 4, 256, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 256, F, F, L, W, 4, 4, 8, 256, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F, F, F, F, F, F, 256, F + 4 * 256 - 4, F, L, W, 4, 4, 256, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_recur_fwd(F, F + 4, F, F, F, F, F, 16, F, F, L, W, 4, 4, 16, 0, nullptr), ASR_ERR_ARG);
+    EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 16, F + 4 * 16 - 1, F, L, W, 4, 4, 8, 16, 0, nullptr), ASR_ERR_ARG);
 
     // ASR_ERR_UNSUPPORTED
     EXPECT(asr_lstm_fwd(F, F, F, F, F, F, F, F, 20, F, F, L, W, 4, 4, 8, 20, 0, nullptr), ASR_ERR_UNSUPPORTED);
