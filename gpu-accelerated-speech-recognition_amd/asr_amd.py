@@ -63,6 +63,13 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           (asr_attn_beam_step, host twin
                                           asr_attn_beam_step_host); no reference
                                           member
+    TransformerDecoder.beam_search(..., ctc=emissions, ctc_weight=0.3) / CTCPrefixScorer(...)
+                                          joint CTC / attention decoding: the CTC
+                                          prefix scores of every candidate and the
+                                          joint row in one launch
+                                          (asr_ctc_prefix_score), the state in fp64
+                                          (asr_ctc_prefix_begin / _advance); no
+                                          reference member
     FeatureFrontend(sample_rate=..., n_mfcc=..., n_context=...).forward
                                           waveform -> log-mel / MFCC features
                                           (asr_fbank_*); no reference member
@@ -143,6 +150,7 @@ EXPORTS = [
     "asr_attention_fwd", "asr_layernorm_fwd", "asr_mask_rows",
     "asr_cross_attention_fwd", "asr_token_score",
     "asr_decode_attention_fwd", "asr_embed_fwd", "asr_attn_beam_step", "asr_attn_beam_step_host",
+    "asr_ctc_prefix_begin", "asr_ctc_prefix_score", "asr_ctc_prefix_advance",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
     "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
@@ -282,6 +290,9 @@ def lib() -> ctypes.CDLL:
                           _i, _i, _i, _i, _vp],
         "asr_attn_beam_step": [_vp, _vp, ctypes.c_long] + [_vp] * 12,
         "asr_attn_beam_step_host": [_vp, _vp, ctypes.c_long] + [_vp] * 11,
+        "asr_ctc_prefix_begin": [_vp, _vp, ctypes.c_long] + [_vp] * 6,
+        "asr_ctc_prefix_score": [_vp, _vp, ctypes.c_long] + [_vp] * 8 + [ctypes.c_long, _vp, ctypes.c_long, _vp],
+        "asr_ctc_prefix_advance": [_vp, _vp, ctypes.c_long] + [_vp] * 12,
         "asr_fbank_num_frames": [_vp, _i],
         "asr_fbank_feature_dim": [_vp],
         "asr_fbank_host_tables": [_vp, _vp, _vp, _vp],
@@ -2199,9 +2210,10 @@ class TransformerDecoder:
     score (asr_token_score).  Autoregressive decoding on a K/V cache: begin /
     step / prune, and beam_search / greedy on top of them
     (asr_decode_attention_fwd, asr_attn_beam_step).  embedding [V, E]; w_out
-    [E, V] in the [in][out] layout, b_out [V].  A right-to-left decoder
-    (reverse_weight), joint CTC / attention decoding and length penalties are
-    not built."""
+    [E, V] in the [in][out] layout, b_out [V].  beam_search / greedy decode
+    jointly with CTC when given the emissions (CTCPrefixScorer,
+    asr_ctc_prefix_score).  A right-to-left decoder (reverse_weight) is not
+    built."""
 
     def __init__(self, embedding, layers: Sequence[TransformerDecoderLayer], w_out, b_out=None,
                  final_norm: Optional[LayerNorm] = None, scale_embedding: bool = True,
@@ -2451,7 +2463,7 @@ class TransformerDecoder:
 
     def beam_search(self, memory, T: int, B: int, enc_lengths=None, beam: int = 10, max_len: Optional[int] = None,
                     sos: Optional[int] = None, eos: Optional[int] = None, nbest: Optional[int] = None,
-                    stream: int = 0):
+                    stream: int = 0, ctc=None, ctc_weight: float = 0.0, blank: int = 0, length_bonus: float = 0.0):
         """Attention-decoder beam search (the toolkits' `attention` decode
         mode): per utterance [(tokens, score)], score descending (equal scores
         in slot order), tokens without sos / eos, at most nbest (default beam)
@@ -2463,13 +2475,42 @@ class TransformerDecoder:
         An utterance with no encoder frames returns [([], score)], score the
         log-prob of eos after sos over an all-zero context.  The result plugs
         into attention_combine, nbest_mbr and edit_distance as the other
-        searches' n-bests do."""
+        searches' n-bests do.
+        Joint CTC / attention decoding (the toolkits' default mode, ESPnet's
+        ctc_weight): with ctc, the CTC log-softmax emissions [T*B, V_out] of
+        the same utterances on the device (blank their blank token), and
+        ctc_weight in (0, 1], every candidate of every step scores (1 -
+        ctc_weight) * attention log-prob + ctc_weight * (psi(g.c) - psi(g)) +
+        length_bonus, psi the CTC prefix log-probability (CTCPrefixScorer:
+        one asr_ctc_prefix_score between step and prune, one
+        asr_ctc_prefix_advance behind the prune), and the returned scores are
+        these joint totals.  A candidate CTC cannot emit in the utterance's
+        frames is dropped.  With ctc None or ctc_weight 0 the scorer is never
+        called, length_bonus included, and an utterance without frames
+        returns what it returns without ctc."""
         eos = self.V - 1 if eos is None else int(eos)
         if eos < 0 or eos >= self.V_out:
             raise ValueError(f"TransformerDecoder.beam_search: eos {eos} outside [0, {self.V_out})")
         if nbest is not None and nbest < 1:
             raise ValueError(f"TransformerDecoder.beam_search: nbest {nbest}")
+        w, bonus, blank = float(ctc_weight), float(length_bonus), int(blank)
+        if not 0.0 <= w <= 1.0:
+            raise ValueError(f"TransformerDecoder.beam_search: ctc_weight {ctc_weight} outside [0, 1]")
+        if not np.isfinite(bonus):
+            raise ValueError(f"TransformerDecoder.beam_search: length_bonus {length_bonus} is not finite")
+        joint = ctc is not None and w > 0.0
+        if joint:
+            if blank < 0 or blank >= self.V_out or blank == eos or blank == (self.V - 1 if sos is None else int(sos)):
+                raise ValueError(f"TransformerDecoder.beam_search: blank {blank} outside [0, {self.V_out}), or eos "
+                                 "or sos")
+            if ctc.rows != int(T) * int(B) or ctc.cols != self.V_out:
+                raise ValueError(f"TransformerDecoder.beam_search: ctc is {ctc.rows} x {ctc.cols}, not T*B x V_out "
+                                 f"= {int(T) * int(B)} x {self.V_out}")
         state = self.begin(memory, T, B, enc_lengths, beam, max_len, sos, stream)
+        scorer = None
+        if joint:
+            scorer = CTCPrefixScorer(ctc, state.T, state.B, state.klen, state.K, blank, eos)
+            scorer.begin(stream)
         empty, none = {}, np.flatnonzero(state.enc == 0)
         for s in range(state.max_len):
             logp = self.step(state, stream=stream)
@@ -2479,7 +2520,12 @@ class TransformerDecoder:
                     check(lib().asr_memcpy_d2h(_ptr(one), logp.ptr + 4 * (int(b) * state.K * logp.cols + eos), 4,
                                                stream or 0), "asr_memcpy_d2h")
                     empty[int(b)] = float(np.float64(one[0]))
-            live = self.prune(state, logp, eos, stream)
+            if scorer is None:
+                live = self.prune(state, logp, eos, stream)
+            else:                            # the joint row, the prune on it, the kept hypotheses' new CTC state
+                live = self.prune(state, scorer.score(state, logp, ctc_weight=w, length_bonus=bonus, stream=stream),
+                                  eos, stream)
+                scorer.advance(state, stream)
             if s == 0 and len(none):         # ... and its slots leave the search: they hold no one up
                 state.drop_utterances(none, stream or 0)
                 live = 1
@@ -2491,9 +2537,11 @@ class TransformerDecoder:
         return out
 
     def greedy(self, memory, T: int, B: int, enc_lengths=None, max_len: Optional[int] = None,
-               sos: Optional[int] = None, eos: Optional[int] = None, stream: int = 0):
+               sos: Optional[int] = None, eos: Optional[int] = None, stream: int = 0, ctc=None,
+               ctc_weight: float = 0.0, blank: int = 0, length_bonus: float = 0.0):
         """beam_search with one slot per utterance."""
-        return self.beam_search(memory, T, B, enc_lengths, 1, max_len, sos, eos, None, stream)
+        return self.beam_search(memory, T, B, enc_lengths, 1, max_len, sos, eos, None, stream, ctc, ctc_weight, blank,
+                                length_bonus)
 
 
 class DecoderState:
@@ -2575,6 +2623,97 @@ class DecoderState:
             rows.sort(key=lambda r: -r[1])
             out.append(rows[:nbest] if nbest is not None else rows)
         return out
+
+
+class CtcPrefixDesc(ctypes.Structure):
+    """asr_ctc_prefix_desc (include/asr_amd.h)."""
+    _fields_ = [("B", _i), ("K", _i), ("V", _i), ("T", _i), ("blank", _i), ("eos", _i),
+                ("ctc_weight", ctypes.c_double), ("length_bonus", ctypes.c_double)]
+
+
+class CTCPrefixScorer:
+    """The CTC prefix scorer of joint CTC / attention decoding
+    (asr_ctc_prefix_begin / _score / _advance): emissions the CTC log-softmax
+    outputs [T*B, >= V] on the device (anything with .ptr, .rows and .cols;
+    row t*B + b, V default .cols, the row stride ld default .cols),
+    enc_lengths [B] a host sequence, a device buffer or None (T), beam the
+    slots per utterance (slot n = b*beam + k as in DecoderState).  Holds two
+    copies of the fp64 state (rn, rb [T][N], psi [N], last int32 [N]; cur names
+    the current one): advance() gathers from one into the other, as a prune
+    does with its tables.  Driven by a DecoderState, or by anything with its
+    scores / fin / cur / parent / token."""
+
+    def __init__(self, emissions, T: int, B: int, enc_lengths=None, beam: int = 10, blank: int = 0,
+                 eos: Optional[int] = None, V: Optional[int] = None, ld: Optional[int] = None):
+        T, B, K = int(T), int(B), int(beam)
+        V = int(emissions.cols if V is None else V)
+        eos, blank = V - 1 if eos is None else int(eos), int(blank)
+        if T < 1 or B < 1 or V < 1:
+            raise ValueError(f"CTCPrefixScorer: T {T}, B {B}, V {V}")
+        if K < 1 or K > ATTN_BEAM_MAX_K:
+            raise ValueError(f"CTCPrefixScorer: beam {K} outside [1, {ATTN_BEAM_MAX_K}]")
+        if not (0 <= blank < V and 0 <= eos < V) or blank == eos:
+            raise ValueError(f"CTCPrefixScorer: blank {blank} / eos {eos} outside [0, {V}) or equal")
+        _need_matrix("CTCPrefixScorer: emissions", emissions, T * B, V, ld)
+        self.emis, self.ld = emissions, int(emissions.cols if ld is None else ld)
+        self.enc = _device_int32_exact("CTCPrefixScorer: enc_lengths", np.full(B, T) if enc_lengths is None
+                                       else enc_lengths, B)
+        self.T, self.B, self.K, self.V, self.N, self.blank, self.eos = T, B, K, V, B * K, blank, eos
+        N = self.N
+        self.rn, self.rb = [DeviceBytes(8 * T * N) for _ in range(2)], [DeviceBytes(8 * T * N) for _ in range(2)]
+        self.psi, self.last = [DeviceBytes(8 * N) for _ in range(2)], [DeviceBytes(4 * N) for _ in range(2)]
+        self.cur, self.out = 0, None
+
+    def _desc(self, ctc_weight: float = 0.0, length_bonus: float = 0.0) -> CtcPrefixDesc:
+        return CtcPrefixDesc(self.B, self.K, self.V, self.T, self.blank, self.eos, ctc_weight, length_bonus)
+
+    def begin(self, stream: int = 0) -> None:
+        """The state of the empty prefix in every slot of the current copy."""
+        c = self.cur
+        check(lib().asr_ctc_prefix_begin(ctypes.byref(self._desc()), self.emis.ptr, self.ld, self.enc.ptr,
+                                         self.rn[c].ptr, self.rb[c].ptr, self.psi[c].ptr, self.last[c].ptr,
+                                         stream or 0), "asr_ctc_prefix_begin")
+
+    def score(self, state, att=None, out=None, ctc_weight: float = 0.0, length_bonus: float = 0.0,
+              ld_att: Optional[int] = None, ldo: Optional[int] = None, stream: int = 0):
+        """out [N, >= V] (default a zero-filled buffer of this scorer, reused by
+        the next call): the deltas psi(g.c) - psi(g) of the state's live
+        unfinished slots, or with att (the decoder's log-probs [N, >= V]) the
+        joint rows (1 - ctc_weight) * att + ctc_weight * delta + length_bonus,
+        which prune() takes as its logp.  Rows of empty or finished slots and
+        of utterances without frames are not touched."""
+        w, bonus = float(ctc_weight), float(length_bonus)
+        if not 0.0 <= w <= 1.0 or not np.isfinite(bonus):
+            raise ValueError(f"CTCPrefixScorer.score: ctc_weight {ctc_weight} outside [0, 1] or length_bonus "
+                             f"{length_bonus} not finite")
+        if out is None:
+            if self.out is None:
+                self.out = DeviceMatrix(self.N, self.V, np.zeros((self.N, self.V), np.float32))
+            out = self.out
+        _need_matrix("CTCPrefixScorer.score: out", out, self.N, self.V, ldo)
+        if att is not None:
+            _need_matrix("CTCPrefixScorer.score: att", att, self.N, self.V, ld_att)
+        sc, fin = state.scores[state.cur], state.fin[state.cur]
+        if sc.nbytes < 8 * self.N or fin.nbytes < 4 * self.N:
+            raise ValueError(f"CTCPrefixScorer.score: the state's scores / flags are not over N = {self.N} slots")
+        c = self.cur
+        check(lib().asr_ctc_prefix_score(
+            ctypes.byref(self._desc(w, bonus)), self.emis.ptr, self.ld, self.enc.ptr, self.rn[c].ptr, self.rb[c].ptr,
+            self.psi[c].ptr, self.last[c].ptr, sc.ptr, fin.ptr, att.ptr if att is not None else None,
+            int(att.cols if ld_att is None else ld_att) if att is not None else 0, out.ptr,
+            int(out.cols if ldo is None else ldo), stream or 0), "asr_ctc_prefix_score")
+        return out
+
+    def advance(self, state, stream: int = 0) -> None:
+        """After the prune: slot n continues the prune's parent[n] with token[n]; the other copy becomes current."""
+        if state.parent.nbytes < 4 * self.N or state.token.nbytes < 4 * self.N:
+            raise ValueError(f"CTCPrefixScorer.advance: the state's parent / token are not over N = {self.N} slots")
+        c, o = self.cur, 1 - self.cur
+        check(lib().asr_ctc_prefix_advance(
+            ctypes.byref(self._desc()), self.emis.ptr, self.ld, self.enc.ptr, state.parent.ptr, state.token.ptr,
+            self.rn[c].ptr, self.rb[c].ptr, self.psi[c].ptr, self.last[c].ptr, self.rn[o].ptr, self.rb[o].ptr,
+            self.psi[o].ptr, self.last[o].ptr, stream or 0), "asr_ctc_prefix_advance")
+        self.cur = o
 
 
 def attention_combine(nbest, att, ctc, ctc_weight: float):

@@ -733,8 +733,8 @@ int asr_embed_fwd(const float* d_emb, long lde, const double* d_pe, long ldp, co
  * V or max_len <= 0; K outside [1, ASR_ATTN_BEAM_MAX_K]; step outside
  * [0, max_len); eos outside [0, V); ld < V; an out table that is its in table.
  * ASR_ERR_UNSUPPORTED: B*K*max_len > INT_MAX.
- * Not built: joint CTC / attention decoding with a CTC prefix scorer; length
- * penalties. */
+ * Joint CTC / attention decoding and a length bonus come in through d_logp:
+ * asr_ctc_prefix_score below writes the joint row this prune takes. */
 #define ASR_ATTN_BEAM_MAX_K 16
 typedef struct asr_attn_beam_desc {
     int B, K, V;           /* utterances, slots per utterance, vocabulary */
@@ -750,6 +750,91 @@ int asr_attn_beam_step_host(const asr_attn_beam_desc* d, const float* logp, long
                             const int32_t* finished, const int32_t* tokens_in, const int32_t* anc_in,
                             double* scores_out, int32_t* finished_out, int32_t* parent, int32_t* token,
                             int32_t* tokens_out, int32_t* anc_out, int32_t* all_finished);
+
+/* The CTC prefix scorer of joint CTC / attention decoding (ESPnet's ctc_weight in
+ * beam search: every candidate of every step scores (1 - w) * attention log-prob
+ * + w * CTC prefix log-prob); no reference member.  Watanabe et al.'s prefix
+ * probabilities in the log domain, (+) being log-sum-exp:
+ * x[t, b, c] = d_emis[(t*B + b)*ld + c] are CTC log-softmax emissions, utterance
+ * b has T_b = d_enc_lengths[b] frames (clamped to [0, T]).  A hypothesis g (its
+ * tokens without sos, last token last(g)) has the state rn[t], rb[t], t < T_b:
+ * the log-probability of emitting exactly g in frames 0 .. t ending in a
+ * non-blank / in blank, and its prefix log-probability psi(g).
+ *   begin    rn[t] = -inf, rb[t] = sum_{tau <= t} x[tau, b, blank], psi = 0, last = -1.
+ *   score    phi_c[t] = rb[t] if c == last(g), else rn[t] (+) rb[t];
+ *            psi(g.c) = [g empty] x[0, b, c] (+) (+)_{t = 1}^{T_b - 1} (phi_c[t-1] + x[t, b, c])
+ *            for c neither blank nor eos; psi(g.eos) = rn[T_b-1] (+) rb[T_b-1];
+ *            psi(g.blank) = -inf.  The output is the DELTA d(g, c) = psi(g.c) - psi(g),
+ *            <= 0 up to rounding, formed directly: phi is shifted by psi(g) in fp64
+ *            before anything is rounded to fp32, so the accuracy does not ride on
+ *            the difference of two numbers near -500.
+ *   advance  the hypothesis kept as (parent g, token c):
+ *            rn'[t] = (rn'[t-1] (+) phi_c[t-1]) + x[t, b, c],
+ *            rb'[t] = (rn'[t-1] (+) rb'[t-1]) + x[t, b, blank],
+ *            rn'[0] = x[0, b, c] if g is empty, else -inf, rb'[0] = -inf,
+ *            psi' = psi(g.c) recomputed in fp64, last' = c.  Token eos (a finished
+ *            parent, a hypothesis that ends now, an empty slot of the prune) and a
+ *            token outside [0, V) pass the parent's state on unchanged.
+ * Layout: N = B*K slots, slot n = b*K + k as in asr_attn_beam_step; rn and rb fp64
+ * [T][N] (frame t of slot n at t*N + n: the slots side by side), psi fp64 [N],
+ * last int32 [N] (-1: the empty prefix).  State rows t >= T_b are never read or
+ * written, emission rows t >= T_b never read.
+ * asr_ctc_prefix_score: d_scores fp64 [N] and d_finished int32 [N] are the
+ * search's (asr_attn_beam_step's); the row of an empty (score -inf or NaN) or
+ * finished slot, and every row of an utterance with T_b = 0, is not touched and
+ * its state not read.  A live slot whose psi is -inf (it cannot be emitted in T_b
+ * frames) gets a row of -inf.  d_att NULL: d_out[n*ldo + c] = d(n, c), c < V.
+ * d_att fp32 [N, V] (row stride ld_att, the decoder's log-probs): the joint row
+ *   d_out[n*ldo + c] = fp32((1 - w) * att[n, c] + w * d(n, c) + length_bonus)
+ * in fp64 from the fp32 delta, -inf wherever d is -inf (at every w, w = 0
+ * included); asr_attn_beam_step takes it as its d_logp, so no other kernel
+ * touches [N, V].  d_out may be d_att.  Columns >= V of d_out are not touched.
+ * Kernel: grid (ceil(V / 256), B), a workgroup serves one utterance and 256
+ * tokens, a lane one token with one (maximum, sum) accumulator pair per live
+ * hypothesis of the utterance, so each emission is read once per call for all K;
+ * phi in both forms, shifted and rounded to fp32, is staged in LDS 64 frames at a
+ * time.  fp32 terms in the base-2 domain, a running maximum per eight frames
+ * (t = 1 + 8q .. 8 + 8q): the largest term contributes exactly 1, so the result
+ * is finite wherever the exact one is and -inf exactly where it is -inf, with no
+ * floor.  No MFMA: a log-domain sum is not a product-sum, and in the probability
+ * domain terms hundreds of nats apart underflow.
+ * asr_ctc_prefix_advance: d_parent / d_token int32 [N] are the prune's; parent is
+ * clamped into the slot's utterance where it is read.  The out state must not be
+ * the in state (a gather through parent), double-buffered like the token and
+ * ancestry tables.  fp64 throughout, a lane per slot, T_b dependent steps of
+ * three log-sum-exps: latency-bound, N x T cells against the scorer's N x V x T.
+ * asr_ctc_prefix_begin writes the state of the empty prefix into all N slots.
+ * Bit property: a slot's output row and new state depend only on its own state
+ * and last token (the parent's, for advance), its utterance's emissions and
+ * length and the descriptor's scalars: never on B, K, N, the slot number, the
+ * other slots, ld / ld_att / ldo or pointer alignment.
+ * Every entry is one launch, asynchronous on s; none allocates or synchronises.
+ * Checks, in this order, all before any HIP call — ASR_ERR_ARG: a NULL pointer
+ * (d_att may be NULL); B, V or T <= 0; K outside [1, ASR_ATTN_BEAM_MAX_K]; blank
+ * or eos outside [0, V), or blank == eos; ctc_weight outside [0, 1] or NaN; a
+ * length_bonus that is not finite; ld < V; then score: ldo < V, or ld_att < V with
+ * d_att; advance: an out buffer that is an in buffer or the other out buffer;
+ * begin: d_rn == d_rb.  ASR_ERR_UNSUPPORTED: B > 65535; B*K*T > INT_MAX.
+ * Measured: DESIGN.md section 35.
+ * Not built: candidate lists (a pre-beam: scoring only the attention decoder's
+ * top candidates); the right-to-left decoder; a language model in the joint
+ * score; windowed (time-synchronous) prefix scoring. */
+typedef struct asr_ctc_prefix_desc {
+    int B, K, V, T;        /* utterances, slots per utterance, vocabulary, frames (rows of the state) */
+    int blank, eos;
+    double ctc_weight;     /* w in [0, 1]; used with d_att */
+    double length_bonus;   /* added to every candidate of a joint row */
+} asr_ctc_prefix_desc;
+int asr_ctc_prefix_begin(const asr_ctc_prefix_desc* d, const float* d_emis, long ld, const int32_t* d_enc_lengths,
+                         double* d_rn, double* d_rb, double* d_psi, int32_t* d_last, asr_stream_t s);
+int asr_ctc_prefix_score(const asr_ctc_prefix_desc* d, const float* d_emis, long ld, const int32_t* d_enc_lengths,
+                         const double* d_rn, const double* d_rb, const double* d_psi, const int32_t* d_last,
+                         const double* d_scores, const int32_t* d_finished, const float* d_att, long ld_att,
+                         float* d_out, long ldo, asr_stream_t s);
+int asr_ctc_prefix_advance(const asr_ctc_prefix_desc* d, const float* d_emis, long ld, const int32_t* d_enc_lengths,
+                           const int32_t* d_parent, const int32_t* d_token, const double* d_rn_in,
+                           const double* d_rb_in, const double* d_psi_in, const int32_t* d_last_in, double* d_rn_out,
+                           double* d_rb_out, double* d_psi_out, int32_t* d_last_out, asr_stream_t s);
 
 /* LayerNorm over the N columns of each row of a time-major [T*B, N] buffer,
  * with an optional fused residual (torch.nn.LayerNorm semantics):
