@@ -37,6 +37,11 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           LayerNorm and TransformerEncoderLayer,
                                           time-major (asr_attention_fwd,
                                           asr_layernorm_fwd); no reference member
+    RelPositionMultiheadAttention.from_torch(module, chunk, left, right).forward
+                                          the toolkits' relative-position
+                                          (Transformer-XL) self-attention
+                                          (asr_attention_rel_fwd); a ConformerLayer
+                                          takes it in place of MultiheadAttention
     ConformerLayer.from_torch(ffn1=..., attn=..., conv=..., ffn2=..., final_norm=...).forward
     ConformerConv.from_torch(norm, pw1, dw, bn, pw2).forward / Conformer(layers).forward
                                           a Conformer encoder block, time-major:
@@ -147,7 +152,7 @@ EXPORTS = [
     "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
     "asr_conv1d_out_frames", "asr_conv1d_fwd", "asr_glu_dwconv_fwd",
     "asr_conv2d_out_frames", "asr_conv2d_out_feats", "asr_conv2d_fwd",
-    "asr_attention_fwd", "asr_layernorm_fwd", "asr_mask_rows",
+    "asr_attention_fwd", "asr_attention_rel_fwd", "asr_layernorm_fwd", "asr_mask_rows",
     "asr_cross_attention_fwd", "asr_token_score",
     "asr_decode_attention_fwd", "asr_embed_fwd", "asr_attn_beam_step", "asr_attn_beam_step_host",
     "asr_ctc_prefix_begin", "asr_ctc_prefix_score", "asr_ctc_prefix_advance",
@@ -278,6 +283,8 @@ def lib() -> ctypes.CDLL:
         "asr_glu_dwconv_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _vp],
         "asr_attention_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp,
                               ctypes.c_long, _i, _i, _i, _i, _i, _vp],
+        "asr_attention_rel_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long,
+                                  _i, _i, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp],
         "asr_layernorm_fwd": [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _f, _vp, _vp, ctypes.c_long,
                               _i, _i, _i, _vp],
         "asr_mask_rows": [_vp, ctypes.c_long, _vp, _i, _i, _i, _vp],
@@ -1375,8 +1382,8 @@ def rel_positional_encoding(max_left: int, max_right: int, E: int) -> np.ndarray
     frame - key frame), from max_left down to -max_right, so distance 0 is row
     max_left.  The row of delta holds sin(delta w_k) at column 2k and
     cos(delta w_k) at column 2k + 1, w_k = 10000^(-2k / E); computed in float64
-    on the host.  E even.  Host only: the relative-position attention that
-    would read it is not built."""
+    on the host.  E even.  Host only: RelPositionMultiheadAttention projects it
+    with linear_pos for asr_attention_rel_fwd."""
     if max_left < 0 or max_right < 0 or E <= 0 or E % 2:
         raise ValueError(f"rel_positional_encoding: max_left {max_left}, max_right {max_right}, E {E}")
     delta = np.arange(max_left, -max_right - 1, -1, dtype=np.float64)[:, None]
@@ -1384,6 +1391,37 @@ def rel_positional_encoding(max_left: int, max_right: int, E: int) -> np.ndarray
     out = np.empty((max_left + max_right + 1, E), np.float64)
     out[:, 0::2], out[:, 1::2] = np.sin(delta * w), np.cos(delta * w)
     return out.astype(np.float32)
+
+
+def rel_needed_rows(Tq: int, Tk: int, chunk: int = 1, left: int = -1, right: int = -1, q_pos0: int = 0,
+                    k_pos0: int = 0) -> Tuple[int, int]:
+    """(delta_max, delta_min): the largest and smallest distance query frame -
+    key frame a call can ask for, from its frames and the window, lengths
+    ignored: the table rows pos_zero - delta_max .. pos_zero - delta_min that
+    asr_attention_rel_fwd wants."""
+    dmax, dmin = q_pos0 + Tq - 1 - k_pos0, q_pos0 - (k_pos0 + Tk - 1)
+    if left >= 0:
+        dmax = min(dmax, (left + 1) * chunk - 1)
+    if right >= 0:
+        dmin = max(dmin, -((right + 1) * chunk - 1))
+    return dmax, dmin
+
+
+def attention_rel_fwd(q, k, v, out, Tq: int, Tk: int, B: int, desc: AttnDesc, pos, pos_zero: int, bias_u=None,
+                      bias_v=None, lengths: Optional[DeviceBytes] = None, q_pos0: int = 0, k_pos0: int = 0,
+                      ldq: Optional[int] = None, ldk: Optional[int] = None, ldv: Optional[int] = None,
+                      ldo: Optional[int] = None, ldp: Optional[int] = None, stream: int = 0):
+    """attention_fwd with the relative-position term (asr_attention_rel_fwd):
+    pos is the projected table [n_pos, >= E] whose row pos_zero - delta holds
+    distance delta = query frame - key frame, bias_u / bias_v device [E] or
+    None (zeros).  Everything else as attention_fwd."""
+    ld = lambda m, given: int(m.cols if given is None else given)   # noqa: E731
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_attention_rel_fwd(ctypes.byref(desc), q.ptr, ld(q, ldq), k.ptr, ld(k, ldk), v.ptr, ld(v, ldv),
+                                      pos.ptr, ld(pos, ldp), int(pos.rows), int(pos_zero), opt(bias_u), opt(bias_v),
+                                      opt(lengths), out.ptr, ld(out, ldo), Tq, q_pos0, Tk, k_pos0, B, stream),
+          "asr_attention_rel_fwd")
+    return out
 
 
 def layernorm_fwd(x, out, T: int, B: int, N: int, gamma=None, beta=None, eps: float = 1e-5, res=None,
@@ -1507,6 +1545,8 @@ class MultiheadAttention:
         are zeros (asr_mask_rows after the output projection) unless
         zero_padding is False, in which case they hold the output bias."""
         E, M, st = self.E, T * B, stream or 0
+        if hasattr(x, "rows"):
+            _need_matrix("MultiheadAttention.forward: x", x, M, E)
         lengths = _device_lengths_or_none(lengths)
         qkv = self._scratch.get("qkv", M, 3 * E)
         ctx = self._scratch.get("ctx", M, E)
@@ -1555,6 +1595,108 @@ class MultiheadAttention:
         decode_attention_fwd(ColumnView(row, 0), ColumnView(cache, E), ColumnView(cache, 2 * E), ctx, N, step + 1, N,
                              self._xdesc, anc, ldc=N, stream=st)
         linear_fwd(ctx, self.w_out, self.b_out, out, EPI_BIAS, st)
+        return out
+
+
+class RelPositionMultiheadAttention:
+    """The toolkits' RelPositionMultiHeadedAttention (ESPnet, WeNet, NeMo,
+    icefall) as self-attention for inference: asr_linear_fwd to [T*B, 3E], one
+    asr_attention_rel_fwd on its three column ranges, asr_linear_fwd;
+    time-major, no arithmetic here.  w_in [E, 3E] (linear_q | k | v), w_pos
+    [E, E] (linear_pos, no bias) and w_out [E, E] in the [in][out] layout, b_in
+    [3E], b_out [E], bias_u / bias_v [heads][d_k] (zeros if None).  The
+    projected table of the distances a call needs is built from
+    rel_positional_encoding through asr_linear_fwd, kept on the layer and
+    rebuilt only when a call needs a distance outside it.  chunk / left / right:
+    the window of asr_attn_desc.  Dropout is ignored."""
+
+    def __init__(self, embed_dim: int, heads: int, w_in=None, b_in=None, w_pos=None, bias_u=None, bias_v=None,
+                 w_out=None, b_out=None, chunk: int = 1, left: int = -1, right: int = -1):
+        E = int(embed_dim)
+        if heads <= 0 or E <= 0 or E % heads or E % 2:
+            raise ValueError(f"RelPositionMultiheadAttention: embed_dim {E} is not an even multiple of heads {heads}")
+        hd = E // heads
+        if hd % 4 or hd > 128 or E > 4096:
+            raise ValueError(f"RelPositionMultiheadAttention: head_dim {hd} (% 4 == 0, <= 128) / embed_dim {E} "
+                             "(<= 4096) outside what asr_attention_rel_fwd takes")
+        if chunk < 1 or left < -1 or right < -1:
+            raise ValueError(f"RelPositionMultiheadAttention: window chunk {chunk}, left {left}, right {right}")
+        self.E, self.heads = E, heads
+        self.desc = attn_desc(heads, hd, 0.0, chunk, left, right)
+        up = lambda a, shape: DeviceMatrix.from_numpy(   # noqa: E731
+            np.zeros(shape, np.float32) if a is None else np.asarray(a, np.float32).reshape(shape))
+        self.w_in, self.b_in = up(w_in, (E, 3 * E)), up(b_in, (3 * E, 1))
+        self.w_pos, self.w_out, self.b_out = up(w_pos, (E, E)), up(w_out, (E, E)), up(b_out, (E, 1))
+        self.bias_u, self.bias_v = up(bias_u, (E, 1)), up(bias_v, (E, 1))
+        self._scratch, self._keep = _Scratch(), None
+        self._table = None                           # (delta_max, delta_min, projected DeviceMatrix)
+
+    @staticmethod
+    def pack_torch(m):
+        """(w_in [E, 3E], b_in [3E], w_pos [E, E], bias_u [E], bias_v [E], w_out
+        [E, E], b_out [E]) float32 from a module with linear_q / k / v / out,
+        linear_pos (no bias) and pos_bias_u / pos_bias_v [heads][d_k].  No
+        device call."""
+        host = lambda p: p.detach().cpu().float().numpy()   # noqa: E731
+        if getattr(m.linear_pos, "bias", None) is not None:
+            raise ValueError("RelPositionMultiheadAttention.from_torch: linear_pos with a bias is not supported")
+        ws, bs = zip(*(_torch_linear(lin) for lin in (m.linear_q, m.linear_k, m.linear_v)))
+        w_out, b_out = _torch_linear(m.linear_out)
+        E = w_out.shape[0]
+        if any(w.shape != (E, E) for w in ws) or tuple(m.pos_bias_u.shape) != tuple(m.pos_bias_v.shape):
+            raise ValueError("RelPositionMultiheadAttention.from_torch: the linears are not all E x E")
+        return (np.ascontiguousarray(np.concatenate(ws, axis=1)), np.concatenate(bs),
+                np.ascontiguousarray(host(m.linear_pos.weight).T), host(m.pos_bias_u).reshape(E),
+                host(m.pos_bias_v).reshape(E), w_out, b_out)
+
+    @classmethod
+    def from_torch(cls, m, chunk: int = 1, left: int = -1, right: int = -1) -> "RelPositionMultiheadAttention":
+        w_in, b_in, w_pos, bu, bv, w_out, b_out = cls.pack_torch(m)
+        return cls(w_out.shape[0], int(m.pos_bias_u.shape[0]), w_in, b_in, w_pos, bu, bv, w_out, b_out, chunk, left,
+                   right)
+
+    @staticmethod
+    def table_range(cached, dmax: int, dmin: int):
+        """The (delta_max, delta_min) a table must span so that a call needing
+        dmax .. dmin finds its rows: cached if it covers them (no rebuild),
+        else the union of both, widened to include distance 0."""
+        if cached is not None and cached[0] >= dmax and cached[1] <= dmin:
+            return cached
+        lo = cached if cached is not None else (0, 0)
+        return max(dmax, lo[0], 0), min(dmin, lo[1], 0)
+
+    def _pos_table(self, T: int, st: int):
+        """(projected table, pos_zero) for a plain call over T frames."""
+        d = self.desc
+        dmax, dmin = rel_needed_rows(T, T, d.chunk, d.left, d.right)
+        have = None if self._table is None else self._table[:2]
+        want = self.table_range(have, dmax, dmin)
+        if want != have:
+            raw = DeviceMatrix.from_numpy(rel_positional_encoding(want[0], -want[1], self.E))
+            proj = DeviceMatrix(raw.rows, self.E)
+            linear_fwd(raw, self.w_pos, None, proj, EPI_NONE, st)
+            self._table = (want[0], want[1], proj, raw)       # raw stays alive until the GEMM has run
+        return self._table[2], self._table[0]
+
+    def forward(self, x, T: int, B: int, lengths=None, out=None, zero_padding: bool = True, stream: int = 0):
+        """MultiheadAttention.forward's contract: time-major x [T*B, E] to out
+        [T*B, E] (a buffer of this layer unless given), rows past the lengths
+        zeros unless zero_padding is False."""
+        E, M, st = self.E, T * B, stream or 0
+        if hasattr(x, "rows"):
+            _need_matrix("RelPositionMultiheadAttention.forward: x", x, M, E)
+        lengths = _device_lengths_or_none(lengths)
+        pos, pos_zero = self._pos_table(T, st)
+        qkv = self._scratch.get("qkv", M, 3 * E)
+        ctx = self._scratch.get("ctx", M, E)
+        out = self._scratch.get("out", M, E) if out is None else out
+        linear_fwd(x, self.w_in, self.b_in, qkv, EPI_BIAS, st)
+        attention_rel_fwd(ColumnView(qkv, 0), ColumnView(qkv, E), ColumnView(qkv, 2 * E), ctx, T, T, B, self.desc,
+                          pos, pos_zero, self.bias_u, self.bias_v, lengths=lengths, stream=st)
+        linear_fwd(ctx, self.w_out, self.b_out, out, EPI_BIAS, st)
+        if zero_padding and lengths is not None:
+            mask_rows(out, T, B, E, lengths, st)
+        self._keep = lengths
         return out
 
 
@@ -2916,7 +3058,8 @@ class ConformerLayer:
     each FFN LayerNorm -> Linear -> SiLU -> Linear.  The feed-forwards are
     asr_linear_fwd with EPI_BIAS_SILU and EPI_BIAS, the 1/2 folded into the second
     linear's weights and bias when packing (exact: a power of two); attention
-    is MultiheadAttention (with its chunk / left / right window), the
+    is MultiheadAttention or RelPositionMultiheadAttention (with its chunk /
+    left / right window), the
     convolution module ConformerConv; the residuals are asr_matadd, the last one
     the fused residual of the final asr_layernorm_fwd.  No arithmetic here;
     dropout is ignored.  ffn1 / ffn2: (LayerNorm, w1 [E, F], b1 [F], w2 [F, E],
@@ -2972,9 +3115,15 @@ class ConformerLayer:
             for key, a in zip(("w1", "b1", "w2", "b2"), ConformerLayer.pack_ffn(ln, lin1, lin2)):
                 out[f"{name}.{key}"] = a
         norm("attn", attn[0])
-        for key, a in zip(("w_in", "b_in", "w_out", "b_out"), MultiheadAttention.pack_torch(attn[1])):
+        if hasattr(attn[1], "linear_pos"):           # the toolkits' relative-position module
+            keys = ("w_in", "b_in", "w_pos", "bias_u", "bias_v", "w_out", "b_out")
+            packed, heads = RelPositionMultiheadAttention.pack_torch(attn[1]), attn[1].pos_bias_u.shape[0]
+        else:
+            keys = ("w_in", "b_in", "w_out", "b_out")
+            packed, heads = MultiheadAttention.pack_torch(attn[1]), attn[1].num_heads
+        for key, a in zip(keys, packed):
             out["attn." + key] = a
-        out["attn.heads"] = int(attn[1].num_heads)
+        out["attn.heads"] = int(heads)
         for key, a in ConformerConv.pack_torch(*conv, padding=conv_padding).items():
             out["conv." + key] = a
         norm("final", final_norm)
@@ -2984,7 +3133,8 @@ class ConformerLayer:
     def from_torch(cls, ffn1, attn, conv, ffn2, final_norm, convolution_first: bool = False, chunk: int = 1,
                    left: int = -1, right: int = -1, conv_padding=None) -> "ConformerLayer":
         """From explicit torch parts: ffn1 / ffn2 = (LayerNorm, Linear, Linear),
-        attn = (LayerNorm, MultiheadAttention), conv = (LayerNorm, pointwise
+        attn = (LayerNorm, MultiheadAttention or a relative-position module with
+        linear_pos: RelPositionMultiheadAttention then), conv = (LayerNorm, pointwise
         Conv1d, depthwise Conv1d, BatchNorm1d, pointwise Conv1d), final_norm a
         LayerNorm; chunk / left / right the attention window; conv_padding as
         ConformerConv.pack_torch's padding."""
@@ -2992,8 +3142,13 @@ class ConformerLayer:
         E = p["attn.w_out"].shape[0]
         ln = lambda k: LayerNorm(E, p[k + ".norm_eps"], p[k + ".norm_weight"], p[k + ".norm_bias"])   # noqa: E731
         ffn = lambda k: (ln(k), p[k + ".w1"], p[k + ".b1"], p[k + ".w2"], p[k + ".b2"])   # noqa: E731
-        mha = MultiheadAttention(E, p["attn.heads"], p["attn.w_in"], p["attn.b_in"], p["attn.w_out"],
-                                 p["attn.b_out"], chunk, left, right)
+        if "attn.w_pos" in p:
+            mha = RelPositionMultiheadAttention(E, p["attn.heads"], p["attn.w_in"], p["attn.b_in"], p["attn.w_pos"],
+                                                p["attn.bias_u"], p["attn.bias_v"], p["attn.w_out"],
+                                                p["attn.b_out"], chunk, left, right)
+        else:
+            mha = MultiheadAttention(E, p["attn.heads"], p["attn.w_in"], p["attn.b_in"], p["attn.w_out"],
+                                     p["attn.b_out"], chunk, left, right)
         conv_m = ConformerConv._from_packed({k[5:]: v for k, v in p.items() if k.startswith("conv.")})
         return cls(ffn("ffn1"), ln("attn"), mha, conv_m, ffn("ffn2"), ln("final"), convolution_first)
 
@@ -3039,6 +3194,8 @@ class ConformerLayer:
         new DeviceMatrix [T*B, E] with zero rows past the lengths; rows of x
         past them may hold anything."""
         E, M, st = self.E, T * B, stream or 0
+        if hasattr(x, "rows"):
+            _need_matrix("ConformerLayer.forward: x", x, M, E)
         lengths = _device_lengths_or_none(lengths)
         sc = self._scratch
         h, h2, n = sc.get("h", M, E), sc.get("h2", M, E), sc.get("n", M, E)

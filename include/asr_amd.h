@@ -556,7 +556,8 @@ int asr_glu_dwconv_fwd(const asr_glu_dwconv_desc* d, const float* d_u, long ldu,
  * that is not finite or < 0.  ASR_ERR_UNSUPPORTED: head_dim % 4 != 0 or > 128;
  * heads*head_dim > 4096; heads or B > 65535 (grid dimensions); q_pos0 + Tq or
  * k_pos0 + Tk > INT_MAX - 64; Tq*B or Tk*B > INT_MAX.
- * Not built: relative-position or rotary terms and additive score biases;
+ * Not built: rotary terms and additive score biases (the relative-position
+ * term is asr_attention_rel_fwd);
  * the attention probabilities as an output; a split-bf16 variant; training.
  * (Cross-attention with different batch sizes is asr_cross_attention_fwd.) */
 #define ASR_ATTN_KEY_BLOCK 64
@@ -570,6 +571,46 @@ typedef struct asr_attn_desc {
 int asr_attention_fwd(const asr_attn_desc* d, const float* d_q, long ldq, const float* d_k, long ldk,
                       const float* d_v, long ldv, const int32_t* d_lengths, float* d_out, long ldo,
                       int Tq, int q_pos0, int Tk, int k_pos0, int B, asr_stream_t s);
+
+/* Relative-position (Transformer-XL) self-attention, the attention of the
+ * Conformer encoders of ESPnet, WeNet, NeMo and icefall:
+ *   score(p, r) = scale * ((q_p + u_h) . k_r + (q_p + v_h) . pi_h(p - r)),
+ *   out(p, b, h, :) = sum_r softmax_r(score(p, r)) v(r)  over the keys p sees.
+ * Everything asr_attention_fwd means stays: layout, absolute positions,
+ * lengths, the chunk / left / right window, exact zeros for dead queries and
+ * for queries that see nothing, NaN allowed in padding rows.
+ * d_pos is the already projected table [n_pos][>= E] (row stride ldp): the
+ * caller runs asr_linear_fwd with linear_pos over the sinusoidal table once per
+ * table.  Row pos_zero - delta holds distance delta = query frame - key frame
+ * (the order of the toolkits' pos_emb); head h reads columns [h*head_dim,
+ * (h+1)*head_dim).  d_bias_u / d_bias_v: device [heads*head_dim]
+ * (pos_bias_u / pos_bias_v flattened), NULL = zeros (the add is skipped).
+ * The distances a call can ask for, lengths aside:
+ *   delta_max = min(q_pos0 + Tq - 1 - k_pos0, (left + 1) * chunk - 1),
+ *   delta_min = max(q_pos0 - (k_pos0 + Tk - 1), -((right + 1) * chunk - 1))
+ * (the min / max only for a side that is not -1).  The table must hold rows
+ * pos_zero - delta_max .. pos_zero - delta_min; no row outside that range is
+ * ever loaded (such rows may hold NaN).
+ * Arithmetic: both score terms and P V on v_mfma_f32_16x16x4_f32, fp32 online
+ * softmax; the content term keeps asr_attention_fwd's chain, so a zero table
+ * with NULL biases gives asr_attention_fwd's bits.  The workgroup stages the
+ * table rows of a key block once in LDS (a ring of two 64-row halves, 64 new
+ * rows per key block); see csrc/attention_rel.hip.  An output row's bits depend
+ * only on its query, the keys, values and table rows it sees at their absolute
+ * positions and distances, the biases and the descriptor: never on B, Tq, Tk,
+ * how a stream is cut, pos_zero, n_pos, strides or alignment.
+ * One launch, asynchronous on s, no allocation, no host sync.  Checks, in this
+ * order, all before any HIP call: asr_attention_fwd's, with the new arguments
+ * beside their kind.  ASR_ERR_ARG: a NULL descriptor, d_q, d_k, d_v, d_out or
+ * d_pos; non-positive Tq, Tk, B, heads, head_dim, chunk or n_pos; left or right
+ * < -1; negative q_pos0 or k_pos0; a stride (ldp included) below
+ * heads*head_dim; a scale that is not finite or < 0; pos_zero - delta_max < 0
+ * or pos_zero - delta_min > n_pos - 1.  ASR_ERR_UNSUPPORTED: as
+ * asr_attention_fwd. */
+int asr_attention_rel_fwd(const asr_attn_desc* d, const float* d_q, long ldq, const float* d_k, long ldk,
+                          const float* d_v, long ldv, const float* d_pos, long ldp, int n_pos, int pos_zero,
+                          const float* d_bias_u, const float* d_bias_v, const int32_t* d_lengths, float* d_out,
+                          long ldo, int Tq, int q_pos0, int Tk, int k_pos0, int B, asr_stream_t s);
 
 /* Grouped cross-attention, the hot path of attention-decoder rescoring (WeNet's
  * attention_rescoring, ESPnet's joint CTC / attention scoring): N = sum n_b
