@@ -93,6 +93,15 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           RNN-T greedy decoding, the whole (t, u)
                                           walk in one launch (asr_rnnt_*); no
                                           reference member
+    TransducerDecoder.from_icefall(decoder, joiner) / TransducerDecoder.stateless(desc, weights)
+                                          the same decoder for a stateless predictor
+                                          (k2 / icefall: an embedding of the last
+                                          context_size tokens, a grouped Conv1d,
+                                          ReLU): per-token context tables, a step
+                                          is row gathers (asr_rnnt_create_stateless,
+                                          asr_rnnt_greedy_stateless); beam_search,
+                                          score, align and rescore work unchanged;
+                                          no reference member
     TransducerDecoder.beam_search(enc, beam=4)
                                           RNN-T beam search, one symbol per frame,
                                           the n-best in one launch (asr_rnnt_beam*);
@@ -167,6 +176,7 @@ EXPORTS = [
     "asr_ctc_lm_create_word",
     "asr_rnnt_create", "asr_rnnt_upload", "asr_rnnt_get_info", "asr_rnnt_destroy", "asr_rnnt_workspace_bytes",
     "asr_rnnt_greedy", "asr_rnnt_greedy_host",
+    "asr_rnnt_create_stateless", "asr_rnnt_context", "asr_rnnt_greedy_stateless", "asr_rnnt_greedy_stateless_host",
     "asr_rnnt_beam_workspace_bytes", "asr_rnnt_beam", "asr_rnnt_beam_host",
     "asr_rnnt_lm_create", "asr_rnnt_lm_destroy", "asr_rnnt_beam_lm_workspace_bytes", "asr_rnnt_beam_lm",
     "asr_rnnt_beam_lm_host",
@@ -339,6 +349,10 @@ def lib() -> ctypes.CDLL:
         "asr_rnnt_destroy": [_vp],
         "asr_rnnt_greedy": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_greedy_host": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_create_stateless": [_vp, _vp, ctypes.POINTER(_vp)],
+        "asr_rnnt_context": [_vp],
+        "asr_rnnt_greedy_stateless": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_greedy_stateless_host": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_beam": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_beam_host": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_lm_create": [_vp, _vp, _vp, _f, _f, _i, ctypes.POINTER(_vp)],
@@ -4128,6 +4142,27 @@ class RnntInfo(ctypes.Structure):
                 ("weight_bytes", ctypes.c_int64)]
 
 
+ASR_RNNT_MAX_CONTEXT = 4
+
+
+class RnntStatelessDesc(ctypes.Structure):
+    """asr_rnnt_stateless_desc."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("V", "blank", "E", "D", "Hp", "J", "act", "max_symbols", "context",
+                                              "start_fill")]
+    L = 0     # what asr_rnnt_get_info reports for a stateless handle
+
+
+class RnntStatelessWeights(ctypes.Structure):
+    """asr_rnnt_stateless_weights: host pointers; w_ctx and b_ctx may be NULL."""
+    _fields_ = [(n, _vp) for n in ("emb", "w_ctx", "b_ctx", "w_enc", "b_enc", "w_pred", "b_pred", "w_out", "b_out")]
+
+
+def rnnt_stateless_desc(V: int, blank: int, E: int, D: int, Hp: int, J: int, act="tanh", max_symbols: int = 1,
+                        context: int = 2, start_fill: int = -1) -> RnntStatelessDesc:
+    return RnntStatelessDesc(V, blank, E, D, Hp, J, RNNT_ACTS[act] if isinstance(act, str) else int(act), max_symbols,
+                             context, start_fill)
+
+
 def rnnt_desc(V: int, blank: int, E: int, D: int, Hp: int, L: int, J: int, act="relu",
               max_symbols: int = 10) -> RnntDesc:
     return RnntDesc(V, blank, E, D, Hp, L, J, RNNT_ACTS[act] if isinstance(act, str) else int(act), max_symbols)
@@ -4146,7 +4181,14 @@ class TransducerDecoder:
     [V, D]; w_ih, w_hh, b_ih, b_hh: lists of L arrays ([in, 4Hp], [Hp, 4Hp],
     [4Hp]); w_enc [E, J], b_enc; w_pred [Hp, J], b_pred; w_out [J, V], b_out.
     labels (optional): label i's string, by which the LM keywords find the LM
-    token of a label when no tok_of_label is given."""
+    token of a label when no tok_of_label is given.
+
+    A stateless predictor (TransducerDecoder.stateless / from_icefall;
+    asr_rnnt_create_stateless) gives the same object: context > 0, the state of
+    decode / decode_host is the int32 context [B, C], and every other method
+    works unchanged."""
+
+    context = 0      # C of a stateless predictor, 0: an LSTM
 
     def __init__(self, desc: RnntDesc, weights: dict, labels: Optional[Sequence[str]] = None):
         self.desc = desc
@@ -4214,6 +4256,90 @@ class TransducerDecoder:
             raise ValueError("the modules' sizes do not chain")
         return cls(d, wt)
 
+    @classmethod
+    def stateless(cls, desc: RnntStatelessDesc, weights: dict,
+                  labels: Optional[Sequence[str]] = None) -> "TransducerDecoder":
+        """A stateless-predictor transducer (asr_rnnt_create_stateless).  weights:
+        fp32 arrays in [in][out] layout: emb [V, D]; w_ctx [C, D, Hp] or None
+        (context 1, D = Hp: no conv); b_ctx [Hp] or None; w_enc [E, J], b_enc;
+        w_pred [Hp, J], b_pred; w_out [J, V], b_out."""
+        self = cls.__new__(cls)
+        self.desc, self.h, self._fuse, self._work, self._uploaded = desc, None, {}, None, False
+        self.labels = list(labels) if labels is not None else None
+        self.context = int(desc.context)
+        d = desc
+        shapes = {"emb": (d.V, d.D), "w_ctx": (d.context, d.D, d.Hp), "b_ctx": (d.Hp,), "w_enc": (d.E, d.J),
+                  "b_enc": (d.J,), "w_pred": (d.Hp, d.J), "b_pred": (d.J,), "w_out": (d.J, d.V), "b_out": (d.V,)}
+        keep, w = {}, RnntStatelessWeights()
+        for name, shape in shapes.items():
+            if name in ("w_ctx", "b_ctx") and weights.get(name) is None:
+                continue
+            a = np.ascontiguousarray(weights[name], dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{name}: shape {a.shape}, expected {shape}")
+            keep[name] = a
+            setattr(w, name, _ptr(a))
+        self.weights = keep
+        h = _vp()
+        check(lib().asr_rnnt_create_stateless(ctypes.byref(desc), ctypes.byref(w), ctypes.byref(h)),
+              "asr_rnnt_create_stateless")
+        self.h = h.value
+        return self
+
+    @classmethod
+    def from_icefall(cls, decoder, joiner, blank=None, activation: str = "tanh", max_symbols: int = 1,
+                     start_fill=None) -> "TransducerDecoder":
+        """From an icefall stateless Decoder and Joiner, duck-typed:
+        decoder.embedding (torch.nn.Embedding), decoder.conv (a Conv1d over the
+        context, groups dividing the dimension; absent or unused when
+        decoder.context_size == 1) and decoder.context_size;
+        joiner.encoder_proj, joiner.decoder_proj, joiner.output_linear
+        (torch.nn.Linear).  The grouped conv weight [Hp, D / groups, C] expands
+        to the dense block-diagonal w_ctx [C, D, Hp].  blank defaults to
+        decoder.blank_id (else 0); start_fill defaults to -1 when the embedding
+        has no padding_idx (Zipformer starts from [-1] * (C - 1) + [blank])
+        and to blank when it has one (the older recipes start from
+        [blank] * C)."""
+        def arr(t):
+            return t.detach().cpu().numpy().astype(np.float32)
+
+        def lin(m):
+            b = arr(m.bias) if m.bias is not None else np.zeros(m.out_features, np.float32)
+            return np.ascontiguousarray(arr(m.weight).T), b
+
+        emb = decoder.embedding
+        C = int(decoder.context_size)
+        if blank is None:
+            blank = int(getattr(decoder, "blank_id", 0))
+        if start_fill is None:
+            start_fill = -1 if getattr(emb, "padding_idx", None) is None else blank
+        wt = {"emb": arr(emb.weight)}
+        D = Hp = emb.embedding_dim
+        conv = getattr(decoder, "conv", None) if C > 1 else None
+        if C > 1 and conv is None:
+            raise ValueError("context_size > 1 needs decoder.conv")
+        if conv is not None:
+            cw = arr(conv.weight)     # [Hp, D / groups, C]
+            Hp, per_in, groups = cw.shape[0], cw.shape[1], int(conv.groups)
+            if cw.shape[2] != C or per_in * groups != D or Hp % groups or getattr(conv, "padding", (0,))[0] != 0:
+                raise ValueError("decoder.conv is not an unpadded Conv1d over the context of the embedding")
+            per_out = Hp // groups
+            w_ctx = np.zeros((C, D, Hp), np.float32)
+            for gi in range(groups):      # output channel o reads the input channels of its group
+                blk = cw[gi * per_out:(gi + 1) * per_out]                        # [per_out, per_in, C]
+                w_ctx[:, gi * per_in:(gi + 1) * per_in, gi * per_out:(gi + 1) * per_out] = blk.transpose(2, 1, 0)
+            wt["w_ctx"] = w_ctx
+            wt["b_ctx"] = arr(conv.bias) if conv.bias is not None else None
+        wt["w_enc"], wt["b_enc"] = lin(joiner.encoder_proj)
+        wt["w_pred"], wt["b_pred"] = lin(joiner.decoder_proj)
+        wt["w_out"], wt["b_out"] = lin(joiner.output_linear)
+        d = rnnt_stateless_desc(emb.num_embeddings, blank, joiner.encoder_proj.in_features, D, Hp,
+                                joiner.encoder_proj.out_features, activation, max_symbols, C, start_fill)
+        if joiner.decoder_proj.in_features != Hp or joiner.decoder_proj.out_features != d.J or \
+                joiner.output_linear.in_features != d.J or joiner.output_linear.out_features != d.V:
+            raise ValueError("the modules' sizes do not chain")
+        return cls.stateless(d, wt)
+
     def info(self) -> dict:
         info = RnntInfo()
         check(lib().asr_rnnt_get_info(self.h, ctypes.byref(info)), "asr_rnnt_get_info")
@@ -4229,13 +4355,24 @@ class TransducerDecoder:
         return int(lib().asr_rnnt_workspace_bytes(self.h, T, B))
 
     def state_shape(self, B: int) -> tuple:
-        """(2, L, B, Hp): h of every layer, then c."""
+        """(2, L, B, Hp): h of every layer, then c.  A stateless predictor: (B, C),
+        the context as int32."""
+        if self.context:
+            return (int(B), self.context)
         return (2, int(self.desc.L), int(B), int(self.desc.Hp))
 
     def decode_device(self, d_enc: int, T: int, B: int, max_out: int, d_tokens: int, d_timesteps: int, d_logp: int,
                       d_count: int, d_total: int, d_work: int, d_lengths: int = 0, d_state_in: int = 0,
                       d_state_out: int = 0, stream: int = 0) -> None:
-        """asr_rnnt_greedy on device pointers: asynchronous on stream."""
+        """asr_rnnt_greedy (a stateless predictor: asr_rnnt_greedy_stateless, the
+        states int32 contexts) on device pointers: asynchronous on stream."""
+        if self.context:
+            check(lib().asr_rnnt_greedy_stateless(self.h, d_enc or None, d_lengths or None, T, B, max_out,
+                                                  d_state_in or None, d_state_out or None, d_tokens or None,
+                                                  d_timesteps or None, d_logp or None, d_count or None,
+                                                  d_total or None, d_work or None, stream or None),
+                  "asr_rnnt_greedy_stateless")
+            return
         check(lib().asr_rnnt_greedy(self.h, d_enc or None, d_lengths or None, T, B, max_out, d_state_in or None,
                                     d_state_out or None, d_tokens or None, d_timesteps or None, d_logp or None,
                                     d_count or None, d_total or None, d_work or None, stream or None),
@@ -4275,9 +4412,10 @@ class TransducerDecoder:
         d_len = _upload(ln, stream) if ln is not None else None
         shape = self.state_shape(B)
         nstate = int(np.prod(shape))
+        sty = np.int32 if self.context else np.float32
         d_sin = None
         if state is not None:
-            st = np.ascontiguousarray(state, dtype=np.float32)
+            st = np.ascontiguousarray(state, dtype=sty)
             if st.shape != shape:
                 raise ValueError(f"state: shape {st.shape}, expected {shape}")
             d_sin = _upload(st, stream)
@@ -4296,7 +4434,7 @@ class TransducerDecoder:
         tok = _download(d_tok, (B, mo), np.int32, stream)
         ts = _download(d_ts, (B, mo), np.int32, stream)
         lp = _download(d_lp, (B, mo), np.float64, stream)
-        new_state = _download(d_sout, shape, np.float32, stream)
+        new_state = _download(d_sout, shape, sty, stream)
         return self._unpack(B, max_out, tok, ts, lp, cnt, total), new_state, cnt
 
     def decode_host(self, enc, lengths=None, state=None, max_out=None, gaps: bool = False):
@@ -4305,19 +4443,21 @@ class TransducerDecoder:
         utterance's walk."""
         enc, ln, T, B, max_out = self._prepare(enc, lengths, max_out)
         shape = self.state_shape(B)
+        sty = np.int32 if self.context else np.float64
+        fn = lib().asr_rnnt_greedy_stateless_host if self.context else lib().asr_rnnt_greedy_host
         sin = None
         if state is not None:
-            sin = np.ascontiguousarray(state, dtype=np.float64)
+            sin = np.ascontiguousarray(state, dtype=sty)
             if sin.shape != shape:
                 raise ValueError(f"state: shape {sin.shape}, expected {shape}")
-        sout = np.zeros(shape, np.float64)
+        sout = np.zeros(shape, sty)
         mo = max(max_out, 1)
         tok, ts, lp = np.zeros((B, mo), np.int32), np.zeros((B, mo), np.int32), np.zeros((B, mo), np.float64)
         cnt, total, gap = np.zeros(B, np.int32), np.zeros(B, np.float64), np.zeros(B, np.float64)
-        check(lib().asr_rnnt_greedy_host(self.h, _ptr(enc), _ptr(ln) if ln is not None else None, T, B, max_out,
-                                         _ptr(sin) if sin is not None else None, _ptr(sout), _ptr(tok), _ptr(ts),
-                                         _ptr(lp), _ptr(cnt), _ptr(total), _ptr(gap) if gaps else None),
-              "asr_rnnt_greedy_host")
+        check(fn(self.h, _ptr(enc), _ptr(ln) if ln is not None else None, T, B, max_out,
+                 _ptr(sin) if sin is not None else None, _ptr(sout), _ptr(tok), _ptr(ts), _ptr(lp), _ptr(cnt),
+                 _ptr(total), _ptr(gap) if gaps else None),
+              "asr_rnnt_greedy_stateless_host" if self.context else "asr_rnnt_greedy_host")
         res = self._unpack(B, max_out, tok, ts, lp, cnt, total), sout, cnt
         return res + (gap,) if gaps else res
 

@@ -361,6 +361,7 @@ static int rnnt_greedy_check(const asr_rnnt* h, const void* enc, int T, int B, i
     if (!h || !enc || !count || !total || T <= 0 || B <= 0 || max_out < 0) return ASR_ERR_ARG;
     if (max_out > 0 && (!tokens || !timesteps || !logp)) return ASR_ERR_ARG;
     if ((long)T * B > INT_MAX || (long)T * (h->d.max_symbols + 1) >= INT_MAX) return ASR_ERR_UNSUPPORTED;
+    if (h->C) return ASR_ERR_UNSUPPORTED;   // a stateless handle: asr_rnnt_greedy_stateless
     return ASR_OK;
 }
 
@@ -429,6 +430,7 @@ int asr_rnnt_get_info(const asr_rnnt_t* h, asr_rnnt_info* info) {
 int asr_rnnt_upload(asr_rnnt_t* h) {
     if (!h) return ASR_ERR_ARG;
     if (h->d_blob) return ASR_OK;
+    if (h->C) return asr::rnnt_ctx_upload(h);   // a stateless handle: the context tables
     const asr_rnnt_desc& d = h->d;
     const size_t H4 = 4 * (size_t)d.Hp;
     // one allocation, every array at a 16-byte aligned offset (in floats: a multiple of 4)
@@ -487,6 +489,8 @@ int asr_rnnt_upload(asr_rnnt_t* h) {
 
 size_t asr_rnnt_workspace_bytes(const asr_rnnt_t* h, int T, int B) {
     if (!h || T <= 0 || B <= 0 || (long)T * B > INT_MAX) return 0;
+    if (h->C)   // a stateless handle: f, then g [16][J] per 16 utterances, to a multiple of 32 utterances
+        return ((size_t)T * B + ((size_t)B + 31) / 32 * 32) * h->d.J * sizeof(float);
     const size_t tiles = ((size_t)B + asr::RT_ROWS - 1) / asr::RT_ROWS;
     // f [T*B][J], then per workgroup c [L][16][Hp] and g [16][J]
     return ((size_t)T * B * h->d.J + tiles * asr::RT_ROWS * ((size_t)h->d.L * h->d.Hp + h->d.J)) * sizeof(float);

@@ -71,7 +71,8 @@ static RaLayout ra_layout(const asr_rnnt_desc& d, int T, int B, int N, int mtl) 
     RaLayout o{};
     size_t at = 0;
     o.f = at;    at += (size_t)T * B * d.J * 4;
-    o.p = at;    at += (NU * 4 * d.Hp + (size_t)N * d.Hp) * 4;   // asr_lstm_workspace_bytes(U1, N, Hp)
+    // asr_lstm_workspace_bytes(U1, N, Hp); a stateless handle (d.L = 0): p [NU][Hp], and no hid
+    o.p = at;    at += d.L ? (NU * 4 * d.Hp + (size_t)N * d.Hp) * 4 : NU * d.Hp * 4;
     o.hid = at;  at += (size_t)d.L * NU * d.Hp * 4;
     o.g = at;    at += NU * d.J * 4;
     o.lpb = at;  at += ra_up4((size_t)N * T * U1) * 4;
@@ -85,7 +86,7 @@ static RaLayout ra_layout(const asr_rnnt_desc& d, int T, int B, int N, int mtl) 
 struct RaArgs {
     const float* f;      // [T*B][J]
     const float* g;      // [(mtl+1)*N][J], row u * N + n
-    const float* embw;   // [V][4Hp]
+    const float* embw;   // [V][4Hp]; NULL for a stateless handle
     float* P;            // [(mtl+1)*N][4Hp]
     const float* wout;
     const float* bout;
@@ -133,6 +134,7 @@ __global__ __launch_bounds__(256) void rnnt_align_prep_kernel(const RaArgs p) {
         p.ok[n] = !(bad || b < 0 || (len == 0 && U > 0) || (p.topology == ASR_RNNT_LATTICE_ONE_PER_FRAME && U > len));
     }
     const int q4 = p.Hp;   // float4s of a row of 4Hp floats
+    if (!p.embw) return;   // a stateless handle: rnnt_ctx_align_rows makes p
     for (int x = tid; x < (p.mtl + 1) * q4; x += 256) {
         const int u = x / q4, k = x - u * q4;
         int tok = p.blank;
@@ -414,7 +416,7 @@ static int ra_check(const asr_rnnt* h, const void* enc, int T, int B, const void
     if (mtl > RA_MAX_U) return ASR_ERR_UNSUPPORTED;
     const long U1 = mtl + 1, tiles = ((long)T * U1 + 15) / 16;
     if ((long)T * B > INT_MAX || (long)N * U1 > INT_MAX || (long)T * U1 > INT_MAX || (long)N * tiles > INT_MAX ||
-        (long)N * 16 * h->d.Hp > RA_LSTM_OOB)
+        (!h->C && (long)N * 16 * h->d.Hp > RA_LSTM_OOB))   // a stateless handle runs no recurrence
         return ASR_ERR_UNSUPPORTED;
     return ASR_OK;
 }
@@ -471,7 +473,8 @@ int asr_rnnt_align(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_len
     asr::RaArgs a{};
     // the model's part from the one place that knows the handle; the kernels' argument layout stays their own
     const asr::RtNet net = asr::rnnt_net(h);
-    a.f = f; a.g = gbuf; a.embw = net.embw; a.P = P; a.wout = net.wout; a.bout = net.bout;
+    // a stateless handle has no Emb.W_ih (RtNet::tab shares embw's storage): NULL tells the prep kernel so
+    a.f = f; a.g = gbuf; a.embw = h->C ? nullptr : net.embw; a.P = P; a.wout = net.wout; a.bout = net.bout;
     a.lengths = d_lengths; a.targets = d_targets; a.ldt = ldt; a.target_lengths = d_target_lengths; a.utt = d_utt;
     a.lens1 = (int32_t*)(wk + lay.meta);
     a.ok = a.lens1 + N;
@@ -485,10 +488,14 @@ int asr_rnnt_align(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_len
     // 2. the predictor over the N targets, then g = h_top.W_pred + b_pred
     hipLaunchKernelGGL(asr::rnnt_align_prep_kernel, dim3((unsigned)N), dim3(256), 0, st, a);
     ASR_LAUNCH_TRY();
-    if (int rc = asr_lstm_recur_fwd(P, nullptr, nullptr, h->d_whh[0], h->d_bih[0], h->d_bhh[0], hid, d.Hp, nullptr,
-                                    nullptr, a.lens1, P, U1, N, d.Hp, 0, s))
-        return rc;
     const float* htop = hid;
+    if (h->C) {   // a stateless predictor: p of every position by row gathers
+        if (int rc = asr::rnnt_ctx_align_rows(h, d_targets, ldt, d_target_lengths, N, max_target_len, P, st)) return rc;
+        htop = P;
+    } else if (int rc = asr_lstm_recur_fwd(P, nullptr, nullptr, h->d_whh[0], h->d_bih[0], h->d_bhh[0], hid, d.Hp,
+                                           nullptr, nullptr, a.lens1, P, U1, N, d.Hp, 0, s)) {
+        return rc;
+    }
     if (d.L == 2) {
         float* const hid1 = hid + (size_t)U1 * N * d.Hp;
         if (int rc = asr_lstm_fwd(hid, nullptr, nullptr, h->d_wih1, h->d_whh[1], h->d_bih[1], h->d_bhh[1], hid1, d.Hp,
@@ -531,8 +538,7 @@ int asr_rnnt_align_host(const asr_rnnt_t* h, const float* h_enc, const int32_t* 
     const bool topo1 = topology == ASR_RNNT_LATTICE_ONE_PER_FRAME;
     try {
         asr::RnntHost m(*h);
-        const size_t LH = (size_t)d.L * d.Hp;
-        std::vector<double> hs(LH), cs(LH), gs, logit(d.V), lpb, lpy, a, v, cb, cy, vb, vy;
+        std::vector<double> hs(m.nh()), cs(m.nc()), gs, logit(d.V), lpb, lpy, a, v, cb, cy, vb, vy;
         std::vector<unsigned char> bits;
         for (int n = 0; n < N; n++) {
             const int U = std::min(std::max(h_target_lengths[n], 0), max_target_len), U1 = U + 1;
@@ -552,10 +558,9 @@ int asr_rnnt_align_host(const asr_rnnt_t* h, const float* h_enc, const int32_t* 
             } else if (feasible) {
                 // the predictor, teacher-forced: g_u for u = 0 .. U
                 gs.assign((size_t)U1 * d.J, 0.0);
-                std::fill(hs.begin(), hs.end(), 0.0);
-                std::fill(cs.begin(), cs.end(), 0.0);
                 for (int u = 0; u <= U; u++) {
-                    m.step(u ? tgt[u - 1] : d.blank, hs.data(), cs.data());
+                    if (u) m.step(tgt[u - 1], hs.data(), cs.data());
+                    else m.start(hs.data(), cs.data());
                     m.pred_proj(hs.data());
                     std::copy(m.g.begin(), m.g.end(), gs.begin() + (size_t)u * d.J);
                 }

@@ -58,6 +58,13 @@
 // A row kept by blank, at whatever rank, keeps its slot; rows that took a token
 // get the slots nobody kept.  Nothing of this exists in the LM = false
 // instantiation.
+//
+// Stateless predictors (asr_rnnt_create_stateless): the kernel's
+// second template parameter is the predictor kind.  With RT_PRED_CTX a row's
+// state is its context of C tokens in the small area, the step is rt_ctx_step
+// (row gathers, no product), there is one p buffer where the LSTM has 2 L h
+// buffers and the slice holds no c.  Those instantiations are compiled in
+// rnnt_stateless_beam.hip, which includes this file for the kernel alone.
 #include "lm_tables.h"
 #include "rnnt_common.h"
 
@@ -141,11 +148,16 @@ __device__ __forceinline__ int rb_here(int x) {
 // Horner loops.  Inlined as they stand, the chains' ~25 fp64 constants are
 // hoisted into VGPRs for the whole frame loop, which then spills; a merge is one
 // thread's work a few times per utterance, so the rolled form costs nothing.
-__constant__ double RB_EXP_C[14] = {1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0,
+#ifdef ASR_RNNT_BEAM_KERNEL_ONLY
+#define RB_TABLE static __constant__   // rnnt_stateless_beam.hip's own copy beside this file's object
+#else
+#define RB_TABLE __constant__
+#endif
+RB_TABLE double RB_EXP_C[14] = {1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0,
                                     1.0 / 362880.0,     1.0 / 40320.0,     1.0 / 5040.0,     1.0 / 720.0,
                                     1.0 / 120.0,        1.0 / 24.0,        1.0 / 6.0,        0.5,
                                     1.0,                1.0};
-__constant__ double RB_LOG_C[10] = {2.0 / 21.0, 2.0 / 19.0, 2.0 / 17.0, 2.0 / 15.0, 2.0 / 13.0,
+RB_TABLE double RB_LOG_C[10] = {2.0 / 21.0, 2.0 / 19.0, 2.0 / 17.0, 2.0 / 15.0, 2.0 / 13.0,
                                     2.0 / 11.0, 2.0 / 9.0,  2.0 / 7.0,  2.0 / 5.0,  2.0 / 3.0};
 __device__ __forceinline__ double rb_lse2(double a, double b) {
     if (a == -INFINITY) return b;
@@ -197,7 +209,9 @@ __device__ __forceinline__ bool rb_same_seq(const int4* nodes, int na, int nb, i
     return true;
 }
 
-template <bool LM>
+constexpr int RT_PRED_LSTM = 0, RT_PRED_CTX = 1;
+
+template <bool LM, int PRED>
 __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs p, const BeamLmArgs q) {
     extern __shared__ __attribute__((aligned(16))) float rb_lds[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -207,9 +221,9 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
     const int LDH = Hp + 4, LDJ = J + 4;
     const int lgR = p.lgR, R = 1 << lgR, U = RT_ROWS >> lgR;
     const int b0 = blockIdx.x * U;
-    // LDS: h [2][L][16][LDH], z [16][LDJ], then the small area
+    // LDS: h [2][L][16][LDH] (a stateless predictor: p [16][LDH]), z [16][LDJ], then the small area
     float* const hbuf = rb_lds;
-    float* const zbuf = hbuf + (size_t)2 * L * RT_ROWS * LDH;
+    float* const zbuf = hbuf + (PRED == RT_PRED_CTX ? (size_t)RT_ROWS * LDH : (size_t)2 * L * RT_ROWS * LDH);
     float* const small = zbuf + (size_t)RT_ROWS * LDJ;
     // 8-byte items first: [16] each but the candidates' [16][16]
     double* const row_score = reinterpret_cast<double*>(small);
@@ -252,6 +266,7 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
     int* const lm_m = ent_slot + RT_ROWS;         // tokens of context in lm_ctx
     int* const fill_list = lm_m + RT_ROWS;        // the rows to fill, then their number at [16]
     int* const lm_ctx = fill_list + 2 * RT_ROWS;  // [16][LM_CTX]: the row's last LM tokens, oldest first
+    int* const row_ctx = lm_ctx + RT_ROWS * LM_CTX;   // RT_PRED_CTX only, [16][RT_CTX]: the predictor's context
     auto hb = [&](int buf, int l) { return hbuf + ((size_t)buf * L + l) * RT_ROWS * LDH; };
     // this workgroup's slice: c [2][L][16][Hp], g [16][J], logits [16][V]
     const size_t csz = (size_t)L * RT_ROWS * Hp;
@@ -277,6 +292,8 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
             row_L[tid] = 0.0;
             row_slot[tid] = tid;
         }
+        if constexpr (PRED == RT_PRED_CTX)
+            for (int i = 0; i < net.C; i++) row_ctx[tid * RT_CTX + i] = rt_ctx_start(net.C, i, net.start_fill, net.blank);
     }
     for (int x = tid; x < L * RT_ROWS * Hp; x += 64 * RT_WAVES) {
         const int l = x / (RT_ROWS * Hp), row = (x / Hp) % RT_ROWS, n = x % Hp;
@@ -330,11 +347,18 @@ __global__ __launch_bounds__(64 * RT_WAVES) void rnnt_beam_kernel(const BeamArgs
                 }
             }
             // Predictor step by parent row; rows without a token copy their parent's h and c.
-            rt_lstm_step(net, hb, cur, cw + (size_t)cur * csz, cw + (size_t)(cur ^ 1) * csz,
-                         [&](int row) { return row_prow[row]; }, [&](int row) { return row_tok[row]; }, w, g, c);
-            cur ^= 1;
+            if constexpr (PRED == RT_PRED_CTX) {
+                // the context of the parent row, the token shifted in; at the start no token, the first p (-2)
+                rt_ctx_step(net, hbuf, row_ctx, [&](int row) { return row_prow[row]; },
+                            [&](int row) { return it == 0 ? -2 : row_tok[row]; }, tid);
+            } else {
+                rt_lstm_step(net, hb, cur, cw + (size_t)cur * csz, cw + (size_t)(cur ^ 1) * csz,
+                             [&](int row) { return row_prow[row]; }, [&](int row) { return row_tok[row]; }, w, g, c);
+                cur ^= 1;
+            }
             // g = h_top.W_pred + b_pred of every row
-            rt_sweep<1, false>(hb(cur, L - 1) + c * LDH + 4 * g, 0, Hp >> 4, net.wpred, net.bpred, J, w, g, c,
+            const float* const htop = PRED == RT_PRED_CTX ? hbuf : hb(cur, L - 1);
+            rt_sweep<1, false>(htop + c * LDH + 4 * g, 0, Hp >> 4, net.wpred, net.bpred, J, w, g, c,
                                [&](int, int n, f32x4 x) {
 #pragma unroll
                                    for (int j = 0; j < 4; j++) gw[(unsigned)((4 * g + j) * J + n)] = x[j];
@@ -662,7 +686,7 @@ struct BeamHyp {
     std::vector<int32_t> ys, ts;
     double score = 0.0;           // acoustic
     double W = 0.0, Lg = 0.0;     // LM weight and log10 sum of ys
-    std::vector<double> h, c, g;
+    std::vector<double> h, c, g;    // the predictor state as RnntHost keeps it, and g
     std::vector<double> lmv;      // LM: lm_position's value of ys + [v], every label v
 };
 struct BeamCand {
@@ -675,8 +699,12 @@ struct BeamCand {
     bool dead;
 };
 
+// The search's one launch for a stateless handle (rnnt_stateless_beam.hip): the RT_PRED_CTX instantiations.
+int rnnt_beam_ctx_launch(const BeamArgs& a, const BeamLmArgs& q, bool lm, unsigned tiles, size_t lds, hipStream_t st);
+
 }  // namespace asr
 
+#ifndef ASR_RNNT_BEAM_KERNEL_ONLY
 // The fusion handle: a model, an LM and how they combine.  Both must outlive it.
 struct asr_rnnt_lm {
     const asr_rnnt* model = nullptr;
@@ -712,7 +740,7 @@ static int rnnt_beam_launch(const asr_rnnt* h, const asr_rnnt_lm* z, const LmTab
                             int32_t* d_timesteps, int32_t* d_len, double* d_score, double* d_total, double* d_lm_log10,
                             int32_t* d_ntok, int32_t* d_nhyp, void* d_work, asr_stream_t s) {
     const asr_rnnt_desc& d = h->d;
-    const long lds = rnnt_lds_bytes(d.L, d.Hp, d.J, RB_LDS_SMALL);
+    const long lds = rnnt_lds_of(h, RB_LDS_SMALL);
     float* f = (float*)d_work;
     if (int rc = rnnt_enc_launch(h, d_enc, T, B, f, asr_stream(s))) return rc;
     const int lgR = asr::rb_log2_rows(K), U = asr::RT_ROWS >> lgR;
@@ -737,15 +765,18 @@ static int rnnt_beam_launch(const asr_rnnt* h, const asr_rnnt_lm* z, const LmTab
         q.aln10 = z->aln10;
         q.beta = z->beta;
         q.flags = z->flags;
+    }
+    if (h->C) return rnnt_beam_ctx_launch(a, q, z != nullptr, (unsigned)tiles, (size_t)lds, asr_stream(s));
+    if (z) {
         static AsrAttrOnce attr;
-        if (int rc = attr.set((const void*)rnnt_beam_kernel<true>, RT_LDS_MAX)) return rc;
-        hipLaunchKernelGGL(rnnt_beam_kernel<true>, dim3((unsigned)tiles), dim3(64 * RT_WAVES), (size_t)lds, asr_stream(s),
-                           a, q);
+        if (int rc = attr.set((const void*)rnnt_beam_kernel<true, RT_PRED_LSTM>, RT_LDS_MAX)) return rc;
+        hipLaunchKernelGGL((rnnt_beam_kernel<true, RT_PRED_LSTM>), dim3((unsigned)tiles), dim3(64 * RT_WAVES), (size_t)lds,
+                           asr_stream(s), a, q);
     } else {
         static AsrAttrOnce attr;
-        if (int rc = attr.set((const void*)rnnt_beam_kernel<false>, RT_LDS_MAX)) return rc;
-        hipLaunchKernelGGL(rnnt_beam_kernel<false>, dim3((unsigned)tiles), dim3(64 * RT_WAVES), (size_t)lds, asr_stream(s),
-                           a, q);
+        if (int rc = attr.set((const void*)rnnt_beam_kernel<false, RT_PRED_LSTM>, RT_LDS_MAX)) return rc;
+        hipLaunchKernelGGL((rnnt_beam_kernel<false, RT_PRED_LSTM>), dim3((unsigned)tiles), dim3(64 * RT_WAVES), (size_t)lds,
+                           asr_stream(s), a, q);
     }
     ASR_LAUNCH_TRY();
     return ASR_OK;
@@ -765,7 +796,7 @@ int asr_rnnt_beam(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_leng
     if (int rc = asr::rnnt_beam_check(h, d_enc, T, B, K, nbest, max_out, d_tokens, d_timesteps, d_len, d_score, d_nhyp))
         return rc;
     if (!d_work) return ASR_ERR_ARG;
-    if (asr::rnnt_lds_bytes(h->d.L, h->d.Hp, h->d.J, asr::RB_LDS_SMALL) > asr::RT_LDS_MAX) return ASR_ERR_UNSUPPORTED;
+    if (asr::rnnt_lds_of(h, asr::RB_LDS_SMALL) > asr::RT_LDS_MAX) return ASR_ERR_UNSUPPORTED;
     if (!h->d_blob) return ASR_ERR_STATE;
     return asr::rnnt_beam_launch(h, nullptr, nullptr, d_enc, d_lengths, T, B, K, nbest, max_out, d_tokens, d_timesteps,
                                  d_len, d_score, nullptr, nullptr, nullptr, d_nhyp, d_work, s);
@@ -804,7 +835,6 @@ static int rnnt_beam_host_run(const asr_rnnt* h, const asr_rnnt_lm* z, const flo
                               int32_t* h_len, double* h_total, double* h_am, double* h_lm_log10, int32_t* h_ntok,
                               int32_t* h_nhyp, double* h_margin) {
     const asr_rnnt_desc& d = h->d;
-    const size_t LH = (size_t)d.L * d.Hp;
     const LmTables* lt = nullptr;
     if (z) {
         const LmTables* dev;
@@ -816,9 +846,9 @@ static int rnnt_beam_host_run(const asr_rnnt* h, const asr_rnnt_lm* z, const flo
         std::vector<BeamCand> cands, kept;
         for (int b = 0; b < B; b++) {
             std::vector<BeamHyp> A(1);
-            A[0].h.assign(LH, 0.0);
-            A[0].c.assign(LH, 0.0);
-            m.step(d.blank, A[0].h.data(), A[0].c.data());
+            A[0].h.assign(m.nh(), 0.0);
+            A[0].c.assign(m.nc(), 0.0);
+            m.start(A[0].h.data(), A[0].c.data());
             m.pred_proj(A[0].h.data());
             A[0].g = m.g;
             if (z) rnnt_lm_row(*z, *lt, A[0].ys, d.V, d.blank, A[0].lmv);
@@ -1005,7 +1035,7 @@ int asr_rnnt_beam_lm(asr_rnnt_lm_t* z, const float* d_enc, const int32_t* d_leng
     if (int rc = asr::rnnt_beam_check(h, d_enc, T, B, K, nbest, max_out, d_tokens, d_timesteps, d_len, d_total, d_nhyp))
         return rc;
     if (!d_work) return ASR_ERR_ARG;
-    if (asr::rnnt_lds_bytes(h->d.L, h->d.Hp, h->d.J, asr::RB_LDS_SMALL) > asr::RT_LDS_MAX) return ASR_ERR_UNSUPPORTED;
+    if (asr::rnnt_lds_of(h, asr::RB_LDS_SMALL) > asr::RT_LDS_MAX) return ASR_ERR_UNSUPPORTED;
     const asr::LmTables *host, *dev;
     if (!h->d_blob || !asr_internal_lm_tables(z->lm, &host, &dev)) return ASR_ERR_STATE;
     if (!z->d_tok) {   // once per handle
@@ -1036,3 +1066,4 @@ int asr_rnnt_beam_lm_host(const asr_rnnt_lm_t* z, const float* h_enc, const int3
 }
 
 }  // extern "C"
+#endif  // ASR_RNNT_BEAM_KERNEL_ONLY

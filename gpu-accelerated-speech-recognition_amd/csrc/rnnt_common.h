@@ -4,8 +4,8 @@
 // device the MFMA column-tile product with its register ring (rt_mma), the
 // schedule of the column tiles over the waves (rt_sweep), the running (max,
 // argmax, sum-exp) of a row with its reduction (RtTop, rt_row_partial,
-// rt_row_total) and the LSTM predictor step (rt_lstm_step); and the fp64 host
-// model.  A row's bits depend on the model's shape only, so the k order and the
+// rt_row_total), the LSTM predictor step (rt_lstm_step) and the stateless
+// predictor's (rt_ctx_gather, rt_ctx_step); and the fp64 host model.  A row's bits depend on the model's shape only, so the k order and the
 // tile-to-wave map are the same in every kernel.  The beam kernel calls all of
 // it; rnnt_greedy_kernel and rnnt_joint_kernel call rt_mma and keep their own
 // text of the schedule, the reduction and the step, for a measured reason
@@ -23,6 +23,10 @@ struct asr_rnnt {
     asr_rnnt_desc d{};
     std::vector<float> emb, wih[ASR_RNNT_MAX_LAYERS], whh[ASR_RNNT_MAX_LAYERS], bih[ASR_RNNT_MAX_LAYERS],
         bhh[ASR_RNNT_MAX_LAYERS], wenc, benc, wpred, bpred, wout, bout;
+    // stateless predictor (asr_rnnt_create_stateless, rnnt_stateless.hip): d.L = 0, C tokens of context
+    int C = 0, start_fill = 0;
+    bool conv = false;               // false: C = 1 without W_ctx, T_0 = Emb
+    std::vector<float> wctx, bctx;   // [C][D][Hp]; [Hp], zeros when none was given
     int lds_bytes = 0;
     int64_t weight_bytes = 0;
     // device copy (asr_rnnt_upload): one allocation
@@ -30,6 +34,7 @@ struct asr_rnnt {
     const float *d_embw = nullptr, *d_wih1 = nullptr, *d_whh[ASR_RNNT_MAX_LAYERS] = {}, *d_bih[ASR_RNNT_MAX_LAYERS] = {},
                 *d_bhh[ASR_RNNT_MAX_LAYERS] = {}, *d_wenc = nullptr, *d_benc = nullptr, *d_wpred = nullptr,
                 *d_bpred = nullptr, *d_wout = nullptr, *d_bout = nullptr;
+    const float *d_tab = nullptr, *d_bctx = nullptr;   // stateless: T_c = Emb.W_ctx[c], [C][V][Hp]
 };
 
 namespace asr {
@@ -47,13 +52,29 @@ constexpr int RT_LDS_MAX = 160 * 1024;
 static long rnnt_lds_bytes(int L, int Hp, int J, int small) {
     return ((long)2 * L * (Hp + 4) + (J + 4)) * RT_ROWS * 4 + small;
 }
+// The same of a stateless handle: p [16][Hp + 4] in the place of the h buffers.
+static long rnnt_ctx_lds_bytes(int Hp, int J, int small) { return ((long)(Hp + 4) + (J + 4)) * RT_ROWS * 4 + small; }
+static long rnnt_lds_of(const asr_rnnt* h, int small) {
+    return h->C ? rnnt_ctx_lds_bytes(h->d.Hp, h->d.J, small) : rnnt_lds_bytes(h->d.L, h->d.Hp, h->d.J, small);
+}
 
 // The model as the kernels take it: the device pointers of an uploaded handle and its shape.
+// A stateless predictor (C > 0 in the handle, L = 0 here) keeps its fields in the storage of LSTM ones it has no
+// use for, so that the argument layout of the LSTM kernels is what it was: the context tables [C][V][Hp] in embw's
+// place, and C and the start fill in wih1's.
 struct RtNet {
-    const float* embw;       // [V][4Hp] = Emb.W_ih of layer 0
-    const float* wih1;       // [Hp][4Hp], layer 1 (L = 2)
+    union {
+        const float* embw;   // [V][4Hp] = Emb.W_ih of layer 0
+        const float* tab;    // stateless: T_c = Emb.W_ctx[c], [C][V][Hp]
+    };
+    union {
+        const float* wih1;   // [Hp][4Hp], layer 1 (L = 2)
+        struct {
+            int C, start_fill;   // stateless
+        };
+    };
     const float* whh[2];
-    const float* bih[2];
+    const float* bih[2];     // stateless: bih[0] is b_ctx [Hp]
     const float* bhh[2];
     const float* wpred;
     const float* bpred;
@@ -72,6 +93,9 @@ static RtNet rnnt_net(const asr_rnnt* h) {
     }
     n.wpred = h->d_wpred; n.bpred = h->d_bpred; n.wout = h->d_wout; n.bout = h->d_bout;
     n.Hp = h->d.Hp; n.J = h->d.J; n.V = h->d.V; n.L = h->d.L; n.blank = h->d.blank; n.act = h->d.act;
+    if (h->C) {
+        n.tab = h->d_tab; n.bih[0] = h->d_bctx; n.C = h->C; n.start_fill = h->start_fill;
+    }
     return n;
 }
 
@@ -299,12 +323,71 @@ __device__ __forceinline__ void rt_lstm_step(const RtNet& net, Hb hb, int cur, c
     }
 }
 
+// The stateless predictor.  A row's state is its context: the
+// last C tokens, oldest first, -1 for none, at ctx[row * RT_CTX + i].
+constexpr int RT_CTX = ASR_RNNT_MAX_CONTEXT;
+
+// Entry i of the start context (start_fill, ..., start_fill, blank).
+__host__ __device__ __forceinline__ int rt_ctx_start(int C, int i, int start_fill, int blank) {
+    return i == C - 1 ? blank : start_fill;
+}
+
+// p[row] = relu(T_0[y_0] + ... + T_{C-1}[y_{C-1}] + b_ctx) of the rows with
+// need(row), by all 512 threads, a float4 of a row each: C row gathers from L2,
+// no product.  The sum runs in ascending c, then the bias; y < 0 adds nothing.
+// A row's bits depend on its context only.  No barrier.
+template <class Need>
+__device__ __forceinline__ void rt_ctx_gather(const RtNet& net, float* p, const int* ctx, int rows, Need need, int tid) {
+    const int Hp = net.Hp, q4 = Hp >> 2, LDH = Hp + 4;
+    for (int x = tid; x < rows * q4; x += 64 * RT_WAVES) {
+        const int row = x / q4, k = x - row * q4;
+        if (!need(row)) continue;
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int i = 0; i < net.C; i++) {
+            const int y = ctx[row * RT_CTX + i];
+            if (y < 0) continue;
+            const float4 t = reinterpret_cast<const float4*>(net.tab + ((size_t)i * net.V + y) * Hp)[k];
+            s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
+        }
+        const float4 b = reinterpret_cast<const float4*>(net.bih[0])[k];
+        s.x = fmaxf(s.x + b.x, 0.f); s.y = fmaxf(s.y + b.y, 0.f);
+        s.z = fmaxf(s.z + b.z, 0.f); s.w = fmaxf(s.w + b.w, 0.f);
+        *reinterpret_cast<float4*>(p + row * LDH + 4 * k) = s;
+    }
+}
+
+// One stateless predictor step of the workgroup's 16 rows, rt_lstm_step's
+// calling shape.  New row r takes the context of row prow(r); with tok(r) >= 0
+// it shifts the token in.  p is a function of the context alone, so nothing of
+// p is copied: a row whose context changed (a token, another parent, or
+// tok(r) < -1: the start) gathers its p again, and a row that kept its context
+// keeps its p untouched.  One p buffer, no second state buffer.  Ends behind a
+// barrier.
+template <class Prow, class Tok>
+__device__ __forceinline__ void rt_ctx_step(const RtNet& net, float* p, int* ctx, Prow prow, Tok tok, int tid) {
+    const int row = tid / RT_CTX, i = tid % RT_CTX;
+    int y = -1;
+    if (tid < RT_ROWS * RT_CTX && i < net.C) {
+        const int pr = prow(row), tk = tok(row);
+        y = tk >= 0 ? (i == net.C - 1 ? tk : ctx[pr * RT_CTX + i + 1]) : ctx[pr * RT_CTX + i];
+    }
+    __syncthreads();   // every parent's context was read
+    if (tid < RT_ROWS * RT_CTX && i < net.C) ctx[tid] = y;
+    __syncthreads();
+    rt_ctx_gather(net, p, ctx, RT_ROWS, [&](int r) { return tok(r) != -1 || prow(r) != r; }, tid);
+    __syncthreads();   // the new p, before g reads it
+}
+
 // ---------------------------------------------------------------------------
 // Host model: one thread, fp64 accumulation from the fp32 weights.
 // ---------------------------------------------------------------------------
 struct RnntHost {
     const asr_rnnt& m;
     std::vector<double> gates, gx, x, g, f, z;
+    // The predictor state of the twins: LSTM h, c [L][Hp] each; stateless h = p [Hp], c = the context [C]
+    // (token ids as doubles).
+    size_t nh() const { return m.C ? (size_t)m.d.Hp : (size_t)m.d.L * m.d.Hp; }
+    size_t nc() const { return m.C ? (size_t)m.C : (size_t)m.d.L * m.d.Hp; }
     explicit RnntHost(const asr_rnnt& mm) : m(mm) {
         const int in = std::max(m.d.D, m.d.Hp);
         gates.resize(4 * (size_t)m.d.Hp);
@@ -324,9 +407,47 @@ struct RnntHost {
         }
     }
     static double sigmoid(double v) { return 1.0 / (1.0 + std::exp(-v)); }
-    // one predictor step on Emb[tok]; h, c: [L][Hp]
+    // stateless: p = relu(sum_c Emb[y_c].W_ctx[c] + b_ctx) of the context c, ascending c, then the bias;
+    // Emb[y].W_ctx in fp64 from the fp32 weights, never through an fp32 table
+    void ctx_pred(const double* c, double* p) {
+        const int Hp = m.d.Hp, D = m.d.D;
+        for (int n = 0; n < Hp; n++) p[n] = 0.0;
+        for (int i = 0; i < m.C; i++) {
+            const int y = (int)c[i];
+            if (y < 0) continue;
+            for (int k = 0; k < D; k++) x[k] = (double)m.emb[(size_t)y * D + k];
+            if (!m.conv) {
+                for (int n = 0; n < Hp; n++) p[n] += x[n];
+            } else {
+                matvec(x.data(), m.wctx.data() + (size_t)i * D * Hp, D, Hp, gx.data());
+                for (int n = 0; n < Hp; n++) p[n] += gx[n];
+            }
+        }
+        for (int n = 0; n < Hp; n++) {
+            const double v = p[n] + (double)m.bctx[n];
+            p[n] = v > 0.0 ? v : 0.0;
+        }
+    }
+    // the state before the first token: LSTM h = c = 0 stepped on Emb[blank]; stateless the start context
+    void start(double* h, double* c) {
+        if (m.C) {
+            for (int i = 0; i < m.C; i++) c[i] = (double)rt_ctx_start(m.C, i, m.start_fill, m.d.blank);
+            ctx_pred(c, h);
+            return;
+        }
+        std::fill(h, h + nh(), 0.0);
+        std::fill(c, c + nc(), 0.0);
+        step(m.d.blank, h, c);
+    }
+    // one predictor step on Emb[tok]; h, c: [L][Hp] (stateless: the context shifts, p follows)
     void step(int tok, double* h, double* c) {
         const int Hp = m.d.Hp;
+        if (m.C) {
+            for (int i = 0; i + 1 < m.C; i++) c[i] = c[i + 1];
+            c[m.C - 1] = (double)tok;
+            ctx_pred(c, h);
+            return;
+        }
         int in = m.d.D;
         for (int k = 0; k < in; k++) x[k] = (double)m.emb[(size_t)tok * in + k];
         for (int l = 0; l < m.d.L; l++) {
@@ -346,7 +467,7 @@ struct RnntHost {
         }
     }
     void pred_proj(const double* h) {
-        matvec(h + (size_t)(m.d.L - 1) * m.d.Hp, m.wpred.data(), m.d.Hp, m.d.J, g.data());
+        matvec(h + (m.C ? 0 : (size_t)(m.d.L - 1) * m.d.Hp), m.wpred.data(), m.d.Hp, m.d.J, g.data());
         for (int n = 0; n < m.d.J; n++) g[n] += (double)m.bpred[n];
     }
     void enc_proj(const float* e) {
@@ -364,5 +485,11 @@ struct RnntHost {
         for (int v = 0; v < m.d.V; v++) logit[v] += (double)m.bout[v];
     }
 };
+
+// rnnt_stateless.hip: the table upload asr_rnnt_upload hands a stateless handle to, and the producer of
+// asr_rnnt_align's p [(mtl+1)*N][Hp] (row u * N + n: the last C of start-context + y_n[:u]).
+int rnnt_ctx_upload(asr_rnnt* h);
+int rnnt_ctx_align_rows(const asr_rnnt* h, const int32_t* d_targets, long ldt, const int32_t* d_target_lengths, int N,
+                        int mtl, float* d_p, hipStream_t st);
 
 }  // namespace asr

@@ -1810,6 +1810,90 @@ int asr_rnnt_greedy_host(const asr_rnnt_t* h, const float* h_enc, const int32_t*
                          const double* h_state_in, double* h_state_out, int32_t* h_tokens, int32_t* h_timesteps,
                          double* h_logp, int32_t* h_count, double* h_total, double* h_gap);
 
+/* Transducers with a stateless predictor (Ghodsi et al.; k2 / icefall's
+ * pruned_transducer_stateless* and Zipformer recipes): the same handle type,
+ * made by asr_rnnt_create_stateless.  The predictor is
+ *   p = relu(T_0[y_0] + T_1[y_1] + ... + T_{C-1}[y_{C-1}] + b_ctx)     [Hp]
+ *       T_c = Emb.W_ctx[c]      Emb [V][D], W_ctx [C][D][Hp], c = 0 the oldest
+ *   g = p.W_pred + b_pred       W_pred [Hp][J]
+ * and the joint is the one above.  (y_0 .. y_{C-1}) is the context: the last
+ * C = context emitted tokens, oldest first.  An entry of -1 contributes nothing
+ * (Zipformer's embedding(y.clamp(min=0)) * (y >= 0)).  The sum runs in
+ * ascending c, then adds b_ctx, then the ReLU.  A dense [D][Hp] matrix per
+ * position covers icefall's depthwise, grouped and ungrouped Conv1d alike (a
+ * grouped weight expands to a block-diagonal one).  w_ctx == NULL is allowed
+ * for context = 1 only, requires D == Hp and means T_0 = Emb (icefall's
+ * context_size = 1, which has no conv); b_ctx may be NULL (no bias).  Without a
+ * given state the start context is (start_fill, ..., start_fill, blank):
+ * start_fill = blank for the older recipes, -1 for Zipformer.
+ *
+ * asr_rnnt_create_stateless: host pointers, a host copy is kept.  Checks, in
+ * this order - ASR_ERR_ARG: a NULL argument; V < 2; blank outside [0, V); a
+ * non-positive E, D, Hp, J; max_symbols < 1; act neither ASR_RNNT_ACT_RELU nor
+ * _TANH; context outside [1, ASR_RNNT_MAX_CONTEXT]; start_fill outside
+ * [-1, V).  ASR_ERR_UNSUPPORTED: D, Hp or J not a multiple of 16; the limit of
+ * the decode kernel, whose rows live in LDS:
+ *     64 * ((Hp + 4) + (J + 4)) + 4096 <= 160 KiB
+ * (up to Hp = J = 1232; the beam search's small area is 8192 bytes, so
+ * asr_rnnt_beam* take up to Hp = J = 1200); context * V * Hp > INT_MAX.  Then
+ * ASR_ERR_ARG: a NULL weight other than w_ctx and b_ctx; w_ctx NULL with
+ * context > 1 or D != Hp.
+ * asr_rnnt_upload, asr_rnnt_get_info (desc.L = 0, D as given), asr_rnnt_destroy
+ * and asr_rnnt_workspace_bytes take either kind of handle.  The upload
+ * computes the C tables T_c [V][Hp] on the device (C GEMMs under the
+ * asr_set_dense_arith setting of that moment), so a predictor step on the
+ * device is C row gathers, adds and a ReLU.  The workspace of a stateless
+ * handle is f [T*B][J] and g [16][J] per 16 utterances, to a multiple of 32
+ * utterances; there is no c.
+ * asr_rnnt_context: C of a stateless handle, 0 for an LSTM handle or NULL.
+ *
+ * asr_rnnt_greedy_stateless / _host: asr_rnnt_greedy / _host with the context
+ * as the state: ctx_in, ctx_out int32 [B][C], either may be NULL, they may be
+ * the same array.  The walk, the outputs, the max_symbols and max_out rules and
+ * the iteration bound are asr_rnnt_greedy's; a token that is emitted shifts
+ * into the context.  A call ends at a frame boundary, so ctx_out as the next
+ * call's ctx_in reproduces a whole decode bit for bit.  An entry of ctx_in
+ * outside [-1, V) is the caller's error; it is clamped into that range and
+ * nothing faults.  The host twin computes Emb[y].W_ctx[c] in fp64 from the fp32
+ * weights, never through a table.  Checks: asr_rnnt_greedy's in its order,
+ * then ASR_ERR_UNSUPPORTED for an LSTM handle; in the same place
+ * asr_rnnt_greedy / _host refuse a stateless handle with ASR_ERR_UNSUPPORTED.
+ * All of these come before any HIP call.
+ *
+ * asr_rnnt_beam*, asr_rnnt_lm_create / asr_rnnt_beam_lm* and asr_rnnt_align*,
+ * their _host twins and their *_workspace_bytes take either kind of handle
+ * unchanged; their definitions below hold word for word, with "the predictor
+ * state after ys" read as "the last C tokens of start-context + ys".  For a
+ * stateless handle the workspaces hold no c slices, asr_rnnt_align runs no
+ * recurrence (its 0x7ff00000 limit does not apply) and g comes from one
+ * gather kernel and one GEMM. */
+#define ASR_RNNT_MAX_CONTEXT 4
+typedef struct asr_rnnt_stateless_desc {
+    int32_t V, blank, E, D, Hp, J, act, max_symbols, context, start_fill;
+} asr_rnnt_stateless_desc;
+typedef struct asr_rnnt_stateless_weights {
+    const float* emb;      /* [V][D] */
+    const float* w_ctx;    /* [context][D][Hp], or NULL (context = 1, D = Hp) */
+    const float* b_ctx;    /* [Hp] or NULL */
+    const float* w_enc;    /* [E][J] */
+    const float* b_enc;
+    const float* w_pred;   /* [Hp][J] */
+    const float* b_pred;
+    const float* w_out;    /* [J][V] */
+    const float* b_out;
+} asr_rnnt_stateless_weights;
+int asr_rnnt_create_stateless(const asr_rnnt_stateless_desc* desc, const asr_rnnt_stateless_weights* weights,
+                              asr_rnnt_t** out);
+int asr_rnnt_context(const asr_rnnt_t* h);
+int asr_rnnt_greedy_stateless(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_lengths, int T, int B,
+                              int max_out, const int32_t* d_ctx_in, int32_t* d_ctx_out, int32_t* d_tokens,
+                              int32_t* d_timesteps, double* d_logp, int32_t* d_count, double* d_total, void* d_work,
+                              asr_stream_t s);
+int asr_rnnt_greedy_stateless_host(const asr_rnnt_t* h, const float* h_enc, const int32_t* h_lengths, int T, int B,
+                                   int max_out, const int32_t* h_ctx_in, int32_t* h_ctx_out, int32_t* h_tokens,
+                                   int32_t* h_timesteps, double* h_logp, int32_t* h_count, double* h_total,
+                                   double* h_gap);
+
 /* RNN-T beam search, one symbol per frame (the "modified beam search" of k2 /
  * icefall), on an asr_rnnt handle.  The model and the start are the greedy
  * walk's (h = c = 0, then one predictor step on Emb[blank]); desc.max_symbols
