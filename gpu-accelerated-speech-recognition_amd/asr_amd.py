@@ -102,6 +102,14 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           asr_rnnt_greedy_stateless); beam_search,
                                           score, align and rescore work unchanged;
                                           no reference member
+    TransducerDecoder.tdt(desc, weights, durations) / .from_torch(..., durations=[0, 1, 2, 3, 4])
+                                          token-and-duration transducers (NeMo's
+                                          *-tdt): a duration head rides the W_out
+                                          stream, an evaluation gives (token,
+                                          duration) and the walk jumps, the frame
+                                          skip carried across chunks
+                                          (asr_rnnt_create_tdt, asr_rnnt_greedy_tdt);
+                                          greedy decoding only; no reference member
     TransducerDecoder.beam_search(enc, beam=4)
                                           RNN-T beam search, one symbol per frame,
                                           the n-best in one launch (asr_rnnt_beam*);
@@ -177,6 +185,7 @@ EXPORTS = [
     "asr_rnnt_create", "asr_rnnt_upload", "asr_rnnt_get_info", "asr_rnnt_destroy", "asr_rnnt_workspace_bytes",
     "asr_rnnt_greedy", "asr_rnnt_greedy_host",
     "asr_rnnt_create_stateless", "asr_rnnt_context", "asr_rnnt_greedy_stateless", "asr_rnnt_greedy_stateless_host",
+    "asr_rnnt_create_tdt", "asr_rnnt_tdt_durations", "asr_rnnt_greedy_tdt", "asr_rnnt_greedy_tdt_host",
     "asr_rnnt_beam_workspace_bytes", "asr_rnnt_beam", "asr_rnnt_beam_host",
     "asr_rnnt_lm_create", "asr_rnnt_lm_destroy", "asr_rnnt_beam_lm_workspace_bytes", "asr_rnnt_beam_lm",
     "asr_rnnt_beam_lm_host",
@@ -353,6 +362,10 @@ def lib() -> ctypes.CDLL:
         "asr_rnnt_context": [_vp],
         "asr_rnnt_greedy_stateless": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_greedy_stateless_host": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "asr_rnnt_create_tdt": [_vp, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_vp)],
+        "asr_rnnt_tdt_durations": [_vp, _vp],
+        "asr_rnnt_greedy_tdt": [_vp, _vp, _vp, _i, _i, _i] + [_vp] * 12,
+        "asr_rnnt_greedy_tdt_host": [_vp, _vp, _vp, _i, _i, _i] + [_vp] * 12,
         "asr_rnnt_beam": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_beam_host": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
         "asr_rnnt_lm_create": [_vp, _vp, _vp, _f, _f, _i, ctypes.POINTER(_vp)],
@@ -4186,11 +4199,21 @@ class TransducerDecoder:
     A stateless predictor (TransducerDecoder.stateless / from_icefall;
     asr_rnnt_create_stateless) gives the same object: context > 0, the state of
     decode / decode_host is the int32 context [B, C], and every other method
-    works unchanged."""
+    works unchanged.
+
+    A token-and-duration transducer (TransducerDecoder.tdt / from_torch with
+    durations; asr_rnnt_create_tdt) has a duration head beside the tokens:
+    weights also hold w_dur [J, D] and b_dur [D].  decode, decode_host and
+    decode_device are asr_rnnt_greedy_tdt*: every result also carries the
+    per-token durations, and the state is the pair (the LSTM state, the int32
+    frame skip [B]).  The beam search, LM fusion and lattice methods raise the
+    library's ASR_ERR_UNSUPPORTED."""
 
     context = 0      # C of a stateless predictor, 0: an LSTM
+    durations = None  # the duration table of a token-and-duration transducer
 
-    def __init__(self, desc: RnntDesc, weights: dict, labels: Optional[Sequence[str]] = None):
+    def __init__(self, desc: RnntDesc, weights: dict, labels: Optional[Sequence[str]] = None,
+                 durations: Optional[Sequence[int]] = None):
         self.desc = desc
         self.h = None
         self.labels = list(labels) if labels is not None else None
@@ -4220,16 +4243,43 @@ class TransducerDecoder:
                 getattr(w, name)[l] = _ptr(a)
         self.weights = keep            # the fp32 arrays the handle was made from
         h = _vp()
-        check(lib().asr_rnnt_create(ctypes.byref(desc), ctypes.byref(w), ctypes.byref(h)), "asr_rnnt_create")
+        if durations is not None:
+            dur = np.ascontiguousarray(durations, dtype=np.int32)
+            if dur.ndim != 1:
+                raise ValueError(f"durations: shape {dur.shape}, expected one dimension")
+            for name, shape in (("w_dur", (d.J, len(dur))), ("b_dur", (len(dur),))):
+                a = np.ascontiguousarray(weights[name], dtype=np.float32)
+                if a.shape != shape:
+                    raise ValueError(f"{name}: shape {a.shape}, expected {shape}")
+                keep[name] = a
+            check(lib().asr_rnnt_create_tdt(ctypes.byref(desc), ctypes.byref(w), len(dur), _ptr(dur),
+                                            _ptr(keep["w_dur"]), _ptr(keep["b_dur"]), ctypes.byref(h)),
+                  "asr_rnnt_create_tdt")
+            self.durations = dur.tolist()
+        else:
+            check(lib().asr_rnnt_create(ctypes.byref(desc), ctypes.byref(w), ctypes.byref(h)), "asr_rnnt_create")
         self.h = h.value
         self._work = None
         self._uploaded = False
 
     @classmethod
+    def tdt(cls, desc: RnntDesc, weights: dict, durations: Sequence[int],
+            labels: Optional[Sequence[str]] = None) -> "TransducerDecoder":
+        """A token-and-duration transducer (asr_rnnt_create_tdt): the weights of
+        the constructor (w_out [J, V] the token columns only) plus w_dur
+        [J, D] and b_dur [D]; durations: the D integers a duration index
+        stands for."""
+        return cls(desc, weights, labels, durations=durations)
+
+    @classmethod
     def from_torch(cls, embedding, lstm, enc_proj, pred_proj, out_proj, blank: int, activation: str = "relu",
-                   max_symbols: int = 10) -> "TransducerDecoder":
+                   max_symbols: int = 10, durations: Optional[Sequence[int]] = None) -> "TransducerDecoder":
         """From torch.nn.Embedding, torch.nn.LSTM (unidirectional, with bias, no
-        projection) and three torch.nn.Linear, transposed into [in][out]."""
+        projection) and three torch.nn.Linear, transposed into [in][out].
+        With durations (a list of D integers) out_proj has V + D outputs, the
+        first V the tokens and the last D the durations (NeMo's TDT joint,
+        whose blank is V - 1), and the result is a token-and-duration
+        transducer."""
         if lstm.bidirectional or not lstm.bias or getattr(lstm, "proj_size", 0):
             raise ValueError("the predictor is a unidirectional LSTM with bias and no projection")
 
@@ -4251,10 +4301,14 @@ class TransducerDecoder:
         wt["w_out"], wt["b_out"] = lin(out_proj)
         d = rnnt_desc(embedding.num_embeddings, blank, enc_proj.in_features, embedding.embedding_dim,
                       lstm.hidden_size, L, enc_proj.out_features, activation, max_symbols)
+        nd = 0 if durations is None else len(durations)
         if lstm.input_size != d.D or pred_proj.in_features != d.Hp or pred_proj.out_features != d.J or \
-                out_proj.in_features != d.J or out_proj.out_features != d.V:
+                out_proj.in_features != d.J or out_proj.out_features != d.V + nd:
             raise ValueError("the modules' sizes do not chain")
-        return cls(d, wt)
+        if durations is not None:
+            wt["w_dur"], wt["b_dur"] = np.ascontiguousarray(wt["w_out"][:, d.V:]), wt["b_out"][d.V:].copy()
+            wt["w_out"], wt["b_out"] = np.ascontiguousarray(wt["w_out"][:, :d.V]), wt["b_out"][:d.V].copy()
+        return cls(d, wt, durations=durations)
 
     @classmethod
     def stateless(cls, desc: RnntStatelessDesc, weights: dict,
@@ -4363,9 +4417,20 @@ class TransducerDecoder:
 
     def decode_device(self, d_enc: int, T: int, B: int, max_out: int, d_tokens: int, d_timesteps: int, d_logp: int,
                       d_count: int, d_total: int, d_work: int, d_lengths: int = 0, d_state_in: int = 0,
-                      d_state_out: int = 0, stream: int = 0) -> None:
+                      d_state_out: int = 0, stream: int = 0, d_durations: int = 0, d_skip_in: int = 0,
+                      d_skip_out: int = 0) -> None:
         """asr_rnnt_greedy (a stateless predictor: asr_rnnt_greedy_stateless, the
-        states int32 contexts) on device pointers: asynchronous on stream."""
+        states int32 contexts; a token-and-duration transducer:
+        asr_rnnt_greedy_tdt, with d_durations int32 [B, max_out] and the
+        optional frame skips int32 [B]) on device pointers: asynchronous on
+        stream."""
+        if self.durations is not None:
+            check(lib().asr_rnnt_greedy_tdt(self.h, d_enc or None, d_lengths or None, T, B, max_out,
+                                            d_state_in or None, d_state_out or None, d_skip_in or None,
+                                            d_skip_out or None, d_tokens or None, d_timesteps or None,
+                                            d_durations or None, d_logp or None, d_count or None, d_total or None,
+                                            d_work or None, stream or None), "asr_rnnt_greedy_tdt")
+            return
         if self.context:
             check(lib().asr_rnnt_greedy_stateless(self.h, d_enc or None, d_lengths or None, T, B, max_out,
                                                   d_state_in or None, d_state_out or None, d_tokens or None,
@@ -4379,12 +4444,28 @@ class TransducerDecoder:
               "asr_rnnt_greedy")
 
     @staticmethod
-    def _unpack(B, max_out, tok, ts, lp, cnt, total):
+    def _unpack(B, max_out, tok, ts, lp, cnt, total, dur=None):
         out = []
         for b in range(B):
             n = min(int(cnt[b]), max_out)
-            out.append((tok[b, :n].tolist(), ts[b, :n].tolist(), lp[b, :n].copy(), float(total[b])))
+            out.append((tok[b, :n].tolist(), ts[b, :n].tolist(), lp[b, :n].copy(), float(total[b])) +
+                       (() if dur is None else (dur[b, :n].tolist(),)))
         return out
+
+    def _split_state(self, state, B, sty):
+        """(the predictor state checked against state_shape, the frame skip int32 [B] or None): a
+        token-and-duration transducer's state is the pair, any other's the array alone."""
+        skip = None
+        if state is not None and self.durations is not None:
+            state, skip = state
+            skip = np.ascontiguousarray(skip, dtype=np.int32)
+            if skip.shape != (B,):
+                raise ValueError(f"state: skip of shape {skip.shape}, expected ({B},)")
+        if state is not None:
+            state = np.ascontiguousarray(state, dtype=sty)
+            if state.shape != self.state_shape(B):
+                raise ValueError(f"state: shape {state.shape}, expected {self.state_shape(B)}")
+        return state, skip
 
     def _prepare(self, enc, lengths, max_out):
         enc = np.ascontiguousarray(enc, dtype=np.float32)
@@ -4404,7 +4485,10 @@ class TransducerDecoder:
         [2, L, B, Hp] float32 (pass it to the next chunk's decode and add the
         frame offset to the timesteps), and the emission counts int32 [B],
         which exceed max_out where records were dropped.  max_out defaults to
-        T * max_symbols, the most a walk can emit."""
+        T * max_symbols, the most a walk can emit.  A token-and-duration
+        transducer: every utterance's tuple ends with its per-token
+        durations, and the state is (the LSTM state, the frame skip int32
+        [B]): the frames of the next chunk that the last jump consumed."""
         enc, ln, T, B, max_out = self._prepare(enc, lengths, max_out)
         if not self._uploaded:
             self.upload()
@@ -4413,21 +4497,21 @@ class TransducerDecoder:
         shape = self.state_shape(B)
         nstate = int(np.prod(shape))
         sty = np.int32 if self.context else np.float32
-        d_sin = None
-        if state is not None:
-            st = np.ascontiguousarray(state, dtype=sty)
-            if st.shape != shape:
-                raise ValueError(f"state: shape {st.shape}, expected {shape}")
-            d_sin = _upload(st, stream)
+        st, skip = self._split_state(state, B, sty)
+        d_sin = _upload(st, stream) if st is not None else None
         d_sout = DeviceBytes(4 * nstate)
+        tdt = self.durations is not None
+        d_skip = _upload(skip if skip is not None else np.zeros(B, np.int32), stream) if tdt else None
         mo = max(max_out, 1)
         d_tok, d_ts, d_lp = DeviceBytes(4 * B * mo), DeviceBytes(4 * B * mo), DeviceBytes(8 * B * mo)
         d_cnt, d_tot = DeviceBytes(max(4 * B, 16)), DeviceBytes(max(8 * B, 16))
         need = self.workspace_bytes(T, B)
         if self._work is None or self._work.nbytes < need:
             self._work = DeviceBytes(need)
+        d_dur = DeviceBytes(4 * B * mo) if tdt else None
         self.decode_device(d_enc.ptr, T, B, max_out, d_tok.ptr, d_ts.ptr, d_lp.ptr, d_cnt.ptr, d_tot.ptr,
-                           self._work.ptr, d_len.ptr if d_len else 0, d_sin.ptr if d_sin else 0, d_sout.ptr, stream)
+                           self._work.ptr, d_len.ptr if d_len else 0, d_sin.ptr if d_sin else 0, d_sout.ptr, stream,
+                           d_dur.ptr if tdt else 0, d_skip.ptr if tdt else 0, d_skip.ptr if tdt else 0)
         check(lib().asr_stream_sync(stream or None), "asr_stream_sync")
         cnt = _download(d_cnt, (B,), np.int32, stream)
         total = _download(d_tot, (B,), np.float64, stream)
@@ -4435,25 +4519,36 @@ class TransducerDecoder:
         ts = _download(d_ts, (B, mo), np.int32, stream)
         lp = _download(d_lp, (B, mo), np.float64, stream)
         new_state = _download(d_sout, shape, sty, stream)
+        if tdt:
+            dur = _download(d_dur, (B, mo), np.int32, stream)
+            new_state = (new_state, _download(d_skip, (B,), np.int32, stream))
+            return self._unpack(B, max_out, tok, ts, lp, cnt, total, dur), new_state, cnt
         return self._unpack(B, max_out, tok, ts, lp, cnt, total), new_state, cnt
 
     def decode_host(self, enc, lengths=None, state=None, max_out=None, gaps: bool = False):
         """The same through asr_rnnt_greedy_host (one thread, fp64): the state is
         float64; with gaps also the smallest top-2 logit gap of each
-        utterance's walk."""
+        utterance's walk (a token-and-duration transducer: the array [2, B],
+        the token head's gaps, then the duration head's)."""
         enc, ln, T, B, max_out = self._prepare(enc, lengths, max_out)
         shape = self.state_shape(B)
         sty = np.int32 if self.context else np.float64
         fn = lib().asr_rnnt_greedy_stateless_host if self.context else lib().asr_rnnt_greedy_host
-        sin = None
-        if state is not None:
-            sin = np.ascontiguousarray(state, dtype=sty)
-            if sin.shape != shape:
-                raise ValueError(f"state: shape {sin.shape}, expected {shape}")
+        sin, skip = self._split_state(state, B, sty)
         sout = np.zeros(shape, sty)
         mo = max(max_out, 1)
         tok, ts, lp = np.zeros((B, mo), np.int32), np.zeros((B, mo), np.int32), np.zeros((B, mo), np.float64)
         cnt, total, gap = np.zeros(B, np.int32), np.zeros(B, np.float64), np.zeros(B, np.float64)
+        if self.durations is not None:
+            dur, gap = np.zeros((B, mo), np.int32), np.zeros((2, B), np.float64)
+            skip = np.zeros(B, np.int32) if skip is None else skip.copy()
+            check(lib().asr_rnnt_greedy_tdt_host(self.h, _ptr(enc), _ptr(ln) if ln is not None else None, T, B,
+                                                 max_out, _ptr(sin) if sin is not None else None, _ptr(sout),
+                                                 _ptr(skip), _ptr(skip), _ptr(tok), _ptr(ts), _ptr(dur), _ptr(lp),
+                                                 _ptr(cnt), _ptr(total), _ptr(gap[0]) if gaps else None,
+                                                 _ptr(gap[1]) if gaps else None), "asr_rnnt_greedy_tdt_host")
+            res = self._unpack(B, max_out, tok, ts, lp, cnt, total, dur), (sout, skip), cnt
+            return res + (gap,) if gaps else res
         check(fn(self.h, _ptr(enc), _ptr(ln) if ln is not None else None, T, B, max_out,
                  _ptr(sin) if sin is not None else None, _ptr(sout), _ptr(tok), _ptr(ts), _ptr(lp), _ptr(cnt),
                  _ptr(total), _ptr(gap) if gaps else None),

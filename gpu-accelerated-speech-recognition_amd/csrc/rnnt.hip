@@ -362,6 +362,7 @@ static int rnnt_greedy_check(const asr_rnnt* h, const void* enc, int T, int B, i
     if (max_out > 0 && (!tokens || !timesteps || !logp)) return ASR_ERR_ARG;
     if ((long)T * B > INT_MAX || (long)T * (h->d.max_symbols + 1) >= INT_MAX) return ASR_ERR_UNSUPPORTED;
     if (h->C) return ASR_ERR_UNSUPPORTED;   // a stateless handle: asr_rnnt_greedy_stateless
+    if (h->nd) return ASR_ERR_UNSUPPORTED;  // a token-and-duration handle: asr_rnnt_greedy_tdt
     return ASR_OK;
 }
 

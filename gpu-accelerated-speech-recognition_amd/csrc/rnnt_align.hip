@@ -418,6 +418,7 @@ static int ra_check(const asr_rnnt* h, const void* enc, int T, int B, const void
     if ((long)T * B > INT_MAX || (long)N * U1 > INT_MAX || (long)T * U1 > INT_MAX || (long)N * tiles > INT_MAX ||
         (!h->C && (long)N * 16 * h->d.Hp > RA_LSTM_OOB))   // a stateless handle runs no recurrence
         return ASR_ERR_UNSUPPORTED;
+    if (h->nd) return ASR_ERR_UNSUPPORTED;   // a token-and-duration handle: this lattice is not its model's
     return ASR_OK;
 }
 

@@ -672,6 +672,7 @@ static int rnnt_beam_check(const asr_rnnt* h, const void* enc, int T, int B, int
     if (max_out < 0) return ASR_ERR_ARG;
     if (max_out > 0 && (!tokens || !timesteps)) return ASR_ERR_ARG;
     if ((long)T * B > INT_MAX || (long)T * K + 1 > INT_MAX) return ASR_ERR_UNSUPPORTED;
+    if (h->nd) return ASR_ERR_UNSUPPORTED;   // a token-and-duration handle: this lattice is not its model's
     return ASR_OK;
 }
 

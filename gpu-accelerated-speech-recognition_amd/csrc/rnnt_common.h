@@ -27,6 +27,10 @@ struct asr_rnnt {
     int C = 0, start_fill = 0;
     bool conv = false;               // false: C = 1 without W_ctx, T_0 = Emb
     std::vector<float> wctx, bctx;   // [C][D][Hp]; [Hp], zeros when none was given
+    // token-and-duration transducer (asr_rnnt_create_tdt, rnnt_tdt.hip): nd > 0 duration columns, and wout / bout
+    // hold W_out and W_dur side by side, [J][V + nd] and [V + nd]; only asr_rnnt_greedy_tdt* take such a handle
+    int nd = 0;
+    int32_t durs[16] = {};
     int lds_bytes = 0;
     int64_t weight_bytes = 0;
     // device copy (asr_rnnt_upload): one allocation

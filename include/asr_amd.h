@@ -1894,6 +1894,85 @@ int asr_rnnt_greedy_stateless_host(const asr_rnnt_t* h, const float* h_enc, cons
                                    int32_t* h_timesteps, double* h_logp, int32_t* h_count, double* h_total,
                                    double* h_gap);
 
+/* Token-and-duration transducers (TDT; Xu et al. 2023, NeMo's *-tdt models):
+ * the LSTM-predictor transducer above plus a duration head on the same z,
+ *   dlogit = z.W_dur + b_dur       W_dur [J][D], 1 <= D <= 16
+ * and a table durations[D] of integers in [0, 32767], in any order, at least
+ * one of them > 0.  The same handle type, made by asr_rnnt_create_tdt.
+ *
+ * One joint evaluation gives a pair: k = argmax logit, d = argmax dlogit (each
+ * the lowest index among equal maxima, a NaN never wins), and
+ *   logp = (logit[k] - logsumexp(logit)) + (dlogit[d] - logsumexp(dlogit)).
+ * The two softmaxes are separate: no duration column enters the token sum and
+ * no token column the duration sum.
+ *
+ * The walk of utterance b (length len_b clamped to [0, T]; the start state is
+ * asr_rnnt_greedy's): t = skip_in[b] (0 without one; a negative entry counts
+ * as 0), n = 0.  While t < len_b the joint is evaluated and dur =
+ * durations[d].  k == blank: logp goes to the total only, t += max(dur, 1),
+ * n = 0.  Otherwise (k, t, dur, logp) is recorded, the predictor steps on
+ * Emb[k] and n += 1; then with dur > 0: t += dur, n = 0; else at
+ * n == max_symbols: t += 1, n = 0.  skip_out[b] = t - len_b, the frames of the
+ * next chunk that the last jump has consumed already; with skip_in[b] >= len_b
+ * the chunk is skipped whole and skip_out[b] = skip_in[b] - len_b.  A call
+ * ends with n = 0, so chunks that pass on (h, c) and the skip, with the frame
+ * offset added to the timesteps, equal a whole decode bit for bit.  Counts
+ * keep counting past max_out as asr_rnnt_greedy's do.
+ *
+ * NeMo's loop differs in one case.  It also moves one frame on when its
+ * per-frame symbol counter reaches the cap on an evaluation that advanced
+ * already: when the token that brings the counter to max_symbols has dur > 0
+ * (with max_symbols = 1: every token with dur > 0), t moves by dur + 1 there
+ * and by dur here, where the cap only ends a run of duration-0 tokens at one
+ * frame.  When no frame's run of tokens reaches max_symbols the two walks are
+ * the same.
+ *
+ * asr_rnnt_create_tdt: asr_rnnt_create's desc and weights (w_out [J][V],
+ * b_out [V]: the token columns only) plus D = num_durations, the table and the
+ * duration head.  Checks, in this order - ASR_ERR_ARG: a NULL argument; D
+ * outside [1, ASR_RNNT_TDT_MAX_DURATIONS]; an entry of the table outside
+ * [0, 32767]; a table that is all zero.  Then asr_rnnt_create's checks, its
+ * LDS limit included (ASR_ERR_UNSUPPORTED).  ASR_ERR_UNSUPPORTED: J * (V + D) >
+ * INT_MAX.  asr_rnnt_upload on such a handle puts W_out and W_dur side by side
+ * on the device, one [J][V + D] matrix and one bias [V + D], which the decode
+ * kernel streams once per evaluation.  asr_rnnt_get_info, asr_rnnt_destroy and
+ * asr_rnnt_workspace_bytes (the LSTM handle's sizes) take the handle.
+ * asr_rnnt_tdt_durations: returns D and copies the table to durations (NULL:
+ * nothing is copied); 0 for any other handle or NULL.
+ *
+ * asr_rnnt_greedy_tdt / _host: asr_rnnt_greedy's / _host's arguments, plus
+ * durations int32 [B][max_out] (the duration of every recorded token, beside
+ * tokens, timesteps and logp; NULL only when max_out = 0) and skip_in,
+ * skip_out int32 [B], either may be NULL, they may be the same array.  f for
+ * all T is one GEMM (frames the walk jumps over are projected too); the walk
+ * is one launch, 16 utterances per workgroup, at most T * max_symbols joint
+ * evaluations per utterance by a bound the host sets.  The total adds both
+ * terms of every evaluation.  An utterance's bits depend on the model's shape
+ * only.  The host twin: one thread, fp64 from the fp32 weights; h_gap and
+ * h_dgap (optional, double [B]) are the smallest best-minus-second-best gap of
+ * the token head and of the duration head on the utterance's walk (HUGE_VAL
+ * when nothing was evaluated, and h_dgap for D = 1).
+ * Checks of both: asr_rnnt_greedy's in its order (the durations array with the
+ * token arrays), then ASR_ERR_UNSUPPORTED for a handle that is not a TDT one;
+ * asr_rnnt_greedy_tdt only, then: ASR_ERR_ARG for a NULL d_work, ASR_ERR_STATE
+ * when the weights were not uploaded.  In the same place as their other
+ * ASR_ERR_UNSUPPORTED checks asr_rnnt_greedy / _host, asr_rnnt_greedy_stateless
+ * / _host, asr_rnnt_beam / _host, asr_rnnt_beam_lm / _host and asr_rnnt_align /
+ * _host refuse a TDT handle with ASR_ERR_UNSUPPORTED: their one-softmax
+ * lattice is not this model's.  All of these come before any HIP call. */
+#define ASR_RNNT_TDT_MAX_DURATIONS 16
+int asr_rnnt_create_tdt(const asr_rnnt_desc* desc, const asr_rnnt_weights* weights, int num_durations,
+                        const int32_t* durations, const float* w_dur, const float* b_dur, asr_rnnt_t** out);
+int asr_rnnt_tdt_durations(const asr_rnnt_t* h, int32_t* durations);
+int asr_rnnt_greedy_tdt(const asr_rnnt_t* h, const float* d_enc, const int32_t* d_lengths, int T, int B, int max_out,
+                        const float* d_state_in, float* d_state_out, const int32_t* d_skip_in, int32_t* d_skip_out,
+                        int32_t* d_tokens, int32_t* d_timesteps, int32_t* d_durations, double* d_logp,
+                        int32_t* d_count, double* d_total, void* d_work, asr_stream_t s);
+int asr_rnnt_greedy_tdt_host(const asr_rnnt_t* h, const float* h_enc, const int32_t* h_lengths, int T, int B,
+                             int max_out, const double* h_state_in, double* h_state_out, const int32_t* h_skip_in,
+                             int32_t* h_skip_out, int32_t* h_tokens, int32_t* h_timesteps, int32_t* h_durations,
+                             double* h_logp, int32_t* h_count, double* h_total, double* h_gap, double* h_dgap);
+
 /* RNN-T beam search, one symbol per frame (the "modified beam search" of k2 /
  * icefall), on an asr_rnnt handle.  The model and the start are the greedy
  * walk's (h = c = 0, then one predictor step on Emb[blank]); desc.max_symbols
