@@ -50,6 +50,14 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           with GLU -> depthwise -> BatchNorm ->
                                           SiLU in one launch (asr_glu_dwconv_fwd);
                                           no reference member
+    EBranchformerLayer.from_torch(ffn1=..., attn=..., cgmlp=..., merge=..., ffn2=..., final_norm=...).forward
+    ConvolutionalGatingMLP.from_torch(cgmlp).forward / EBranchformer(layers).forward
+                                          an E-Branchformer encoder block: the
+                                          attention and cgMLP branches (GELU fused,
+                                          EPI_BIAS_GELU; the gating unit in
+                                          asr_csgu_fwd) merged by a depthwise
+                                          convolution over both
+                                          (asr_merge_dwconv_fwd); no reference member
     TransformerDecoder.from_torch(embedding, decoder, output).score(hyps, utt, memory, T, B)
     attention_rescore(nbest, decoder, memory, T, B) / CTCDecoder.attention_rescore(...)
                                           attention-decoder rescoring of an n-best:
@@ -152,7 +160,7 @@ ASR_ERR_UNSUPPORTED = 5
 ASR_ERR_STATE = 6
 ASR_ERR_INTERNAL = 7
 
-EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_LOGSOFTMAX, EPI_BIAS_SILU = 0, 1, 2, 3, 4
+EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_LOGSOFTMAX, EPI_BIAS_SILU, EPI_BIAS_GELU = 0, 1, 2, 3, 4, 6
 SEMANTICS_CPU, SEMANTICS_CUDA = 0, 1   # asr_ctc_set_semantics
 ASR_CTC_WAVES_LIST = -1                # asr_ctc_set_waves: the one-wave list kernel
 ASR_CTC_TS_MAX_T = 65536               # longest decode with timesteps on (16-bit frames)
@@ -168,6 +176,7 @@ EXPORTS = [
     "asr_lstm_workspace_bytes", "asr_lstm_fwd", "asr_lstm_recur_fwd",
     "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
     "asr_conv1d_out_frames", "asr_conv1d_fwd", "asr_glu_dwconv_fwd",
+    "asr_csgu_fwd", "asr_merge_dwconv_fwd",
     "asr_conv2d_out_frames", "asr_conv2d_out_feats", "asr_conv2d_fwd",
     "asr_attention_fwd", "asr_attention_rel_fwd", "asr_layernorm_fwd", "asr_mask_rows",
     "asr_cross_attention_fwd", "asr_token_score",
@@ -300,6 +309,9 @@ def lib() -> ctypes.CDLL:
         "asr_conv2d_out_feats": [_vp],
         "asr_conv2d_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i, _vp],
         "asr_glu_dwconv_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _vp],
+        "asr_csgu_fwd": [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _vp],
+        "asr_merge_dwconv_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _i,
+                                 _i, _vp],
         "asr_attention_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp,
                               ctypes.c_long, _i, _i, _i, _i, _i, _vp],
         "asr_attention_rel_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long,
@@ -3247,6 +3259,394 @@ class Conformer:
     """A stack of ConformerLayers run in turn with the same lengths."""
 
     def __init__(self, layers: Sequence[ConformerLayer]):
+        self.layers = list(layers)
+        assert self.layers and all(l.E == self.layers[0].E for l in self.layers)
+        self.E = self.layers[0].E
+
+    def forward(self, x, T: int, B: int, lengths=None, stream: int = 0) -> DeviceMatrix:
+        """x time-major [T*B, E]; returns the last layer's new DeviceMatrix
+        [T*B, E] with zero rows past the lengths."""
+        lengths = _device_lengths_or_none(lengths)
+        for layer in self.layers:
+            x = layer.forward(x, T, B, lengths, stream=stream)
+        self._keep = lengths
+        return x
+
+
+# ----------------------------------------------------------------- E-Branchformer
+CGMLP_MAX_KERNEL = 80   # ASR_CGMLP_MAX_KERNEL
+
+
+class CsguDesc(ctypes.Structure):
+    """asr_csgu_desc (include/asr_amd.h)."""
+    _fields_ = [("channels", _i), ("kernel", _i), ("pad_left", _i), ("pad_right", _i), ("eps", _f)]
+
+
+class MergeDwconvDesc(ctypes.Structure):
+    """asr_merge_dwconv_desc (include/asr_amd.h)."""
+    _fields_ = [("channels", _i), ("kernel", _i), ("pad_left", _i), ("pad_right", _i)]
+
+
+def _same_pads(kernel: int, pad_left: Optional[int], pad_right: Optional[int]) -> Tuple[int, int]:
+    if pad_left is None:
+        pad_left = (kernel - 1) // 2 if pad_right is None else kernel - 1 - pad_right
+    if pad_right is None:
+        pad_right = kernel - 1 - pad_left
+    return pad_left, pad_right
+
+
+def csgu_desc(channels: int, kernel: int, pad_left: Optional[int] = None, pad_right: Optional[int] = None,
+              eps: float = 1e-5) -> CsguDesc:
+    """A CsguDesc from keywords; the pads default to "same" as glu_dwconv_desc's."""
+    return CsguDesc(channels, kernel, *_same_pads(kernel, pad_left, pad_right), eps)
+
+
+def merge_dwconv_desc(channels: int, kernel: int, pad_left: Optional[int] = None,
+                      pad_right: Optional[int] = None) -> MergeDwconvDesc:
+    """A MergeDwconvDesc from keywords (channels per source); the pads default to "same"."""
+    return MergeDwconvDesc(channels, kernel, *_same_pads(kernel, pad_left, pad_right))
+
+
+def csgu_stats(T: int, B: int) -> DeviceMatrix:
+    """The statistics buffer asr_csgu_fwd wants: 3 floats per row."""
+    return DeviceMatrix(T * B, 3)
+
+
+def csgu_fwd(u, w: DeviceMatrix, b: Optional[DeviceMatrix], out, T: int, B: int, desc: CsguDesc, gamma=None,
+             beta=None, stats: Optional[DeviceMatrix] = None, lengths: Optional[DeviceBytes] = None,
+             stream: int = 0):
+    """The convolutional spatial gating unit (asr_csgu_fwd): u [T*B, >= 2C]
+    time-major, values in columns [0, C) and gates in [C, 2C) (the row stride is
+    u.cols), gamma / beta [C] or None, w [k, C], b [C] or None, out [T*B, >= C]
+    (the row stride is out.cols); stats a csgu_stats(T, B) buffer (allocated
+    here if None: pass one to keep the call free of allocation); lengths from
+    device_lengths()."""
+    C = desc.channels
+    assert u.rows == T * B and u.cols >= 2 * C, (u.rows, u.cols)
+    assert out.rows == T * B and out.cols >= C, (out.rows, out.cols)
+    assert w.rows * w.cols == desc.kernel * C, (w.rows, w.cols)
+    stats = csgu_stats(T, B) if stats is None else stats
+    assert stats.rows * stats.cols >= 3 * T * B, (stats.rows, stats.cols)
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_csgu_fwd(ctypes.byref(desc), u.ptr, u.cols, opt(lengths), opt(gamma), opt(beta), w.ptr, opt(b),
+                             stats.ptr, out.ptr, out.cols, T, B, stream), "asr_csgu_fwd")
+    return out
+
+
+def merge_dwconv_fwd(x1, x2, w: DeviceMatrix, b: Optional[DeviceMatrix], out, T: int, B: int, desc: MergeDwconvDesc,
+                     lengths: Optional[DeviceBytes] = None, stream: int = 0):
+    """cat(x1, x2) + dwconv(cat(x1, x2)) without the concatenation
+    (asr_merge_dwconv_fwd): x1, x2 [T*B, >= C] time-major (the row strides are
+    their .cols), w [k, 2C], b [2C] or None, out [T*B, >= 2C]."""
+    C = desc.channels
+    assert x1.rows == T * B and x2.rows == T * B and x1.cols >= C and x2.cols >= C, (x1.rows, x1.cols, x2.cols)
+    assert out.rows == T * B and out.cols >= 2 * C, (out.rows, out.cols)
+    assert w.rows * w.cols == desc.kernel * 2 * C, (w.rows, w.cols)
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_merge_dwconv_fwd(ctypes.byref(desc), x1.ptr, x1.cols, x2.ptr, x2.cols, opt(lengths), w.ptr,
+                                     opt(b), out.ptr, out.cols, T, B, stream), "asr_merge_dwconv_fwd")
+    return out
+
+
+def _torch_depthwise(what: str, dw, channels: int):
+    """(w [k, C], b [C], (pad_left, pad_right)) float32 of a depthwise
+    torch.nn.Conv1d over `channels`; ValueError for anything else."""
+    if dw.groups != channels or dw.in_channels != channels or dw.out_channels != channels:
+        raise ValueError(f"{what}: the convolution is not depthwise over {channels} channels")
+    if dw.stride[0] != 1 or dw.dilation[0] != 1:
+        raise ValueError(f"{what}: the depthwise convolution needs stride 1 and dilation 1")
+    w, b, kw = Conv1d.pack_torch(dw)
+    pads = kw["padding"]
+    if pads[0] < 0 or pads[1] < 0 or pads[0] + pads[1] != kw["kernel"] - 1:
+        raise ValueError(f"{what}: pads {pads} do not sum to kernel - 1 = {kw['kernel'] - 1}")
+    return w.reshape(kw["kernel"], channels), b, pads
+
+
+class ConvolutionalGatingMLP:
+    """The cgMLP branch of a (E-)Branchformer block for inference, time-major:
+    Linear -> GELU (asr_linear_fwd, EPI_BIAS_GELU) -> convolutional spatial
+    gating unit (asr_csgu_fwd) -> Linear.  No arithmetic here.  w1 [E, 2C],
+    wd [k, C], w2 [C, E] in this library's [in][out] / [tap][channel] layouts;
+    norm_weight / norm_bias [C] or None; padding 'same', 'causal' or (left,
+    right) with left + right = k - 1."""
+
+    def __init__(self, w1, b1, norm_weight, norm_bias, norm_eps, wd, bd, w2, b2, padding="same"):
+        w1, wd, w2 = (np.asarray(a, np.float32) for a in (w1, wd, w2))
+        E, k, C = w1.shape[0], wd.shape[0], wd.shape[1]
+        assert w1.shape == (E, 2 * C) and w2.shape == (C, E), (w1.shape, wd.shape, w2.shape)
+        pl, pr = Conv1d.parse_padding(padding, k)
+        self.E, self.C = E, C
+        self.desc = csgu_desc(C, k, pl, pr, float(norm_eps))
+        up = lambda a, shape: None if a is None else DeviceMatrix.from_numpy(   # noqa: E731
+            np.asarray(a, np.float32).reshape(shape))
+        self.w1, self.b1 = up(w1, (E, 2 * C)), up(b1, (2 * C, 1))
+        self.gamma, self.beta = up(norm_weight, (C, 1)), up(norm_bias, (C, 1))
+        self.wd, self.bd = up(wd, (k, C)), up(bd, (C, 1))
+        self.w2, self.b2 = up(w2, (C, E)), up(b2, (E, 1))
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_torch(m):
+        """A dict of float32 arrays from a module laid out like ESPnet's
+        ConvolutionalGatingMLP: channel_proj1[0] (Linear; [1] a GELU),
+        csgu.norm, csgu.conv (depthwise Conv1d), channel_proj2 (Linear).  No
+        device call.  Raises ValueError for csgu.linear present
+        (use_linear_after_conv), a gate activation other than the identity, a
+        tanh-approximated GELU, or a conv that is not depthwise / stride 1."""
+        what = "ConvolutionalGatingMLP.pack_torch"
+        csgu = m.csgu
+        if getattr(csgu, "linear", None) is not None:
+            raise ValueError(f"{what}: csgu.linear (use_linear_after_conv) is not supported")
+        act = getattr(csgu, "act", None)
+        if act is not None and type(act).__name__ != "Identity":
+            raise ValueError(f"{what}: gate activation {type(act).__name__} is not supported (identity only)")
+        gelu = m.channel_proj1[1]
+        if type(gelu).__name__ != "GELU" or getattr(gelu, "approximate", "none") != "none":
+            raise ValueError(f"{what}: channel_proj1[1] must be the exact GELU")
+        w1, b1 = _torch_linear(m.channel_proj1[0])
+        w2, b2 = _torch_linear(m.channel_proj2)
+        C = csgu.conv.in_channels
+        if w1.shape[1] != 2 * C or w2.shape != (C, w1.shape[0]):
+            raise ValueError(f"{what}: the linears are {w1.shape} and {w2.shape} around {C} gated channels")
+        if tuple(csgu.norm.normalized_shape) != (C,):
+            raise ValueError(f"{what}: csgu.norm over {tuple(csgu.norm.normalized_shape)}, not ({C},)")
+        wd, bd, pads = _torch_depthwise(what, csgu.conv, C)
+        host = lambda p: None if p is None else p.detach().cpu().float().numpy()   # noqa: E731
+        return dict(w1=w1, b1=b1, norm_weight=host(getattr(csgu.norm, "weight", None)),
+                    norm_bias=host(getattr(csgu.norm, "bias", None)), norm_eps=float(csgu.norm.eps), wd=wd, bd=bd,
+                    w2=w2, b2=b2, padding=pads)
+
+    @classmethod
+    def from_torch(cls, m) -> "ConvolutionalGatingMLP":
+        return cls(**cls.pack_torch(m))
+
+    def forward(self, x, T: int, B: int, lengths=None, out=None, zero_padding: bool = True, stream: int = 0):
+        """The branch of time-major x [T*B, E]; lengths as ConformerConv.forward's.
+        Returns out [T*B, E] (a buffer of this module unless given); rows past
+        the lengths are zeros unless zero_padding is False, in which case they
+        hold the last bias."""
+        E, C, M, st = self.E, self.C, T * B, stream or 0
+        lengths = _device_lengths_or_none(lengths)
+        sc = self._scratch
+        u, c, stats = sc.get("u", M, 2 * C), sc.get("c", M, C), sc.get("stats", M, 3)
+        out = sc.get("out", M, E) if out is None else out
+        linear_fwd(x, self.w1, self.b1, u, EPI_BIAS_GELU, st)
+        csgu_fwd(u, self.wd, self.bd, c, T, B, self.desc, self.gamma, self.beta, stats, lengths, st)
+        linear_fwd(c, self.w2, self.b2, out, EPI_BIAS, st)
+        if zero_padding and lengths is not None:
+            mask_rows(out, T, B, E, lengths, st)
+        self._keep = lengths
+        return out
+
+
+class EBranchformerLayer:
+    """One E-Branchformer encoder block for inference, time-major:
+        x + s FFN1(x) (optional) -> two branches of that, LayerNorm -> attention
+        and LayerNorm -> cgMLP -> x + merge_proj(cat + dwconv(cat)) -> + s FFN2
+        (optional) -> LayerNorm,
+    each FFN LayerNorm -> Linear -> SiLU -> Linear with its scale s folded into
+    the second linear (ConformerLayer.pack_ffn).  The concatenation is never
+    written: asr_merge_dwconv_fwd reads the two branches and leaves cat +
+    dwconv(cat) for one asr_linear_fwd with K = 2E.  attention is
+    MultiheadAttention or RelPositionMultiheadAttention, the residuals are
+    asr_matadd, the last one the fused residual of the final asr_layernorm_fwd.
+    No arithmetic here; dropout is ignored.  ffn1 / ffn2: None or (LayerNorm, w1
+    [E, F], b1 [F], w2 [F, E], b2 [E]) already scaled; merge: (wd [k, 2E], bd
+    [2E], w [2E, E], b [E], padding)."""
+
+    def __init__(self, ffn1, attn_norm: LayerNorm, attn, mlp_norm: LayerNorm, cgmlp: ConvolutionalGatingMLP, merge,
+                 ffn2, final_norm: LayerNorm):
+        E = attn.E
+        assert cgmlp.E == E and attn_norm.N == E and mlp_norm.N == E and final_norm.N == E
+        self.E, self.attn_norm, self.attn, self.mlp_norm, self.cgmlp = E, attn_norm, attn, mlp_norm, cgmlp
+        self.final_norm = final_norm
+        self.ffn = []
+        for f in (ffn1, ffn2):
+            if f is None:
+                self.ffn.append(None)
+                continue
+            ln, w1, b1, w2, b2 = f
+            w1, w2 = np.asarray(w1, np.float32), np.asarray(w2, np.float32)
+            F = w1.shape[1]
+            assert ln.N == E and w1.shape == (E, F) and w2.shape == (F, E), (ln.N, w1.shape, w2.shape)
+            self.ffn.append((ln, F, DeviceMatrix.from_numpy(w1),
+                             DeviceMatrix.from_numpy(np.asarray(b1, np.float32).reshape(F, 1)),
+                             DeviceMatrix.from_numpy(w2),
+                             DeviceMatrix.from_numpy(np.asarray(b2, np.float32).reshape(E, 1))))
+        wd, bd, wm, bm, padding = merge
+        wd = np.asarray(wd, np.float32)
+        k = wd.shape[0]
+        assert wd.shape == (k, 2 * E), wd.shape
+        self.merge_desc = merge_dwconv_desc(E, k, *Conv1d.parse_padding(padding, k))
+        up = lambda a, shape: DeviceMatrix.from_numpy(np.asarray(a, np.float32).reshape(shape))   # noqa: E731
+        self.wd, self.bd, self.wm, self.bm = up(wd, (k, 2 * E)), up(bd, (2 * E, 1)), up(wm, (2 * E, E)), up(bm, (E, 1))
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_ffn(ln, lin1, lin2, scale: float = 0.5):
+        """ConformerLayer.pack_ffn for a scale of 1/2, the unscaled arrays for 1;
+        no other scale (the fold must be exact)."""
+        if scale == 0.5:
+            return ConformerLayer.pack_ffn(ln, lin1, lin2)
+        if scale != 1.0:
+            raise ValueError(f"EBranchformerLayer.pack_ffn: ff_scale {scale} is neither 1/2 nor 1")
+        if lin2.in_features != lin1.out_features or lin1.in_features != lin2.out_features:
+            raise ValueError("EBranchformerLayer.pack_ffn: the two linears do not chain E -> F -> E")
+        return _torch_linear(lin1) + _torch_linear(lin2)
+
+    @staticmethod
+    def pack_torch(ffn1, attn, cgmlp, merge, ffn2, final_norm, ff_scale: float = 0.5):
+        """Every packed float32 array of a block, from its torch parts (the
+        arguments of from_torch): a flat dict 'ffn1.w1', ..., 'attn.w_in', ...,
+        'cgmlp.wd', ..., 'merge.wd', 'merge.bd', 'merge.w', 'merge.b',
+        'merge.padding' and the LayerNorms' '<part>.norm_weight' / '.norm_bias'
+        / '.norm_eps' (parts ffn1, ffn2, attn, mlp, final).  No device call."""
+        host = lambda p: None if p is None else p.detach().cpu().float().numpy()   # noqa: E731
+        out = {}
+
+        def norm(prefix, ln):
+            if len(tuple(ln.normalized_shape)) != 1:
+                raise ValueError(f"EBranchformerLayer.pack_torch: {prefix} LayerNorm over "
+                                 f"{tuple(ln.normalized_shape)}")
+            out[prefix + ".norm_weight"] = host(getattr(ln, "weight", None))
+            out[prefix + ".norm_bias"] = host(getattr(ln, "bias", None))
+            out[prefix + ".norm_eps"] = float(ln.eps)
+
+        for name, f in (("ffn1", ffn1), ("ffn2", ffn2)):
+            if f is None:
+                continue
+            norm(name, f[0])
+            for key, a in zip(("w1", "b1", "w2", "b2"), EBranchformerLayer.pack_ffn(*f, scale=ff_scale)):
+                out[f"{name}.{key}"] = a
+        norm("attn", attn[0])
+        if hasattr(attn[1], "linear_pos"):           # the toolkits' relative-position module
+            keys = ("w_in", "b_in", "w_pos", "bias_u", "bias_v", "w_out", "b_out")
+            packed, heads = RelPositionMultiheadAttention.pack_torch(attn[1]), attn[1].pos_bias_u.shape[0]
+        else:
+            keys = ("w_in", "b_in", "w_out", "b_out")
+            packed, heads = MultiheadAttention.pack_torch(attn[1]), attn[1].num_heads
+        for key, a in zip(keys, packed):
+            out["attn." + key] = a
+        out["attn.heads"] = int(heads)
+        norm("mlp", cgmlp[0])
+        for key, a in ConvolutionalGatingMLP.pack_torch(cgmlp[1]).items():
+            out["cgmlp." + key] = a
+        E = out["attn.w_out"].shape[0]
+        dw, proj = merge
+        out["merge.wd"], out["merge.bd"], out["merge.padding"] = _torch_depthwise(
+            "EBranchformerLayer.pack_torch: depthwise_conv_fusion", dw, 2 * E)
+        out["merge.w"], out["merge.b"] = _torch_linear(proj)
+        if out["merge.w"].shape != (2 * E, E):
+            raise ValueError(f"EBranchformerLayer.pack_torch: merge_proj is {out['merge.w'].shape}, not {(2 * E, E)}")
+        norm("final", final_norm)
+        return out
+
+    @classmethod
+    def from_torch(cls, ffn1, attn, cgmlp, merge, ffn2, final_norm, ff_scale: float = 0.5, chunk: int = 1,
+                   left: int = -1, right: int = -1) -> "EBranchformerLayer":
+        """From explicit torch parts: ffn1 / ffn2 = None or (LayerNorm, Linear,
+        Linear), attn = (LayerNorm, MultiheadAttention or a relative-position
+        module with linear_pos), cgmlp = (LayerNorm, a module of ESPnet's
+        ConvolutionalGatingMLP layout), merge = (depthwise Conv1d over 2E
+        channels, Linear 2E -> E), final_norm a LayerNorm; ff_scale 1/2 or 1;
+        chunk / left / right the attention window."""
+        p = cls.pack_torch(ffn1, attn, cgmlp, merge, ffn2, final_norm, ff_scale)
+        E = p["attn.w_out"].shape[0]
+        ln = lambda k: LayerNorm(E, p[k + ".norm_eps"], p[k + ".norm_weight"], p[k + ".norm_bias"])   # noqa: E731
+        ffn = lambda k: ((ln(k), p[k + ".w1"], p[k + ".b1"], p[k + ".w2"], p[k + ".b2"])   # noqa: E731
+                         if k + ".w1" in p else None)
+        if "attn.w_pos" in p:
+            mha = RelPositionMultiheadAttention(E, p["attn.heads"], p["attn.w_in"], p["attn.b_in"], p["attn.w_pos"],
+                                                p["attn.bias_u"], p["attn.bias_v"], p["attn.w_out"],
+                                                p["attn.b_out"], chunk, left, right)
+        else:
+            mha = MultiheadAttention(E, p["attn.heads"], p["attn.w_in"], p["attn.b_in"], p["attn.w_out"],
+                                     p["attn.b_out"], chunk, left, right)
+        mlp = ConvolutionalGatingMLP(**{k[6:]: v for k, v in p.items() if k.startswith("cgmlp.")})
+        merge_p = (p["merge.wd"], p["merge.bd"], p["merge.w"], p["merge.b"], p["merge.padding"])
+        return cls(ffn("ffn1"), ln("attn"), mha, ln("mlp"), mlp, merge_p, ffn("ffn2"), ln("final"))
+
+    @staticmethod
+    def espnet_parts(layer) -> dict:
+        """The parts of from_torch read off a module laid out like ESPnet's
+        EBranchformerEncoderLayer (see from_espnet)."""
+        def ffn(ln, ff):
+            if ff is None:
+                return None
+            name = type(ff.activation).__name__.lower()
+            if name not in ("swish", "silu"):
+                raise ValueError(f"EBranchformerLayer.from_espnet: feed-forward activation {name!r} is not supported "
+                                 "(Swish / SiLU only)")
+            return ln, ff.w_1, ff.w_2
+
+        mac = getattr(layer, "feed_forward_macaron", None)
+        return dict(ffn1=ffn(getattr(layer, "norm_ff_macaron", None), mac),
+                    attn=(layer.norm_mha, layer.attn), cgmlp=(layer.norm_mlp, layer.cgmlp),
+                    merge=(layer.depthwise_conv_fusion, layer.merge_proj),
+                    ffn2=ffn(getattr(layer, "norm_ff", None), getattr(layer, "feed_forward", None)),
+                    final_norm=layer.norm_final,
+                    ff_scale=float(getattr(layer, "ff_scale", 0.5 if mac is not None else 1.0)))
+
+    @classmethod
+    def from_espnet(cls, layer, chunk: int = 1, left: int = -1, right: int = -1) -> "EBranchformerLayer":
+        """A thin adapter over from_torch for a module with the attribute
+        layout of ESPnet's EBranchformerEncoderLayer: feed_forward_macaron /
+        feed_forward (w_1, w_2, a Swish activation; either may be None) with
+        norm_ff_macaron / norm_ff and ff_scale, norm_mha + attn
+        (MultiheadAttention, or the linear_pos kind), norm_mlp + cgmlp
+        (channel_proj1[0], csgu.norm, csgu.conv, channel_proj2),
+        depthwise_conv_fusion, merge_proj, norm_final.  That layout is written
+        from memory: this adapter was never run against ESPnet itself, only
+        against a stand-in module with those attribute names
+        (tests/ebranchformer_reference.py)."""
+        return cls.from_torch(**cls.espnet_parts(layer), chunk=chunk, left=left, right=right)
+
+    def _ffn(self, i: int, x, T: int, B: int, lengths, st: int):
+        """s FFN_i(x) into a scratch buffer."""
+        ln, F, w1, b1, w2, b2 = self.ffn[i]
+        M, sc = T * B, self._scratch
+        n, ff, t = sc.get("n", M, self.E), sc.get("ff", M, F), sc.get("t", M, self.E)
+        ln.forward(x, T, B, lengths, out=n, stream=st)
+        linear_fwd(n, w1, b1, ff, EPI_BIAS_SILU, st)
+        linear_fwd(ff, w2, b2, t, EPI_BIAS, st)
+        return t
+
+    def forward(self, x, T: int, B: int, lengths=None, stream: int = 0) -> DeviceMatrix:
+        """x time-major [T*B, E]; lengths None, a sequence of B counts or a
+        DeviceBytes of int32 [B].  Returns a new DeviceMatrix [T*B, E] with zero
+        rows past the lengths; rows of x past them may hold anything."""
+        E, M, st = self.E, T * B, stream or 0
+        if hasattr(x, "rows"):
+            _need_matrix("EBranchformerLayer.forward: x", x, M, E)
+        lengths = _device_lengths_or_none(lengths)
+        sc = self._scratch
+        h, h2, n, cat = sc.get("h", M, E), sc.get("h2", M, E), sc.get("n", M, E), sc.get("cat", M, 2 * E)
+        add = lambda a, b, z: check(lib().asr_matadd(a.ptr, b.ptr, z.ptr, M, E, 1.0, st), "asr_matadd")   # noqa: E731
+        out = DeviceMatrix(M, E)
+        if self.ffn[0] is not None:
+            add(x, self._ffn(0, x, T, B, lengths, st), h)
+        else:
+            h = x
+        self.attn_norm.forward(h, T, B, lengths, out=n, stream=st)
+        a = self.attn.forward(n, T, B, lengths, zero_padding=False, stream=st)
+        self.mlp_norm.forward(h, T, B, lengths, out=n, stream=st)
+        m = self.cgmlp.forward(n, T, B, lengths, zero_padding=False, stream=st)
+        merge_dwconv_fwd(a, m, self.wd, self.bd, cat, T, B, self.merge_desc, lengths, st)
+        t = sc.get("t", M, E)
+        linear_fwd(cat, self.wm, self.bm, t, EPI_BIAS, st)
+        add(h, t, h2)
+        if self.ffn[1] is not None:
+            self.final_norm.forward(self._ffn(1, h2, T, B, lengths, st), T, B, lengths, res=h2, out=out, stream=st)
+        else:
+            self.final_norm.forward(h2, T, B, lengths, out=out, stream=st)
+        self._keep = lengths
+        return out
+
+
+class EBranchformer:
+    """A stack of EBranchformerLayers run in turn with the same lengths."""
+
+    def __init__(self, layers: Sequence[EBranchformerLayer]):
         self.layers = list(layers)
         assert self.layers and all(l.E == self.layers[0].E for l in self.layers)
         self.E = self.layers[0].E

@@ -11,13 +11,25 @@ enum GemmEpilogue {
     EPI_LOGSOFTMAX = 3,  // C = log_softmax(A.B + b1) per row (fused for N <= 64)
     EPI_DUAL_TANH = 4,   // C = tanh((A.B + A2.B2) + (b2 + b1))
     EPI_ADD_TANH = 5,    // C = tanh((D + A.B) + (b2 + b1)); C may alias D
-    EPI_BIAS_SILU = 6    // C = silu(A.B + b1)
+    EPI_BIAS_SILU = 6,   // C = silu(A.B + b1)
+    EPI_BIAS_GELU = 7    // C = gelu(A.B + b1), the exact (erf) form
 };
+
+// The epilogues that add b1 and then apply an element-wise function (or none).
+constexpr bool epi_has_bias(int epi) {
+    return epi == EPI_BIAS || epi == EPI_BIAS_RELU || epi == EPI_BIAS_SILU || epi == EPI_BIAS_GELU;
+}
 
 // SiLU / Swish of a pre-activation, v / (1 + exp(-v)): one expression for every
 // GEMM epilogue and for glu_conv.hip.  v -> -inf: exp overflows to +inf and the
 // quotient is -0; v -> +inf: the quotient is v.
 __device__ __forceinline__ float silu_f32(float v) { return v / (1.f + __expf(-v)); }
+
+// Exact GELU of a pre-activation, v/2 * (1 + erf(v / sqrt 2)), written with
+// 1 + erf(x) = erfc(-x): one expression for both signs and no cancellation in
+// the negative tail (1 + erf(x) loses every digit below x = -3.5).  v -> -inf:
+// erfc -> 0 and the product is -0; v -> +inf: erfc -> 2 and the product is v.
+__device__ __forceinline__ float gelu_f32(float v) { return (0.5f * v) * erfcf(-0.70710678118654752f * v); }
 
 struct GemmArgs {
     const float* A;   // A(m,k) = A[m*sam + k*sak]

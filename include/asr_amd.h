@@ -90,7 +90,8 @@ typedef enum asr_epilogue {
     ASR_EPI_BIAS = 1,            /* y = x.W + b                                     */
     ASR_EPI_BIAS_RELU = 2,       /* y = max(x.W + b, 0)  — Linear.cu:3-10 ReLU      */
     ASR_EPI_BIAS_LOGSOFTMAX = 3, /* y = log_softmax(x.W + b) per row (model.py:49)  */
-    ASR_EPI_BIAS_SILU = 4        /* y = v / (1 + exp(-v)), v = x.W + b (SiLU / Swish) */
+    ASR_EPI_BIAS_SILU = 4,       /* y = v / (1 + exp(-v)), v = x.W + b (SiLU / Swish) */
+    ASR_EPI_BIAS_GELU = 6        /* y = v/2 * erfc(-v / sqrt(2)), v = x.W + b (exact GELU); 5 is not assigned */
 } asr_epilogue;
 
 /* Linear::forward (Linear.cu:42-49): y[M,N] = epi(x[M,K] . W[K,N] + b[N]).
@@ -99,7 +100,11 @@ typedef enum asr_epilogue {
  * activation; no reference member) is applied where the bias is, in every
  * kernel and both arithmetics a bias GEMM can land on, so the kernel choice
  * and a row's independence of M are those of ASR_EPI_BIAS; a pre-activation
- * of -100 gives -0 (exp overflows to +inf), never NaN.  Every epilogue but
+ * of -100 gives -0 (exp overflows to +inf), never NaN.  ASR_EPI_BIAS_GELU
+ * (the cgMLP's activation: the exact GELU, torch.nn.GELU()'s default, not the
+ * tanh approximation) is applied in the same places under the same rules, as
+ * v/2 * erfc(-v / sqrt(2)): 1 + erf(x) = erfc(-x) has no cancellation in the
+ * negative tail; -100 gives -0 and +100 gives 100.  Every epilogue but
  * ASR_EPI_NONE needs d_b (NULL: ASR_ERR_ARG). */
 int asr_linear_fwd(const float* d_x, const float* d_W, const float* d_b, float* d_y, int M,
                    int K, int N, int epilogue, asr_stream_t s);
@@ -512,6 +517,69 @@ int asr_glu_dwconv_fwd(const asr_glu_dwconv_desc* d, const float* d_u, long ldu,
                        const float* d_w, const float* d_b, float* d_out, long ldo, int T, int B,
                        asr_stream_t s);
 
+/* The two depthwise pieces of an E-Branchformer block,
+ * time-major, fp32 always; no reference member.  Both: stride 1, dilation 1,
+ * pad_left + pad_right = kernel - 1, one fmaf chain per element from 0, taps
+ * ascending, then the bias; d_lengths device int32 [B], clamped to [0, T],
+ * NULL = all T; frames t >= len[b] of the inputs are never read (the zero is
+ * selected, not multiplied: they may hold NaN) and rows t >= len[b] of out are
+ * zeros: each utterance on its own frames.  An output row's bits depend only
+ * on the values in its receptive field, the weights and the descriptor: never
+ * on T, B, the row's position, other utterances, the strides or pointer
+ * alignment, so a causal module run over chunks with their k - 1 history
+ * frames prepended gives the whole call's bits.  Asynchronous on s, no
+ * allocation, no host sync.
+ *
+ * asr_csgu_fwd: the convolutional spatial gating unit of a cgMLP.  d_u: row
+ * t*B + b holds >= 2C floats, row stride ldu: columns [0, C) the values x_r,
+ * [C, 2C) the gates x_g (torch's chunk(2, dim=-1)); d_gamma / d_beta [C] or
+ * NULL (1 / 0); d_w [kernel][C], d_b [C] or NULL; d_out rows receive C floats.
+ *   n(t, b, c)   = (((x_g - mean0) - corr) * rstd) * gamma[c] + beta[c]   for t < len[b], exactly 0 outside
+ *   out(t, b, c) = x_r(t, b, c) * ((sum_{j<k} n(t - pl + j, b, c) w[j][c]) + b[c])
+ * mean0 + corr is the refined mean over the row's C gates and rstd =
+ * 1 / sqrt(var + eps), by asr_layernorm_fwd's expressions and tree (two-pass,
+ * biased).  A padded frame's LayerNorm output (beta) never leaks into a real
+ * frame.  Two launches: a statistics pre-pass writes (mean0, corr, rstd) of
+ * each row inside its length into d_stats, 3*T*B floats of the caller's (the
+ * mean in its two parts: one fp32 would centre a row at 1000 +- 1 up to 3e-5
+ * off); then the convolution, which normalises each staged gate once.
+ * Checks, in this order, all before any HIP call — ASR_ERR_ARG: a NULL
+ * descriptor, d_u, d_w, d_stats or d_out; non-positive T, B, channels or
+ * kernel; a negative pad; ldu < 2C or ldo < C; eps not finite or negative;
+ * d_out == d_u.  ASR_ERR_UNSUPPORTED: pad_left + pad_right != kernel - 1;
+ * kernel > ASR_CGMLP_MAX_KERNEL; C > 4096; T*B > INT_MAX or T > INT_MAX -
+ * 4096; B * ceil(T / 64) * ceil(C / 64) > INT_MAX.
+ *
+ * asr_merge_dwconv_fwd: x + dwconv(x) over x = cat(x1, x2) without the
+ * concatenation (ESPnet's depthwise_conv_fusion and its residual).  d_x1 /
+ * d_x2: rows of >= C floats, strides ldx1 / ldx2; d_w [kernel][2C], d_b [2C]
+ * or NULL; d_out rows receive 2C floats, stride ldo >= 2C.
+ *   s(t, b, c')   = c' < C ? x1(t, b, c') : x2(t, b, c' - C)   for t < len[b], exactly 0 outside
+ *   out(t, b, c') = s(t, b, c') + ((sum_{j<k} s(t - pl + j, b, c') w[j][c']) + b[c'])
+ * One launch; each source is read once.  Checks as above without d_stats and
+ * eps, with ldx1 < C, ldx2 < C or ldo < 2C, and d_out == d_x1 or d_out == d_x2
+ * refused; the grid is B * ceil(T / 64) * ceil(2C / 64).
+ * Not built: a split-bf16 variant, csgu.linear (use_linear_after_conv), a gate
+ * activation. */
+#define ASR_CGMLP_MAX_KERNEL 80
+typedef struct asr_csgu_desc {
+    int channels;             /* C: u rows have 2C floats, out rows C */
+    int kernel;               /* k taps, 1 .. ASR_CGMLP_MAX_KERNEL */
+    int pad_left, pad_right;  /* >= 0, pad_left + pad_right == kernel - 1 */
+    float eps;                /* the LayerNorm's, finite and >= 0 */
+} asr_csgu_desc;
+typedef struct asr_merge_dwconv_desc {
+    int channels;             /* C per source: out rows have 2C floats */
+    int kernel;
+    int pad_left, pad_right;
+} asr_merge_dwconv_desc;
+int asr_csgu_fwd(const asr_csgu_desc* d, const float* d_u, long ldu, const int32_t* d_lengths, const float* d_gamma,
+                 const float* d_beta, const float* d_w, const float* d_b, float* d_stats, float* d_out, long ldo,
+                 int T, int B, asr_stream_t s);
+int asr_merge_dwconv_fwd(const asr_merge_dwconv_desc* d, const float* d_x1, long ldx1, const float* d_x2, long ldx2,
+                         const int32_t* d_lengths, const float* d_w, const float* d_b, float* d_out, long ldo, int T,
+                         int B, asr_stream_t s);
+
 /* Scaled dot-product self-attention over time, all heads in one launch —
  * softmax(Q K^T * scale) V per head with per-utterance lengths and an optional
  * chunked window: the hot path of torch.nn.MultiheadAttention in Transformer /
@@ -658,8 +726,9 @@ int asr_attention_rel_fwd(const asr_attn_desc* d, const float* d_q, long ldq, co
  * T*B > INT_MAX; U*max_hyps > INT_MAX - 64.
  * (Autoregressive decoding with a K/V cache is asr_decode_attention_fwd below.)
  * Not built: a right-to-left decoder (reverse_weight); a compaction of dead
- * query lanes (a lane past qlen[n] stays in its tile); GELU in the decoder's
- * feed-forward. */
+ * query lanes (a lane past qlen[n] stays in its tile); GELU in the decoder
+ * layer's feed-forward (asr_linear_fwd has ASR_EPI_BIAS_GELU; the Python layer
+ * classes do not take it yet). */
 typedef struct asr_xattn_desc {
     int heads, head_dim;   /* limits of asr_attn_desc */
     float scale;           /* 0 = 1/sqrt(head_dim); else finite, > 0 */
@@ -890,8 +959,9 @@ int asr_ctc_prefix_advance(const asr_ctc_prefix_desc* d, const float* d_emis, lo
  * be exactly d_x or d_res (in place).  One wave per row; the sums are a fixed
  * tree (a lane's columns l, l + 64, ... ascending, then the butterfly over the
  * lanes, as asr_lm_score's), so a row's bits never depend on T, B or the
- * row's position.  fp32 always.  GELU is not built (asr_linear_fwd fuses ReLU
- * and Swish / SiLU; GLU is in asr_glu_dwconv_fwd: DESIGN.md section 30).
+ * row's position.  fp32 always.  (asr_linear_fwd fuses ReLU, Swish / SiLU
+ * and GELU; GLU is in asr_glu_dwconv_fwd, the cgMLP's gating unit in
+ * asr_csgu_fwd: DESIGN.md sections 30 and 39.)
  * One launch, asynchronous on s.  Checks, in this order, before any HIP call —
  * ASR_ERR_ARG: NULL d_x or d_out; non-positive T, B or N; a stride < N; eps not
  * finite or < 0.  ASR_ERR_UNSUPPORTED: N > 4096; T*B > INT_MAX. */
