@@ -177,6 +177,8 @@ EXPORTS = [
     "asr_gru_workspace_bytes", "asr_gru_fwd", "asr_gru_recur_fwd",
     "asr_conv1d_out_frames", "asr_conv1d_fwd", "asr_glu_dwconv_fwd",
     "asr_csgu_fwd", "asr_merge_dwconv_fwd",
+    "asr_grouped_conv1d_out_frames", "asr_grouped_conv1d_fwd", "asr_wave_conv_out_frames",
+    "asr_wave_conv_workspace_bytes", "asr_wave_conv_fwd", "asr_layernorm_gelu_fwd",
     "asr_conv2d_out_frames", "asr_conv2d_out_feats", "asr_conv2d_fwd",
     "asr_attention_fwd", "asr_attention_rel_fwd", "asr_layernorm_fwd", "asr_mask_rows",
     "asr_cross_attention_fwd", "asr_token_score",
@@ -404,6 +406,13 @@ def lib() -> ctypes.CDLL:
         "asr_ctc_align": [_vp, _i, _i, _i, ctypes.c_long, ctypes.c_long, _vp, _i, _i, _vp, ctypes.c_long, _vp, _vp,
                           _i, _i, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp],
     }
+    sig["asr_grouped_conv1d_fwd"] = [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp,
+                                     _i, _i, _vp]
+    sig["asr_grouped_conv1d_out_frames"] = [_vp, _i]
+    sig["asr_wave_conv_fwd"] = [_vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _i, _i,
+                                _vp]
+    sig["asr_wave_conv_out_frames"] = [_vp, _i]
+    sig["asr_layernorm_gelu_fwd"] = [_vp, ctypes.c_long, _vp, _vp, _f, _i, _vp, _vp, ctypes.c_long, _i, _i, _i, _vp]
     for name, args in sig.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -414,6 +423,8 @@ def lib() -> ctypes.CDLL:
     L.asr_lstm_workspace_bytes.restype = _sz
     L.asr_gru_workspace_bytes.argtypes = [_i, _i, _i]
     L.asr_gru_workspace_bytes.restype = _sz
+    L.asr_wave_conv_workspace_bytes.argtypes = [_vp, _i, _i]
+    L.asr_wave_conv_workspace_bytes.restype = _sz
     L.asr_fbank_workspace_bytes.argtypes = [_vp, _i, _i]
     L.asr_fbank_workspace_bytes.restype = _sz
     L.asr_ctc_align_workspace_bytes.argtypes = [_i, _i, _i]
@@ -1740,15 +1751,19 @@ class RelPositionMultiheadAttention:
 
 
 class TransformerEncoderLayer:
-    """torch.nn.TransformerEncoderLayer (ReLU feed-forward, norm_first either
-    way) for inference, time-major: MultiheadAttention, two LayerNorms and two
-    asr_linear_fwd (the first with bias + ReLU fused).  Post-norm uses the
+    """torch.nn.TransformerEncoderLayer (ReLU feed-forward, or GELU with
+    activation="gelu": the layers of Wav2Vec2Encoder; norm_first either way)
+    for inference, time-major: MultiheadAttention, two LayerNorms and two
+    asr_linear_fwd (the first with bias + activation fused).  Post-norm uses the
     fused residual of asr_layernorm_fwd, pre-norm asr_matadd.  Dropout is
     ignored."""
 
     def __init__(self, attn: MultiheadAttention, norm1: LayerNorm, norm2: LayerNorm, w1, b1, w2, b2,
-                 norm_first: bool = False):
+                 norm_first: bool = False, activation: str = "relu"):
+        if activation not in ("relu", "gelu"):
+            raise ValueError(f"TransformerEncoderLayer: activation {activation!r} is not 'relu' or 'gelu'")
         E = attn.E
+        self._epi = EPI_BIAS_RELU if activation == "relu" else EPI_BIAS_GELU
         w1, w2 = np.asarray(w1, np.float32), np.asarray(w2, np.float32)
         F = w1.shape[1]
         assert w1.shape == (E, F) and w2.shape == (F, E), (w1.shape, w2.shape)
@@ -1796,7 +1811,7 @@ class TransformerEncoderLayer:
             a = self.attn.forward(n, T, B, lengths, zero_padding=False, stream=st)
             check(lib().asr_matadd(x.ptr, a.ptr, h.ptr, M, E, 1.0, st), "asr_matadd")
             self.norm2.forward(h, T, B, lengths, out=n, stream=st)
-            linear_fwd(n, self.w1, self.b1, ff, EPI_BIAS_RELU, st)
+            linear_fwd(n, self.w1, self.b1, ff, self._epi, st)
             linear_fwd(ff, self.w2, self.b2, n, EPI_BIAS, st)
             check(lib().asr_matadd(h.ptr, n.ptr, out.ptr, M, E, 1.0, st), "asr_matadd")
             if lengths is not None:
@@ -1805,7 +1820,7 @@ class TransformerEncoderLayer:
             a = self.attn.forward(x, T, B, lengths, zero_padding=False, stream=st)
             self.norm1.forward(a, T, B, lengths, res=x, out=h, stream=st)
             f2 = sc.get("f2", M, E)
-            linear_fwd(h, self.w1, self.b1, ff, EPI_BIAS_RELU, st)
+            linear_fwd(h, self.w1, self.b1, ff, self._epi, st)
             linear_fwd(ff, self.w2, self.b2, f2, EPI_BIAS, st)
             self.norm2.forward(f2, T, B, lengths, res=h, out=out, stream=st)
         self._keep = lengths
@@ -3659,6 +3674,380 @@ class EBranchformer:
             x = layer.forward(x, T, B, lengths, stream=stream)
         self._keep = lengths
         return x
+
+
+# ------------------------------------------- wav2vec 2.0 / HuBERT encoders
+WAVE_NORM_NONE, WAVE_NORM_CHANNEL, WAVE_NORM_TIME = 0, 1, 2
+WAVE_NORMS = {None: WAVE_NORM_NONE, "none": WAVE_NORM_NONE, "channel": WAVE_NORM_CHANNEL, "layer": WAVE_NORM_CHANNEL,
+              "time": WAVE_NORM_TIME, "group": WAVE_NORM_TIME}
+GCONV_ACT_NONE, GCONV_ACT_GELU = 0, 1
+
+
+class GroupedConv1dDesc(ctypes.Structure):
+    """asr_grouped_conv1d_desc (include/asr_amd.h)."""
+    _fields_ = [("c_in", _i), ("c_out", _i), ("kernel", _i), ("pad_left", _i), ("pad_right", _i), ("groups", _i),
+                ("act", _i)]
+
+
+class WaveConvDesc(ctypes.Structure):
+    """asr_wave_conv_desc (include/asr_amd.h)."""
+    _fields_ = [("channels", _i), ("kernel", _i), ("stride", _i), ("norm", _i), ("eps", _f)]
+
+
+def grouped_conv1d_desc(c_in: int, c_out: int, kernel: int, groups: int, pad_left: int = 0, pad_right: int = 0,
+                        act=None) -> GroupedConv1dDesc:
+    """A GroupedConv1dDesc from keywords; act: None, "gelu" or an ASR_GCONV_ACT_* value."""
+    a = {None: GCONV_ACT_NONE, "none": GCONV_ACT_NONE, "gelu": GCONV_ACT_GELU}[act] if not isinstance(act, int) else act
+    return GroupedConv1dDesc(c_in, c_out, kernel, pad_left, pad_right, groups, a)
+
+
+def grouped_conv1d_out_frames(desc: GroupedConv1dDesc, n: int) -> int:
+    """asr_grouped_conv1d_out_frames: frames out for n frames in (< 0 for a refused descriptor)."""
+    return int(lib().asr_grouped_conv1d_out_frames(ctypes.byref(desc), int(n)))
+
+
+def grouped_conv1d_fwd(x, W: DeviceMatrix, b: Optional[DeviceMatrix], out, T: int, B: int, desc: GroupedConv1dDesc,
+                       res=None, lengths: Optional[DeviceBytes] = None, out_lengths: Optional[DeviceBytes] = None,
+                       stream: int = 0):
+    """out = res + act(grouped conv(x) + b) (asr_grouped_conv1d_fwd): x [T*B, >= c_in]
+    and out [T_out*B, >= c_out] time-major (the row strides are their .cols), W
+    [k * c_in / groups, c_out], b [c_out] or None, res None or rows of >= c_out
+    floats (it may be x)."""
+    T_out = grouped_conv1d_out_frames(desc, T)
+    assert x.cols >= desc.c_in and out.cols >= desc.c_out, (x.cols, out.cols)
+    assert T_out <= 0 or getattr(out, "rows", T_out * B) == T_out * B, (out.rows, T_out, B)
+    assert W.rows * W.cols == desc.kernel * (desc.c_in // max(desc.groups, 1)) * desc.c_out, (W.rows, W.cols)
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_grouped_conv1d_fwd(ctypes.byref(desc), x.ptr, x.cols, opt(lengths), W.ptr, opt(b), opt(res),
+                                       res.cols if res is not None else 0, out.ptr, out.cols, opt(out_lengths), T, B,
+                                       stream), "asr_grouped_conv1d_fwd")
+    return out
+
+
+def wave_conv_desc(channels: int, kernel: int, stride: int, norm=None, eps: float = 1e-5) -> WaveConvDesc:
+    """A WaveConvDesc from keywords; norm: None, "layer" / "channel", "group" / "time" or an ASR_WAVE_NORM_* value."""
+    return WaveConvDesc(channels, kernel, stride, norm if isinstance(norm, int) else WAVE_NORMS[norm], eps)
+
+
+def wave_conv_out_frames(desc: WaveConvDesc, n: int) -> int:
+    """asr_wave_conv_out_frames: frames out for n samples in (< 0 for a refused descriptor)."""
+    return int(lib().asr_wave_conv_out_frames(ctypes.byref(desc), int(n)))
+
+
+def wave_conv_workspace_bytes(desc: WaveConvDesc, S: int, B: int) -> int:
+    return int(lib().asr_wave_conv_workspace_bytes(ctypes.byref(desc), int(S), int(B)))
+
+
+def wave_conv_fwd(wave, W: DeviceMatrix, b: Optional[DeviceMatrix], out, B: int, S: int, desc: WaveConvDesc,
+                  gamma=None, beta=None, work: Optional[DeviceBytes] = None, nsamples: Optional[DeviceBytes] = None,
+                  out_lengths: Optional[DeviceBytes] = None, stream: int = 0):
+    """The first feature-encoder layer (asr_wave_conv_fwd): wave [B, >= S]
+    batch-major (the row stride is wave.cols), W [k, C], b / gamma / beta [C] or
+    None, out [T1*B, >= C] time-major; work a DeviceBytes of
+    wave_conv_workspace_bytes(desc, S, B) for the time norm (allocated here if
+    None: pass one to keep the call free of allocation)."""
+    assert wave.cols >= S and out.cols >= desc.channels, (wave.cols, out.cols)
+    assert W.rows * W.cols == desc.kernel * desc.channels, (W.rows, W.cols)
+    need = wave_conv_workspace_bytes(desc, S, B)
+    if need and work is None:
+        work = DeviceBytes(need)
+    assert not need or work.nbytes >= need, (work.nbytes, need)
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_wave_conv_fwd(ctypes.byref(desc), wave.ptr, wave.cols, opt(nsamples), W.ptr, opt(b), opt(gamma),
+                                  opt(beta), opt(work), out.ptr, out.cols, opt(out_lengths), B, S, stream),
+          "asr_wave_conv_fwd")
+    return out
+
+
+def layernorm_gelu_fwd(x, out, T: int, B: int, N: int, gamma=None, beta=None, eps: float = 1e-5, norm: bool = True,
+                       lengths: Optional[DeviceBytes] = None, stream: int = 0):
+    """gelu(LayerNorm(x)) over the first N columns of each row, or gelu(x) with
+    norm False (asr_layernorm_gelu_fwd); out may be x; rows past lengths become
+    zeros."""
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_layernorm_gelu_fwd(x.ptr, x.cols, opt(gamma), opt(beta), eps, 1 if norm else 0, opt(lengths),
+                                       out.ptr, out.cols, T, B, N, stream), "asr_layernorm_gelu_fwd")
+    return out
+
+
+class GroupedConv1d:
+    """torch.nn.Conv1d(c_in, c_out, kernel, groups=g) with 1 < g < c_in, stride
+    and dilation 1, for inference on asr_grouped_conv1d_fwd, time-major, bias,
+    GELU (act "gelu") and a residual fused.  padding: (left, right) or an int;
+    weight [k][c_in / g][c_out], bias [c_out] (zeros if None)."""
+
+    def __init__(self, c_in: int, c_out: int, kernel: int, groups: int, padding=0, act=None, weight=None, bias=None):
+        pl, pr = Conv1d.parse_padding(padding, kernel)
+        self.desc = grouped_conv1d_desc(c_in, c_out, kernel, groups, pl, pr, act)
+        rc = grouped_conv1d_out_frames(self.desc, 1 << 20)
+        if rc < 0:
+            raise AsrError(-rc, "asr_grouped_conv1d_out_frames")
+        shape = (kernel * (c_in // groups), c_out)
+        w = np.zeros(shape, np.float32) if weight is None else np.asarray(weight, np.float32).reshape(shape)
+        b = np.zeros(c_out, np.float32) if bias is None else np.asarray(bias, np.float32).reshape(c_out)
+        self.W, self.b = DeviceMatrix.from_numpy(w), DeviceMatrix.from_numpy(b.reshape(-1, 1))
+        self._keep = None
+
+    @staticmethod
+    def pack_torch(conv, same_pad: bool = False):
+        """(W [k][c_in/g][c_out] float32, b [c_out] float32, keywords) from a
+        torch.nn.Conv1d; conv.weight is read, so a weight-norm parametrisation
+        is already folded.  same_pad: the module is followed by HF's
+        Wav2Vec2SamePadLayer, which drops the last frame when the kernel is
+        even (pad_right one less).  No device call."""
+        if conv.padding_mode != "zeros" or isinstance(conv.padding, str):
+            raise ValueError("GroupedConv1d.pack_torch: zero padding given as numbers only")
+        if conv.stride[0] != 1 or conv.dilation[0] != 1:
+            raise ValueError("GroupedConv1d.pack_torch: stride and dilation must be 1")
+        k, pad = conv.kernel_size[0], int(conv.padding[0])
+        pr = pad - 1 if same_pad and k % 2 == 0 else pad
+        if pr < 0:
+            raise ValueError("GroupedConv1d.pack_torch: SamePad of an even kernel needs padding >= 1")
+        w = conv.weight.detach().cpu().double().numpy()                  # [c_out][c_in/g][k]
+        b = (conv.bias.detach().cpu().float().numpy() if conv.bias is not None
+             else np.zeros(conv.out_channels, np.float32))
+        W = np.ascontiguousarray(w.transpose(2, 1, 0)).astype(np.float32)
+        return W, b, dict(c_in=conv.in_channels, c_out=conv.out_channels, kernel=k, groups=conv.groups,
+                          padding=(pad, pr))
+
+    @classmethod
+    def from_torch(cls, conv, act=None, same_pad: bool = False) -> "GroupedConv1d":
+        W, b, kw = cls.pack_torch(conv, same_pad)
+        return cls(**kw, act=act, weight=W, bias=b)
+
+    def out_frames(self, n: int) -> int:
+        return grouped_conv1d_out_frames(self.desc, n)
+
+    def forward(self, x, T: int, B: int, lengths=None, res=None, out=None, stream: int = 0):
+        """x time-major [T*B, c_in]; returns (out [T_out*B, c_out] = res + act(conv(x) + b)
+        with zero rows past each utterance's count, T_out, out_lengths or None)."""
+        T_out = self.out_frames(T)
+        if T_out <= 0:
+            raise AsrError(ASR_ERR_ARG if T_out == 0 else -T_out, "asr_grouped_conv1d_out_frames")
+        lengths = _device_lengths_or_none(lengths)
+        out = DeviceMatrix(T_out * B, self.desc.c_out) if out is None else out
+        oln = None if lengths is None else DeviceBytes(4 * B)
+        grouped_conv1d_fwd(x, self.W, self.b, out, T, B, self.desc, res, lengths, oln, stream or 0)
+        self._keep = lengths
+        return out, T_out, oln
+
+
+class Wav2Vec2FeatureEncoder:
+    """The convolutional feature encoder of wav2vec 2.0 / HuBERT for inference:
+    asr_wave_conv_fwd for layer 0 (convolution, norm and GELU in one entry
+    point), then asr_conv1d_fwd + asr_layernorm_gelu_fwd per layer.  layers: a
+    sequence of dicts with weight ([k][c_in][c_out]; layer 0: [k][C]), bias
+    ([c_out] or None), kernel, stride and, where the layer has a norm, gamma,
+    beta, eps.  mode "group": layer 0 normalises each channel over the
+    utterance's own frames (GroupNorm(C, C)), the others have no norm; "layer":
+    every layer has a LayerNorm over its channels."""
+
+    def __init__(self, layers, mode: str):
+        if mode not in ("group", "layer"):
+            raise ValueError(f"Wav2Vec2FeatureEncoder: mode {mode!r} is not 'group' or 'layer'")
+        self.mode = mode
+        col = lambda a, n: None if a is None else DeviceMatrix.from_numpy(   # noqa: E731
+            np.asarray(a, np.float32).reshape(n, 1))
+        first = layers[0]
+        C = np.asarray(first["weight"]).shape[-1]
+        self.desc0 = wave_conv_desc(C, first["kernel"], first["stride"], mode, first.get("eps", 1e-5))
+        rc = wave_conv_out_frames(self.desc0, 1)
+        if rc < 0:
+            raise AsrError(-rc, "asr_wave_conv_out_frames")
+        self.W0 = DeviceMatrix.from_numpy(np.asarray(first["weight"], np.float32).reshape(first["kernel"], C))
+        self.b0, self.g0, self.bt0 = col(first.get("bias"), C), col(first.get("gamma"), C), col(first.get("beta"), C)
+        self.convs = []
+        for spec in layers[1:]:
+            w = np.asarray(spec["weight"], np.float32)
+            k, c_in, c_out = w.shape
+            conv = Conv1d(c_in, c_out, k, spec["stride"], weight=w, bias=spec.get("bias"))
+            norm = mode == "layer"
+            self.convs.append((conv, norm, col(spec.get("gamma"), c_out) if norm else None,
+                               col(spec.get("beta"), c_out) if norm else None, float(spec.get("eps", 1e-5))))
+        self.channels = self.convs[-1][0].desc.c_out if self.convs else C
+        self._work, self._keep = None, None
+
+    def out_frames(self, n: int) -> int:
+        n = wave_conv_out_frames(self.desc0, n)
+        for conv, *_ in self.convs:
+            n = conv.out_frames(n) if n > 0 else 0
+        return n
+
+    def forward(self, wave, nsamples=None, stream: int = 0):
+        """wave: a numpy [B, S] float32 array or a DeviceMatrix [B, S]; nsamples
+        None, a sequence of B counts or a DeviceBytes of int32 [B].  Returns
+        (features DeviceMatrix [T*B, C] time-major with zero rows past each
+        utterance's count, T, frames DeviceBytes int32 [B])."""
+        st = stream or 0
+        if isinstance(wave, np.ndarray):
+            wave = DeviceMatrix.from_numpy(np.ascontiguousarray(wave, np.float32))
+        B, S = wave.rows, wave.cols
+        nsamples = _device_lengths_or_none(nsamples)
+        T = wave_conv_out_frames(self.desc0, S)
+        if T <= 0 or self.out_frames(S) <= 0:
+            raise AsrError(ASR_ERR_ARG, "Wav2Vec2FeatureEncoder.forward: no output frame for these samples")
+        need = wave_conv_workspace_bytes(self.desc0, S, B)
+        if need and (self._work is None or self._work.nbytes < need):
+            self._work = DeviceBytes(need)
+        x, ln = DeviceMatrix(T * B, self.desc0.channels), DeviceBytes(4 * B)
+        wave_conv_fwd(wave, self.W0, self.b0, x, B, S, self.desc0, self.g0, self.bt0, self._work, nsamples, ln, st)
+        keep = [wave, nsamples, x, ln]
+        for conv, norm, gamma, beta, eps in self.convs:
+            x, T_out, ln = conv.forward(x, T, B, ln, st)
+            layernorm_gelu_fwd(x, x, T_out, B, conv.desc.c_out, gamma, beta, eps, norm, ln, st)
+            T = T_out
+            keep += [x, ln]
+        self._keep = keep
+        return x, T, ln
+
+
+class Wav2Vec2Encoder:
+    """A wav2vec 2.0 / HuBERT / XLS-R / MMS acoustic model for inference, from
+    raw samples to hidden states or CTC log-probabilities:
+    Wav2Vec2FeatureEncoder -> feature projection (LayerNorm, optional for
+    HuBERT, + Linear) -> x + gelu(positional grouped conv(x)) in one launch ->
+    the encoder LayerNorm before the layers (after them with stable_layer_norm)
+    -> N TransformerEncoderLayer(activation="gelu") -> optional lm_head with
+    log-softmax.  The output is the [T*B, V] emissions CTCDecoder, CTCLMDecoder,
+    ctc_align and CTCPrefixScorer take.  Each utterance's result is what it
+    would be alone (a "group"-norm checkpoint run by transformers on a
+    zero-padded batch takes the padding into its statistics; this class never
+    does).  Input normalisation (Wav2Vec2FeatureExtractor's zero mean and unit
+    variance per utterance) stays with the caller."""
+
+    def __init__(self, features: Wav2Vec2FeatureEncoder, fp_norm: Optional[LayerNorm], fp_w, fp_b,
+                 pos_conv: GroupedConv1d, norm: LayerNorm, layers: Sequence[TransformerEncoderLayer],
+                 stable_layer_norm: bool = False, lm_w=None, lm_b=None):
+        fp_w = np.asarray(fp_w, np.float32)
+        self.C, self.E = fp_w.shape
+        if self.C != features.channels or pos_conv.desc.c_in != self.E or pos_conv.desc.c_out != self.E:
+            raise ValueError("Wav2Vec2Encoder: the projection, the feature encoder and the positional conv disagree")
+        if pos_conv.out_frames(7) != 7:
+            raise ValueError("Wav2Vec2Encoder: the positional conv must keep the frame count (SamePad)")
+        self.features, self.fp_norm, self.pos_conv, self.norm = features, fp_norm, pos_conv, norm
+        self.layers, self.stable = list(layers), bool(stable_layer_norm)
+        self.fp_w = DeviceMatrix.from_numpy(fp_w)
+        self.fp_b = DeviceMatrix.from_numpy(np.asarray(fp_b, np.float32).reshape(self.E, 1))
+        self.lm_w = self.lm_b = None
+        if lm_w is not None:
+            lm_w = np.asarray(lm_w, np.float32)
+            self.lm_w = DeviceMatrix.from_numpy(lm_w)
+            self.lm_b = DeviceMatrix.from_numpy((np.zeros(lm_w.shape[1], np.float32) if lm_b is None
+                                                 else np.asarray(lm_b, np.float32)).reshape(-1, 1))
+        self._keep = None
+
+    @staticmethod
+    def pack_transformers(model):
+        """The host-side packing of from_transformers, no device call: a dict
+        with mode, stable, conv (the feature encoder's layer dicts), fp_norm
+        ((gamma, beta, eps) or None), fp (W [C, E], b), pos (GroupedConv1d
+        .pack_torch's triple), norm (gamma, beta, eps), layers (per layer: w_in
+        [E, 3E], b_in, w_out, b_out, heads, norm1, norm2, w1, b1, w2, b2) and
+        lm ((W [E, V], b) or None).  ValueError for what is not built."""
+        base = model
+        for name in ("wav2vec2", "hubert"):
+            base = getattr(model, name, base)
+        cfg, who = base.config, "Wav2Vec2Encoder.from_transformers"
+        if getattr(cfg, "feat_extract_activation", "gelu") != "gelu" or getattr(cfg, "hidden_act", "gelu") != "gelu":
+            raise ValueError(f"{who}: feat_extract_activation / hidden_act other than 'gelu' are not supported")
+        if getattr(cfg, "add_adapter", False) or getattr(base, "adapter", None) is not None:
+            raise ValueError(f"{who}: adapters are not supported")
+        if getattr(cfg, "adapter_attn_dim", None) is not None:
+            raise ValueError(f"{who}: attention adapters are not supported")
+        if getattr(cfg, "position_embeddings_type", None) is not None:
+            raise ValueError(f"{who}: wav2vec2-conformer position embeddings are not supported")
+        mode = cfg.feat_extract_norm
+        if mode not in ("group", "layer"):
+            raise ValueError(f"{who}: feat_extract_norm {mode!r}")
+        pos = base.encoder.pos_conv_embed
+        if not hasattr(pos, "conv"):
+            raise ValueError(f"{who}: more than one positional conv layer is not supported")
+        host = lambda p: None if p is None else p.detach().cpu().float().numpy()   # noqa: E731
+        norm3 = lambda m: (host(m.weight), host(m.bias), float(m.eps))   # noqa: E731
+        conv = []
+        for i, layer in enumerate(base.feature_extractor.conv_layers):
+            c = layer.conv
+            if c.groups != 1 or c.dilation[0] != 1 or c.padding[0] != 0 or (i == 0 and c.in_channels != 1):
+                raise ValueError(f"{who}: feature-encoder conv {i} is not a plain unpadded Conv1d")
+            w = np.ascontiguousarray(host(c.weight).transpose(2, 1, 0))               # [k][c_in][c_out]
+            spec = dict(weight=w[:, 0, :] if i == 0 else w, bias=host(c.bias), kernel=c.kernel_size[0],
+                        stride=c.stride[0])
+            ln = getattr(layer, "layer_norm", None)
+            if (ln is not None) != (mode == "layer" or i == 0):
+                raise ValueError(f"{who}: feature-encoder layer {i}'s norm does not fit feat_extract_norm {mode!r}")
+            if ln is not None:
+                if mode == "group" and (ln.num_groups != ln.num_channels or ln.num_channels != c.out_channels):
+                    raise ValueError(f"{who}: the GroupNorm is not one group per channel")
+                spec.update(gamma=host(ln.weight), beta=host(ln.bias), eps=float(ln.eps))
+            conv.append(spec)
+        fp = base.feature_projection
+        fp_ln = getattr(fp, "layer_norm", None) if getattr(fp, "feat_proj_layer_norm", True) else None
+        layers = []
+        for layer in base.encoder.layers:
+            at = layer.attention
+            if any(hasattr(at, n) for n in ("rel_attn_embed", "gru_rel_pos_linear", "linear_pos")):
+                raise ValueError(f"{who}: relative position attention (WavLM, wav2vec2-conformer) is not supported")
+            ws, bs = zip(*(_torch_linear(lin) for lin in (at.q_proj, at.k_proj, at.v_proj)))
+            w_out, b_out = _torch_linear(at.out_proj)
+            w1, b1 = _torch_linear(layer.feed_forward.intermediate_dense)
+            w2, b2 = _torch_linear(layer.feed_forward.output_dense)
+            layers.append(dict(w_in=np.ascontiguousarray(np.concatenate(ws, axis=1)), b_in=np.concatenate(bs),
+                               w_out=w_out, b_out=b_out, heads=int(at.num_heads), norm1=norm3(layer.layer_norm),
+                               norm2=norm3(layer.final_layer_norm), w1=w1, b1=b1, w2=w2, b2=b2))
+        lm = getattr(model, "lm_head", None)
+        return dict(mode=mode, stable=bool(cfg.do_stable_layer_norm), conv=conv,
+                    fp_norm=None if fp_ln is None else norm3(fp_ln), fp=_torch_linear(fp.projection),
+                    pos=GroupedConv1d.pack_torch(pos.conv, same_pad=True), norm=norm3(base.encoder.layer_norm),
+                    layers=layers, lm=None if lm is None else _torch_linear(lm))
+
+    @classmethod
+    def from_transformers(cls, model) -> "Wav2Vec2Encoder":
+        """From a transformers Wav2Vec2Model / HubertModel or their ForCTC
+        wrappers (or a module with the same attribute names and config
+        fields)."""
+        p = cls.pack_transformers(model)
+        ln = lambda t: LayerNorm(len(t[0]), t[2], t[0], t[1])   # noqa: E731
+        layers = [TransformerEncoderLayer(
+            MultiheadAttention(q["w_out"].shape[0], q["heads"], q["w_in"], q["b_in"], q["w_out"], q["b_out"]),
+            ln(q["norm1"]), ln(q["norm2"]), q["w1"], q["b1"], q["w2"], q["b2"], norm_first=p["stable"],
+            activation="gelu") for q in p["layers"]]
+        W, b, kw = p["pos"]
+        lm_w, lm_b = p["lm"] if p["lm"] is not None else (None, None)
+        return cls(Wav2Vec2FeatureEncoder(p["conv"], p["mode"]), None if p["fp_norm"] is None else ln(p["fp_norm"]),
+                   *p["fp"], GroupedConv1d(**kw, act="gelu", weight=W, bias=b), ln(p["norm"]), layers, p["stable"],
+                   lm_w, lm_b)
+
+    def forward(self, wave, nsamples=None, stream: int = 0):
+        """wave [B, S] (numpy or DeviceMatrix), nsamples None, B counts or a
+        DeviceBytes.  Returns (DeviceMatrix [T*B, E], or [T*B, V] log-softmax
+        with an lm_head, time-major with zero rows past each utterance's
+        count; out_lengths DeviceBytes int32 [B]); T = rows // B."""
+        st = stream or 0
+        x, T, ln = self.features.forward(wave, nsamples, st)
+        B = x.rows // T
+        keep = [x]
+        if self.fp_norm is not None:
+            x = self.fp_norm.forward(x, T, B, ln, stream=st)
+            keep.append(x)
+        h = DeviceMatrix(T * B, self.E)
+        linear_fwd(x, self.fp_w, self.fp_b, h, EPI_BIAS, st)
+        x, _, _ = self.pos_conv.forward(h, T, B, ln, res=h, stream=st)
+        keep += [h, x]
+        if not self.stable:
+            x = self.norm.forward(x, T, B, ln, out=x, stream=st)
+        for layer in self.layers:
+            x = layer.forward(x, T, B, ln, st)
+            keep.append(x)
+        if self.stable:
+            x = self.norm.forward(x, T, B, ln, out=x, stream=st)
+        if self.lm_w is not None:
+            y = DeviceMatrix(T * B, self.lm_w.cols)
+            linear_fwd(x, self.lm_w, self.lm_b, y, EPI_BIAS_LOGSOFTMAX, st)
+            mask_rows(y, T, B, self.lm_w.cols, ln, st)
+            keep.append(x)
+            x = y
+        self._keep = keep
+        return x, ln
 
 
 # ----------------------------------------------------------------- front end

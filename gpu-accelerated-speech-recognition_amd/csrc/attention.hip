@@ -45,6 +45,8 @@
 // mean of the centred values; sums are a lane's columns ascending, then the
 // butterfly l ^ 32, ^ 16, ... ^ 1 (the tree of asr_lm_score).
 #include "asr_internal.h"
+#include "gelu.h"
+#include "layernorm_row.h"
 
 #include <climits>
 #include <cmath>
@@ -278,13 +280,9 @@ struct LnArgs {
     int T, B, N, M;
 };
 
-__device__ __forceinline__ float ln_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-template <int NU>
+// MODE 0: LayerNorm (asr_layernorm_fwd).  MODE 1: the same statistics, tree and affine, then GELU;
+// MODE 2: GELU alone of the row (asr_layernorm_gelu_fwd with norm = 1 / 0).
+template <int NU, int MODE>
 __global__ __launch_bounds__(256) void layernorm_kernel(const LnArgs p) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + w;
@@ -301,41 +299,46 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LnArgs p) {
     const float* xr = p.x + (long)row * p.ldx;
     const float* rr = p.res ? p.res + (long)row * p.ldr : nullptr;
     float v[NU];
-    float sum = 0.f;
 #pragma unroll
     for (int u = 0; u < NU; u++) {
         const int col = lane + 64 * u;
         v[u] = 0.f;
         if (col < p.N) v[u] = rr ? xr[col] + rr[col] : xr[col];
-        sum += v[u];
     }
-    // mean = mean0 + corr: the residual mean of v - mean0 takes out mean0's own rounding error, which is
-    // relative to |v| (a row at 1000 +- 1 would otherwise be centred 5e-5 off)
-    const float mean0 = ln_wave_sum(sum) / (float)p.N;
-    float rs = 0.f;
+    if (MODE == 2) {
 #pragma unroll
-    for (int u = 0; u < NU; u++) {
-        v[u] = (lane + 64 * u < p.N) ? v[u] - mean0 : 0.f;
-        rs += v[u];
+        for (int u = 0; u < NU; u++)
+            if (lane + 64 * u < p.N) orow[lane + 64 * u] = gelu_f32(v[u]);
+        return;
     }
-    const float corr = ln_wave_sum(rs) / (float)p.N;
-    float sq = 0.f;
-#pragma unroll
-    for (int u = 0; u < NU; u++) {
-        v[u] = (lane + 64 * u < p.N) ? v[u] - corr : 0.f;
-        sq += v[u] * v[u];
-    }
-    const float var = ln_wave_sum(sq) / (float)p.N;
-    const float rstd = 1.f / sqrtf(var + p.eps);
+    const float rstd = ln_row_centre<NU>(v, lane, p.N, p.eps);
 #pragma unroll
     for (int u = 0; u < NU; u++) {
         const int col = lane + 64 * u;
         if (col < p.N) {
             const float gm = p.gamma ? p.gamma[col] : 1.f;
             const float bt = p.beta ? p.beta[col] : 0.f;
-            orow[col] = (v[u] * rstd) * gm + bt;
+            const float y = (v[u] * rstd) * gm + bt;
+            orow[col] = MODE == 1 ? gelu_f32(y) : y;
         }
     }
+}
+
+// One launch of layernorm_kernel<NU, MODE> with NU the power of two >= ceil(N / 64).
+template <int MODE>
+static int layernorm_launch(const LnArgs& p, asr_stream_t s) {
+    const dim3 grid((unsigned)((p.M + 3) / 4));
+    hipStream_t st = asr_stream(s);
+    const int nu = (p.N + 63) / 64;
+    if (nu <= 1) hipLaunchKernelGGL((layernorm_kernel<1, MODE>), grid, dim3(256), 0, st, p);
+    else if (nu <= 2) hipLaunchKernelGGL((layernorm_kernel<2, MODE>), grid, dim3(256), 0, st, p);
+    else if (nu <= 4) hipLaunchKernelGGL((layernorm_kernel<4, MODE>), grid, dim3(256), 0, st, p);
+    else if (nu <= 8) hipLaunchKernelGGL((layernorm_kernel<8, MODE>), grid, dim3(256), 0, st, p);
+    else if (nu <= 16) hipLaunchKernelGGL((layernorm_kernel<16, MODE>), grid, dim3(256), 0, st, p);
+    else if (nu <= 32) hipLaunchKernelGGL((layernorm_kernel<32, MODE>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((layernorm_kernel<64, MODE>), grid, dim3(256), 0, st, p);
+    ASR_LAUNCH_TRY();
+    return ASR_OK;
 }
 
 // Zero columns [0, N) of the rows past their utterance's length; one wave per row.
@@ -412,18 +415,24 @@ int asr_layernorm_fwd(const float* d_x, long ldx, const float* d_res, long ldr, 
     p.x = d_x; p.res = d_res; p.gamma = d_gamma; p.beta = d_beta; p.out = d_out;
     p.ldx = ldx; p.ldr = ldr; p.ldo = ldo; p.lengths = d_lengths; p.eps = eps;
     p.T = T; p.B = B; p.N = N; p.M = T * B;
-    const dim3 grid((unsigned)((p.M + 3) / 4));
-    hipStream_t st = asr_stream(s);
-    const int nu = (N + 63) / 64;
-    if (nu <= 1) hipLaunchKernelGGL(asr::layernorm_kernel<1>, grid, dim3(256), 0, st, p);
-    else if (nu <= 2) hipLaunchKernelGGL(asr::layernorm_kernel<2>, grid, dim3(256), 0, st, p);
-    else if (nu <= 4) hipLaunchKernelGGL(asr::layernorm_kernel<4>, grid, dim3(256), 0, st, p);
-    else if (nu <= 8) hipLaunchKernelGGL(asr::layernorm_kernel<8>, grid, dim3(256), 0, st, p);
-    else if (nu <= 16) hipLaunchKernelGGL(asr::layernorm_kernel<16>, grid, dim3(256), 0, st, p);
-    else if (nu <= 32) hipLaunchKernelGGL(asr::layernorm_kernel<32>, grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(asr::layernorm_kernel<64>, grid, dim3(256), 0, st, p);
-    ASR_LAUNCH_TRY();
-    return ASR_OK;
+    return asr::layernorm_launch<0>(p, s);
+}
+
+int asr_layernorm_gelu_fwd(const float* d_x, long ldx, const float* d_gamma, const float* d_beta, float eps, int norm,
+                           const int32_t* d_lengths, float* d_out, long ldo, int T, int B, int N, asr_stream_t s) {
+    if (!d_x || !d_out) return ASR_ERR_ARG;
+    if (T <= 0 || B <= 0 || N <= 0) return ASR_ERR_ARG;
+    if (ldx < N || ldo < N) return ASR_ERR_ARG;
+    if (norm != 0 && norm != 1) return ASR_ERR_ARG;
+    if (norm && (!std::isfinite(eps) || eps < 0.f)) return ASR_ERR_ARG;
+    if (N > 4096) return ASR_ERR_UNSUPPORTED;
+    if ((long)T * B > INT_MAX) return ASR_ERR_UNSUPPORTED;
+
+    asr::LnArgs p{};
+    p.x = d_x; p.gamma = d_gamma; p.beta = d_beta; p.out = d_out;
+    p.ldx = ldx; p.ldo = ldo; p.lengths = d_lengths; p.eps = eps;
+    p.T = T; p.B = B; p.N = N; p.M = T * B;
+    return norm ? asr::layernorm_launch<1>(p, s) : asr::layernorm_launch<2>(p, s);
 }
 
 int asr_mask_rows(float* d_x, long ldx, const int32_t* d_lengths, int T, int B, int N, asr_stream_t s) {

@@ -1,6 +1,7 @@
 // Host/device interface of the dense fp32 kernels (dense.hip).
 #pragma once
 #include "asr_internal.h"
+#include "gelu.h"
 
 namespace asr {
 
@@ -25,11 +26,8 @@ constexpr bool epi_has_bias(int epi) {
 // quotient is -0; v -> +inf: the quotient is v.
 __device__ __forceinline__ float silu_f32(float v) { return v / (1.f + __expf(-v)); }
 
-// Exact GELU of a pre-activation, v/2 * (1 + erf(v / sqrt 2)), written with
-// 1 + erf(x) = erfc(-x): one expression for both signs and no cancellation in
-// the negative tail (1 + erf(x) loses every digit below x = -3.5).  v -> -inf:
-// erfc -> 0 and the product is -0; v -> +inf: erfc -> 2 and the product is v.
-__device__ __forceinline__ float gelu_f32(float v) { return (0.5f * v) * erfcf(-0.70710678118654752f * v); }
+// gelu_f32, the exact (erf) GELU of a pre-activation, is in gelu.h: the convolution
+// and LayerNorm kernels share it with the GEMM epilogues.
 
 struct GemmArgs {
     const float* A;   // A(m,k) = A[m*sam + k*sak]

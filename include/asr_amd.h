@@ -390,6 +390,99 @@ int asr_conv1d_fwd(const asr_conv1d_desc* d, const float* d_x, long ldx, const i
                    const float* d_W, const float* d_b, float* d_out, long ldo,
                    int32_t* d_out_lengths, int T, int B, asr_stream_t s);
 
+/* Grouped convolution over time with 1 < groups < c_in, stride 1, dilation 1,
+ * bias, optional GELU and an optional fused residual — the positional
+ * convolution of wav2vec 2.0 / HuBERT / XLS-R / MMS encoders
+ * (Conv1d(E, E, 128, padding = 64, groups = 16), SamePad, GELU, added to its
+ * input); no reference member.  The cases asr_conv1d_fwd refuses.
+ *   out(t', b, co) = res(t', b, co) + act((sum_{j<k} sum_{ci < c_in/groups}
+ *                        xh(t' - pl + j, b, g c_in/groups + ci) W[j][ci][co]) + b[co]),   g = co / (c_out/groups)
+ * d_x, d_out, d_W, d_b, d_lengths and d_out_lengths as in asr_conv1d_fwd
+ * (d_W [k][c_in / groups][c_out]); T_out = out_frames(T) = T + pl + pr - k + 1
+ * (0 if that is negative or n <= 0).  torch's padding = k/2 followed by HF's
+ * SamePad (drop the last frame when k is even) is pad_left = k/2, pad_right =
+ * k/2 - 1: T_out = T.  xh is x inside the utterance and a selected zero
+ * outside it (padding may hold NaN); rows t' >= out_frames(len[b]) are zeros.
+ * d_res (NULL: none; row stride ldr >= c_out) is added after the activation,
+ * to rows inside the count only; it may be d_x (c_in == c_out) or d_out.  act:
+ * ASR_GCONV_ACT_NONE or _GELU, the exact GELU of ASR_EPI_BIAS_GELU.  The
+ * order is fixed: taps ascending, in a tap the group's channels ascending in
+ * groups of 4 with a zero-filled tail, from a zero accumulator, on fp32 MFMA;
+ * then the bias, the activation, the residual.  A row's bits depend only on
+ * its receptive field, the weights and the descriptor: never on T, B, the
+ * row's position, other utterances, the strides or alignment.
+ * One workgroup stages the (128 + k - 1) x c_in/groups window of x in LDS once
+ * and streams W through it.  One launch, asynchronous
+ * on s, no allocation, no workspace; d_out must not be d_x.  Checks, in this
+ * order, all before any HIP call — ASR_ERR_ARG: a NULL descriptor, d_x, d_W
+ * or d_out; non-positive c_in, c_out, kernel or groups; negative padding;
+ * c_in or c_out not a multiple of groups; an unknown act; non-positive T or
+ * B; ldx < c_in, ldo < c_out, or ldr < c_out with a d_res; d_out == d_x;
+ * T_out = 0.  ASR_ERR_UNSUPPORTED: groups == 1 or groups >= c_in;
+ * c_in / groups or c_out / groups > 128; kernel > 128; groups > 65535;
+ * T + pad_left + pad_right > INT_MAX - 4096; T*B or T_out*B > INT_MAX;
+ * B > 65535.  asr_grouped_conv1d_out_frames is host only: out_frames(n), or
+ * minus the status the descriptor is refused with. */
+enum { ASR_GCONV_ACT_NONE = 0, ASR_GCONV_ACT_GELU = 1 };
+typedef struct asr_grouped_conv1d_desc {
+    int c_in, c_out;          /* multiples of groups; c_in / groups and c_out / groups <= 128 */
+    int kernel;               /* k taps, 1 .. 128 */
+    int pad_left, pad_right;  /* >= 0 */
+    int groups;               /* 1 < groups < c_in */
+    int act;                  /* ASR_GCONV_ACT_* */
+} asr_grouped_conv1d_desc;
+int asr_grouped_conv1d_out_frames(const asr_grouped_conv1d_desc* d, int n_frames);
+int asr_grouped_conv1d_fwd(const asr_grouped_conv1d_desc* d, const float* d_x, long ldx, const int32_t* d_lengths,
+                           const float* d_W, const float* d_b, const float* d_res, long ldr, float* d_out, long ldo,
+                           int32_t* d_out_lengths, int T, int B, asr_stream_t s);
+
+/* The first layer of a wav2vec 2.0 / HuBERT feature encoder: Conv1d(1, C, k,
+ * stride s) over raw samples, a normalisation and GELU in one entry point; no
+ * reference member.  d_wave [B][ldw] batch-major and d_nsamples (device int32
+ * [B], clamped to [0, S], NULL = all S) are asr_fbank_fwd's inputs, so one
+ * upload serves both front ends; samples at or past the count are selected as
+ * zero (they may hold NaN).  out_frames(n) = 0 for n < k, else (n - k) / s + 1;
+ * T1 = out_frames(S).  d_W [k][C], d_b [C] or NULL; d_out time-major, row
+ * t*B + b receives C floats (stride ldo >= C); rows t >= out_frames(n_b) are
+ * zeros and d_out_lengths (may be NULL) receives out_frames(n_b).
+ *   v(t, b, c) = (sum_{j<k} wave(b, t s + j) W[j][c]) + b[c]     one fmaf chain, taps ascending
+ *   ASR_WAVE_NORM_NONE:     out = gelu(v)
+ *   ASR_WAVE_NORM_CHANNEL:  out = gelu(LayerNorm over the C channels of the frame (asr_layernorm_fwd's
+ *                           statistics and tree) * gamma + beta)     (feat_extract_norm = "layer")
+ *   ASR_WAVE_NORM_TIME:     out = gelu((((v - mean_hi) - mean_lo) * rstd) * gamma + beta), mean and biased
+ *                           variance of channel c over the utterance's OWN out_frames(n_b) frames, rstd =
+ *                           1 / sqrt(var + eps): torch.nn.GroupNorm(C, C) of the utterance alone
+ *                           (feat_extract_norm = "group"; the HF model on a zero-padded batch takes the
+ *                           padding into these statistics, this entry point never does).
+ * d_gamma / d_beta [C] or NULL (1 / 0).  GELU is ASR_EPI_BIAS_GELU's.  NONE
+ * and CHANNEL are one launch.  TIME is three, and never stores v: a statistics
+ * pass recomputes the convolution into per (utterance, 256-frame chunk,
+ * channel) fp64 moments centred per chunk, a second merges the chunks in
+ * ascending order (Chan's update, fp64) into (mean_hi, mean_lo, rstd), the
+ * third recomputes, normalises and stores.  The chunk grid follows the frame
+ * index alone: the statistics, like every row's bits, never depend on B, S,
+ * ldw, ldo or other utterances.  d_work: asr_wave_conv_workspace_bytes(d, S, B)
+ * bytes of the caller's, 8-byte aligned (TIME only; 0 and ignored otherwise).
+ * Asynchronous on s, no allocation.  Checks, in this order, before any HIP
+ * call — ASR_ERR_ARG: a NULL descriptor, d_wave, d_W or d_out; non-positive
+ * channels, kernel or stride; an unknown norm; eps not finite or < 0 with a
+ * norm; non-positive B or S; ldw < S; ldo < C; TIME without d_work; T1 = 0.
+ * ASR_ERR_UNSUPPORTED: kernel > 32, stride > 16, C > 4096; T1*B > INT_MAX.
+ * Input normalisation (zero mean, unit variance per utterance) is the
+ * caller's. */
+enum { ASR_WAVE_NORM_NONE = 0, ASR_WAVE_NORM_CHANNEL = 1, ASR_WAVE_NORM_TIME = 2 };
+typedef struct asr_wave_conv_desc {
+    int channels;             /* C, 1 .. 4096 */
+    int kernel, stride;       /* k 1 .. 32, s 1 .. 16 */
+    int norm;                 /* ASR_WAVE_NORM_* */
+    float eps;                /* of the norm, finite and >= 0 */
+} asr_wave_conv_desc;
+int asr_wave_conv_out_frames(const asr_wave_conv_desc* d, int n_samples);
+size_t asr_wave_conv_workspace_bytes(const asr_wave_conv_desc* d, int S, int B);
+int asr_wave_conv_fwd(const asr_wave_conv_desc* d, const float* d_wave, long ldw, const int32_t* d_nsamples,
+                      const float* d_W, const float* d_b, const float* d_gamma, const float* d_beta, void* d_work,
+                      float* d_out, long ldo, int32_t* d_out_lengths, int B, int S, asr_stream_t s);
+
 /* One convolution layer over the (time, frequency) plane — torch.nn.Conv2d
  * semantics on an input [B][C][T][F], in this library's time-major layout,
  * with bias and activation fused: the layers of the Conv2dSubsampling module
@@ -968,6 +1061,19 @@ int asr_ctc_prefix_advance(const asr_ctc_prefix_desc* d, const float* d_emis, lo
 int asr_layernorm_fwd(const float* d_x, long ldx, const float* d_res, long ldr, const float* d_gamma,
                       const float* d_beta, float eps, const int32_t* d_lengths, float* d_out, long ldo,
                       int T, int B, int N, asr_stream_t s);
+
+/* asr_layernorm_fwd without a residual followed by the exact GELU of
+ * ASR_EPI_BIAS_GELU in the same kernel (the same statistics, tree and affine:
+ * the pre-GELU value has asr_layernorm_fwd's bits), or with norm = 0 GELU
+ * alone of each row (d_gamma, d_beta and eps are then ignored): layers 1 .. 6
+ * of a wav2vec 2.0 / HuBERT feature encoder after asr_conv1d_fwd(...,
+ * ASR_CONV_ACT_NONE).  d_out may be d_x; rows t >= len[b] are zeros.  One
+ * launch.  Checks, in this order — ASR_ERR_ARG: NULL d_x or d_out;
+ * non-positive T, B or N; a stride < N; norm other than 0 or 1; with norm = 1
+ * an eps not finite or < 0.  ASR_ERR_UNSUPPORTED: N > 4096; T*B > INT_MAX. */
+int asr_layernorm_gelu_fwd(const float* d_x, long ldx, const float* d_gamma, const float* d_beta, float eps,
+                           int norm, const int32_t* d_lengths, float* d_out, long ldo, int T, int B, int N,
+                           asr_stream_t s);
 
 /* Zero columns [0, N) of the rows t >= len[b] of a time-major [T*B, >= N]
  * buffer in place (row stride ldx; d_lengths device int32 [B], clamped to
