@@ -58,6 +58,13 @@ include/asr_amd.h — it contains no arithmetic of its own:
                                           asr_csgu_fwd) merged by a depthwise
                                           convolution over both
                                           (asr_merge_dwconv_fwd); no reference member
+    ZipformerLayer.from_torch(layer, chunk, left, right).forward / Zipformer(layers, pos_dim).forward
+                                          a Zipformer2 encoder layer: one set of
+                                          attention scores for three value tensors
+                                          (asr_attention_zip_fwd), Swoosh epilogues,
+                                          BiasNorm and the per-channel bypass
+                                          (asr_biasnorm_fwd, asr_bypass_fwd); no
+                                          reference member
     TransformerDecoder.from_torch(embedding, decoder, output).score(hyps, utt, memory, T, B)
     attention_rescore(nbest, decoder, memory, T, B) / CTCDecoder.attention_rescore(...)
                                           attention-decoder rescoring of an n-best:
@@ -181,6 +188,7 @@ EXPORTS = [
     "asr_wave_conv_workspace_bytes", "asr_wave_conv_fwd", "asr_layernorm_gelu_fwd",
     "asr_conv2d_out_frames", "asr_conv2d_out_feats", "asr_conv2d_fwd",
     "asr_attention_fwd", "asr_attention_rel_fwd", "asr_layernorm_fwd", "asr_mask_rows",
+    "asr_attention_zip_fwd", "asr_biasnorm_fwd", "asr_bypass_fwd",
     "asr_cross_attention_fwd", "asr_token_score",
     "asr_decode_attention_fwd", "asr_embed_fwd", "asr_attn_beam_step", "asr_attn_beam_step_host",
     "asr_ctc_prefix_begin", "asr_ctc_prefix_score", "asr_ctc_prefix_advance",
@@ -318,6 +326,11 @@ def lib() -> ctypes.CDLL:
                               ctypes.c_long, _i, _i, _i, _i, _i, _vp],
         "asr_attention_rel_fwd": [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, ctypes.c_long,
                                   _i, _i, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _i, _i, _i, _vp],
+        "asr_attention_zip_fwd": [_vp] + [_vp, ctypes.c_long] * 7 + [_i, _i, _vp, _vp, ctypes.c_long, _i, _i, _i, _i, _i,
+                                                                     _vp],
+        "asr_biasnorm_fwd": [_vp, ctypes.c_long, _vp, _f, _vp, ctypes.c_long, _vp, _vp, _vp, ctypes.c_long, _i, _i, _i,
+                             _vp],
+        "asr_bypass_fwd": [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, ctypes.c_long, _i, _i, _i, _vp],
         "asr_layernorm_fwd": [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _f, _vp, _vp, ctypes.c_long,
                               _i, _i, _i, _vp],
         "asr_mask_rows": [_vp, ctypes.c_long, _vp, _i, _i, _i, _vp],
@@ -3672,6 +3685,247 @@ class EBranchformer:
         lengths = _device_lengths_or_none(lengths)
         for layer in self.layers:
             x = layer.forward(x, T, B, lengths, stream=stream)
+        self._keep = lengths
+        return x
+
+
+# ------------------------------------------------------------------ Zipformer
+EPI_BIAS_SWOOSHL, EPI_BIAS_SWOOSHR = 7, 8
+GLU_ACT_SWOOSHR = 4   # 3 is not assigned
+GLU_ACTS["swooshr"] = GLU_ACT_SWOOSHR
+
+
+class ZattnDesc(ctypes.Structure):
+    """asr_zattn_desc (include/asr_amd.h)."""
+    _fields_ = [("heads", _i), ("query_dim", _i), ("pos_dim", _i), ("value_heads", _i), ("value_dim", _i),
+                ("score_head", _i), ("scale", _f), ("chunk", _i), ("left", _i), ("right", _i), ("gate", _i)]
+
+
+def zattn_desc(heads: int, query_dim: int, pos_dim: int, value_dim: int, value_heads: Optional[int] = None,
+               score_head: int = 0, scale: float = 0.0, chunk: int = 1, left: int = -1, right: int = -1,
+               gate: bool = False) -> ZattnDesc:
+    """A ZattnDesc from keywords: value_heads None = heads (value head g uses
+    score head g), 1 = one wide value head on score head score_head; scale 0 =
+    1/sqrt(query_dim); the window as attn_desc's."""
+    return ZattnDesc(heads, query_dim, pos_dim, heads if value_heads is None else value_heads, value_dim, score_head,
+                     scale, chunk, left, right, int(gate))
+
+
+def attention_zip_fwd(q, k, v, out, Tq: int, Tk: int, B: int, desc: ZattnDesc, pz=None, pos=None, pos_zero: int = 0,
+                      sg=None, y=None, lengths: Optional[DeviceBytes] = None, q_pos0: int = 0, k_pos0: int = 0,
+                      stream: int = 0):
+    """Shared-score attention (asr_attention_zip_fwd): q, k [.., >= H*dq], pz
+    [Tq*B, >= H*dp] and v / sg (Tk frames), y / out (Tq frames) [.., >= G*dv],
+    anything with .ptr and .cols (the row stride), so they may be ColumnViews of
+    projection buffers; pos the projected table [n_pos, >= H*dp] whose row
+    pos_zero - delta holds distance delta = query frame - key frame.  pz / pos
+    only with desc.pos_dim > 0, sg / y only with desc.gate."""
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    ld = lambda m: int(m.cols) if m is not None else 0   # noqa: E731
+    check(lib().asr_attention_zip_fwd(ctypes.byref(desc), q.ptr, ld(q), k.ptr, ld(k), opt(pz), ld(pz), v.ptr, ld(v),
+                                      opt(sg), ld(sg), opt(y), ld(y), opt(pos), ld(pos),
+                                      int(pos.rows) if pos is not None else 0, int(pos_zero), opt(lengths), out.ptr,
+                                      ld(out), Tq, q_pos0, Tk, k_pos0, B, stream), "asr_attention_zip_fwd")
+    return out
+
+
+def biasnorm_fwd(x, bias, log_scale: float, out, T: int, B: int, N: int, x0=None, bypass=None,
+                 lengths: Optional[DeviceBytes] = None, stream: int = 0):
+    """BiasNorm of the first N columns of each row (asr_biasnorm_fwd): out = x *
+    exp(log_scale) / sqrt(mean((x - bias)^2)); with x0 and bypass [N] the
+    layer's last bypass is fused, out = x0 + (out - x0) * bypass.  Rows past
+    lengths become zeros; out may be x or x0."""
+    opt = lambda m: m.ptr if m is not None else None   # noqa: E731
+    check(lib().asr_biasnorm_fwd(x.ptr, x.cols, bias.ptr, float(log_scale), opt(x0), x0.cols if x0 is not None else 0,
+                                 opt(bypass), opt(lengths), out.ptr, out.cols, T, B, N, stream), "asr_biasnorm_fwd")
+    return out
+
+
+def bypass_fwd(x, x0, scale, out, T: int, B: int, N: int, lengths: Optional[DeviceBytes] = None, stream: int = 0):
+    """out = x0 + (x - x0) * scale[c] (asr_bypass_fwd); rows past lengths become
+    zeros; out may be x or x0."""
+    check(lib().asr_bypass_fwd(x.ptr, x.cols, x0.ptr, x0.cols, scale.ptr, lengths.ptr if lengths is not None else None,
+                               out.ptr, out.cols, T, B, N, stream), "asr_bypass_fwd")
+    return out
+
+
+def compact_rel_positional_encoding(T: int, pos_dim: int) -> np.ndarray:
+    """icefall's CompactRelPositionalEncoding table [2T - 1, pos_dim] float32,
+    built in float64 on the host: row n is x = n - (T - 1) = key frame - query
+    frame, log-compressed (c = sqrt(pos_dim): c sign(x) (log(|x| + c) - log c)),
+    warped by atan(. / (pos_dim / 2 pi)), cos(f a) at column 2(f - 1) and
+    sin(f a) at column 2(f - 1) + 1 for f = 1 .. pos_dim / 2, the last column
+    overwritten with 1 (the bias of linear_pos).  Row n holds distance delta =
+    query - key = T - 1 - n: asr_attention_zip_fwd's order with pos_zero = T - 1."""
+    if T <= 0 or pos_dim <= 0 or pos_dim % 2:
+        raise ValueError(f"compact_rel_positional_encoding: T {T}, pos_dim {pos_dim}")
+    x = np.arange(-(T - 1), T, dtype=np.float64)[:, None]
+    c = float(pos_dim) ** 0.5
+    a = np.arctan(c * np.sign(x) * (np.log(np.abs(x) + c) - np.log(c)) / (pos_dim / (2.0 * np.pi)))
+    f = 1.0 + np.arange(pos_dim // 2, dtype=np.float64)[None, :]
+    pe = np.empty((2 * T - 1, pos_dim), np.float64)
+    pe[:, 0::2], pe[:, 1::2] = np.cos(a * f), np.sin(a * f)
+    pe[:, -1] = 1.0
+    return pe.astype(np.float32)
+
+
+class ZipformerLayer:
+    """One Zipformer2 encoder layer (icefall's zipformer.py) for inference,
+    time-major.  In order, every step but the first and the bypasses a residual:
+    the scores' q, k, pz from the layer input; feed-forward 1; the non-linear
+    attention (score head 0 on one wide gated value head); self-attention 1;
+    convolution module 1; feed-forward 2; the mid bypass against the layer
+    input; self-attention 2; convolution module 2; feed-forward 3; BiasNorm and
+    the last bypass in one launch.  The three attentions share q, k and pz and
+    each recomputes the probabilities (asr_attention_zip_fwd); the feed-forwards
+    are asr_linear_fwd with EPI_BIAS_SWOOSHL, the convolution modules
+    asr_glu_dwconv_fwd with GLU_ACT_SWOOSHR.  Balancers, whiteners and dropout
+    are identities in eval mode.  No arithmetic here.
+    The attribute names and the splits of in_proj (q | k | p) and of the
+    non-linear attention's in_proj (s | x | y) follow icefall's source as
+    remembered: no icefall checkpoint was loaded (tests/zipformer_reference.py
+    has a stand-in with those names)."""
+
+    def __init__(self, p: dict, heads: int, query_dim: int, pos_dim: int, chunk: int = 1, left: int = -1,
+                 right: int = -1):
+        f32 = lambda a: np.ascontiguousarray(np.asarray(a, np.float32))   # noqa: E731
+        E = f32(p["attn.w_in"]).shape[0]
+        self.E, self.H, self.dq, self.dp = E, heads, query_dim, pos_dim
+        self.hid = f32(p["nla.w_out"]).shape[0]
+        self.dv = f32(p["sa1.w_out"]).shape[0] // heads
+        self.window = (chunk, left, right)
+        assert f32(p["attn.w_in"]).shape == (E, heads * (2 * query_dim + pos_dim)), f32(p["attn.w_in"]).shape
+        self.log_scale = float(p["norm.log_scale"])
+        self.w = {}
+        for key, a in p.items():
+            if key != "norm.log_scale" and a is not None and not key.endswith(".kernel"):
+                a = f32(a)
+                self.w[key] = DeviceMatrix.from_numpy(a if a.ndim == 2 else a.reshape(-1, 1))
+        self.conv_desc = [glu_dwconv_desc(E, int(p[f"conv{i}.wd"].shape[0]), act="swooshr") for i in (1, 2)]
+        self._scratch, self._keep = _Scratch(), None
+
+    @staticmethod
+    def pack_torch(layer) -> dict:
+        """Every float32 array of a layer with icefall's attribute names, in
+        this library's [in][out] / [tap][channel] layouts.  No device call."""
+        host = lambda t: t.detach().cpu().float().numpy()   # noqa: E731
+        p = {}
+
+        def lin(key, m, suffix=("w_in", "b_in")):
+            p[f"{key}.{suffix[0]}"], p[f"{key}.{suffix[1]}"] = _torch_linear(m)
+
+        saw = layer.self_attn_weights
+        lin("attn", saw.in_proj)
+        p["attn.w_pos"] = _torch_linear(saw.linear_pos)[0]
+        for i, ff in enumerate((layer.feed_forward1, layer.feed_forward2, layer.feed_forward3), 1):
+            lin(f"ff{i}", ff.in_proj)
+            lin(f"ff{i}", ff.out_proj, ("w_out", "b_out"))
+        for key, m in (("nla", layer.nonlin_attention), ("sa1", layer.self_attn1), ("sa2", layer.self_attn2)):
+            lin(key, m.in_proj)
+            lin(key, m.out_proj, ("w_out", "b_out"))
+        for i, cm in enumerate((layer.conv_module1, layer.conv_module2), 1):
+            lin(f"conv{i}", cm.in_proj)
+            lin(f"conv{i}", cm.out_proj, ("w_out", "b_out"))
+            dw = cm.depthwise_conv
+            E, k = dw.in_channels, dw.kernel_size[0]
+            if dw.groups != E or dw.stride[0] != 1 or dw.dilation[0] != 1 or 2 * dw.padding[0] != k - 1:
+                raise ValueError("ZipformerLayer.pack_torch: the depthwise convolution needs groups == channels, stride "
+                                 "1, dilation 1 and 'same' padding (the chunk-causal convolution is not built)")
+            p[f"conv{i}.wd"] = np.ascontiguousarray(host(dw.weight)[:, 0, :].T)
+            p[f"conv{i}.bd"] = host(dw.bias) if dw.bias is not None else np.zeros(E, np.float32)
+        p["bypass_mid.scale"], p["bypass.scale"] = host(layer.bypass_mid.bypass_scale), host(layer.bypass.bypass_scale)
+        p["norm.bias"], p["norm.log_scale"] = host(layer.norm.bias), float(layer.norm.log_scale.detach())
+        return p
+
+    @classmethod
+    def from_torch(cls, layer, chunk: int = 1, left: int = -1, right: int = -1) -> "ZipformerLayer":
+        saw = layer.self_attn_weights
+        return cls(cls.pack_torch(layer), int(saw.num_heads), int(saw.query_head_dim), int(saw.pos_head_dim), chunk,
+                   left, right)
+
+    def _residual(self, h, key: str, a, M: int, st: int):
+        """h += a . w_out + b_out of module key."""
+        t = self._scratch.get("t", M, self.E)
+        linear_fwd(a, self.w[key + ".w_out"], self.w[key + ".b_out"], t, EPI_BIAS, st)
+        check(lib().asr_matadd(h.ptr, t.ptr, h.ptr, M, self.E, 1.0, st), "asr_matadd")
+
+    def forward(self, x, T: int, B: int, pos: DeviceMatrix, pos_zero: int, lengths=None, stream: int = 0) -> DeviceMatrix:
+        """x time-major [T*B, E]; pos the position table on the device [n_pos,
+        pos_emb_dim] (compact_rel_positional_encoding: pos_zero = T - 1), which
+        the layer projects with its own linear_pos.  Returns a new DeviceMatrix
+        [T*B, E] with zero rows past the lengths."""
+        E, M, H, st, sc, w = self.E, T * B, self.H, stream or 0, self._scratch, self.w
+        _need_matrix("ZipformerLayer.forward: x", x, M, E)
+        lengths = _device_lengths_or_none(lengths)
+        chunk, left, right = self.window
+        qkp = linear_fwd(x, w["attn.w_in"], w["attn.b_in"], sc.get("qkp", M, H * (2 * self.dq + self.dp)), EPI_BIAS, st)
+        pp = linear_fwd(pos, w["attn.w_pos"], None, sc.get("pp", pos.rows, H * self.dp), EPI_NONE, st)
+        q, k, pz = qkp, ColumnView(qkp, H * self.dq), ColumnView(qkp, 2 * H * self.dq)
+
+        def ff(i, h):
+            F = w[f"ff{i}.w_in"].cols
+            u = linear_fwd(h, w[f"ff{i}.w_in"], w[f"ff{i}.b_in"], sc.get(f"ff{i}", M, F), EPI_BIAS_SWOOSHL, st)
+            self._residual(h, f"ff{i}", u, M, st)
+
+        def self_attn(i, h):
+            v = linear_fwd(h, w[f"sa{i}.w_in"], w[f"sa{i}.b_in"], sc.get("v", M, H * self.dv), EPI_BIAS, st)
+            d = zattn_desc(H, self.dq, self.dp, self.dv, scale=1.0, chunk=chunk, left=left, right=right)
+            a = attention_zip_fwd(q, k, v, sc.get("a", M, H * self.dv), T, T, B, d, pz=pz, pos=pp, pos_zero=pos_zero,
+                                  lengths=lengths, stream=st)
+            self._residual(h, f"sa{i}", a, M, st)
+
+        def conv(i, h):
+            u = linear_fwd(h, w[f"conv{i}.w_in"], w[f"conv{i}.b_in"], sc.get("cu", M, 2 * E), EPI_BIAS, st)
+            c = glu_dwconv_fwd(u, w[f"conv{i}.wd"], w[f"conv{i}.bd"], sc.get("cc", M, E), T, B, self.conv_desc[i - 1],
+                               lengths=lengths, stream=st)
+            self._residual(h, f"conv{i}", c, M, st)
+
+        h = sc.get("h", M, E)
+        check(lib().asr_memcpy_d2d(h.ptr, x.ptr, 4 * M * E, st), "asr_memcpy_d2d")
+        ff(1, h)
+        hid = self.hid                                       # the non-linear attention: s | x | y
+        u = linear_fwd(h, w["nla.w_in"], w["nla.b_in"], sc.get("nu", M, 3 * hid), EPI_BIAS, st)
+        d = zattn_desc(H, self.dq, self.dp, hid, value_heads=1, score_head=0, scale=1.0, chunk=chunk, left=left,
+                       right=right, gate=True)
+        a = attention_zip_fwd(q, k, ColumnView(u, hid), sc.get("na", M, hid), T, T, B, d, pz=pz, pos=pp,
+                              pos_zero=pos_zero, sg=u, y=ColumnView(u, 2 * hid), lengths=lengths, stream=st)
+        self._residual(h, "nla", a, M, st)
+        self_attn(1, h)
+        conv(1, h)
+        ff(2, h)
+        bypass_fwd(h, x, w["bypass_mid.scale"], h, T, B, E, lengths, st)
+        self_attn(2, h)
+        conv(2, h)
+        ff(3, h)
+        out = DeviceMatrix(M, E)
+        biasnorm_fwd(h, w["norm.bias"], self.log_scale, out, T, B, E, x0=x, bypass=w["bypass.scale"], lengths=lengths,
+                     stream=st)
+        self._keep = lengths
+        return out
+
+
+class Zipformer:
+    """A stack of ZipformerLayers at one resolution, run in turn with the same
+    lengths and one position table (each layer projects it with its own
+    linear_pos).  Not built: the multi-resolution wrapper (SimpleDownsample /
+    Upsample / out_combiner), the ConvNeXt encoder_embed, the chunk-causal
+    convolution and cached left context for streaming."""
+
+    def __init__(self, layers: Sequence[ZipformerLayer], pos_dim: int):
+        self.layers, self.pos_dim = list(layers), int(pos_dim)
+        assert self.layers and all(l.E == self.layers[0].E for l in self.layers)
+        self.E, self._pos = self.layers[0].E, None
+
+    @classmethod
+    def from_torch(cls, layers, pos_dim: int, chunk: int = 1, left: int = -1, right: int = -1) -> "Zipformer":
+        return cls([ZipformerLayer.from_torch(l, chunk, left, right) for l in layers], pos_dim)
+
+    def forward(self, x, T: int, B: int, lengths=None, stream: int = 0) -> DeviceMatrix:
+        lengths = _device_lengths_or_none(lengths)
+        if self._pos is None or self._pos[0] != T:
+            self._pos = (T, DeviceMatrix.from_numpy(compact_rel_positional_encoding(T, self.pos_dim)))
+        for layer in self.layers:
+            x = layer.forward(x, T, B, self._pos[1], T - 1, lengths, stream=stream)
         self._keep = lengths
         return x
 

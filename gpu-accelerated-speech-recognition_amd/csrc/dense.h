@@ -2,6 +2,7 @@
 #pragma once
 #include "asr_internal.h"
 #include "gelu.h"
+#include "swoosh.h"
 
 namespace asr {
 
@@ -13,12 +14,16 @@ enum GemmEpilogue {
     EPI_DUAL_TANH = 4,   // C = tanh((A.B + A2.B2) + (b2 + b1))
     EPI_ADD_TANH = 5,    // C = tanh((D + A.B) + (b2 + b1)); C may alias D
     EPI_BIAS_SILU = 6,   // C = silu(A.B + b1)
-    EPI_BIAS_GELU = 7    // C = gelu(A.B + b1), the exact (erf) form
+    EPI_BIAS_GELU = 7,   // C = gelu(A.B + b1), the exact (erf) form
+    // 8 is dense_x3.hip's X3_EPI_FRAG
+    EPI_BIAS_SWOOSHL = 9,   // C = swooshl(A.B + b1) (swoosh.h)
+    EPI_BIAS_SWOOSHR = 10   // C = swooshr(A.B + b1)
 };
 
 // The epilogues that add b1 and then apply an element-wise function (or none).
 constexpr bool epi_has_bias(int epi) {
-    return epi == EPI_BIAS || epi == EPI_BIAS_RELU || epi == EPI_BIAS_SILU || epi == EPI_BIAS_GELU;
+    return epi == EPI_BIAS || epi == EPI_BIAS_RELU || epi == EPI_BIAS_SILU || epi == EPI_BIAS_GELU ||
+           epi == EPI_BIAS_SWOOSHL || epi == EPI_BIAS_SWOOSHR;
 }
 
 // SiLU / Swish of a pre-activation, v / (1 + exp(-v)): one expression for every

@@ -185,6 +185,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x4 (&a
                 y = silu_f32(y + g.b1[col]);
             } else if (EPI == EPI_BIAS_GELU) {
                 y = gelu_f32(y + g.b1[col]);
+            } else if (EPI == EPI_BIAS_SWOOSHL) {
+                y = swooshl_f32(y + g.b1[col]);
+            } else if (EPI == EPI_BIAS_SWOOSHR) {
+                y = swooshr_f32(y + g.b1[col]);
             }
             g.C[(long)row * g.ldc + col] = y;
         }
@@ -412,8 +416,7 @@ static bool wide_off() {
 // and in any shard of it: utterance sharding over GPUs relies on that).
 template <int EPI>
 static bool try_gemm_wide(const GemmArgs& g, hipStream_t s, int& rc) {
-    if (EPI != EPI_NONE && EPI != EPI_BIAS && EPI != EPI_BIAS_RELU && EPI != EPI_BIAS_SILU &&
-        EPI != EPI_BIAS_GELU)
+    if (EPI != EPI_NONE && !epi_has_bias(EPI))
         return false;
     const bool va = g.sak == 1 && (g.K % 4) == 0 && (g.sam % 4) == 0 && ((uintptr_t)g.A % 16) == 0;
     if (!va || g.sbn != 1 || g.N < 128 || g.K > 256 || (long)g.M < 1024L * 128 || wide_off()) return false;
@@ -487,6 +490,8 @@ int gemm_launch(const GemmArgs& g, int epi, hipStream_t s) {
         case EPI_ADD_TANH: return launch_gemm_epi<EPI_ADD_TANH>(g, s);
         case EPI_BIAS_SILU: return launch_gemm_epi<EPI_BIAS_SILU>(g, s);
         case EPI_BIAS_GELU: return launch_gemm_epi<EPI_BIAS_GELU>(g, s);
+        case EPI_BIAS_SWOOSHL: return launch_gemm_epi<EPI_BIAS_SWOOSHL>(g, s);
+        case EPI_BIAS_SWOOSHR: return launch_gemm_epi<EPI_BIAS_SWOOSHR>(g, s);
         default: return ASR_ERR_ARG;
     }
 }

@@ -326,6 +326,8 @@ __global__ __launch_bounds__(64 * X3_WAVES) void gemm_x3_kernel(GemmArgs g, int 
                         if (EPI == EPI_BIAS_RELU && y < 0.f) y = 0.f;
                         if (EPI == EPI_BIAS_SILU) y = silu_f32(y);
                         if (EPI == EPI_BIAS_GELU) y = gelu_f32(y);
+                        if (EPI == EPI_BIAS_SWOOSHL) y = swooshl_f32(y);
+                        if (EPI == EPI_BIAS_SWOOSHR) y = swooshr_f32(y);
                         bstore(cs, (4 * gq * (int)g.ldc + ncol[ct]) * 4, y);
                     }
                 }
@@ -712,6 +714,8 @@ __global__ __launch_bounds__(64 * XK_WAVES) void gemm_x3k_kernel(GemmArgs g, con
                 if (EPI == EPI_BIAS_RELU && y < 0.f) y = 0.f;
                 if (EPI == EPI_BIAS_SILU) y = silu_f32(y);
                 if (EPI == EPI_BIAS_GELU) y = gelu_f32(y);
+                if (EPI == EPI_BIAS_SWOOSHL) y = swooshl_f32(y);
+                if (EPI == EPI_BIAS_SWOOSHR) y = swooshr_f32(y);
                 bstore(cs, ((32 * wm + 16 * rt + 4 * gq + j) * (int)g.ldc + n) * 4, y);
             }
     }
@@ -770,9 +774,7 @@ static bool x3k_applies(const GemmArgs& g) {
 }
 
 bool gemm_x3_applies(const GemmArgs& g, int epi) {
-    if (epi != EPI_NONE && epi != EPI_BIAS && epi != EPI_BIAS_RELU && epi != EPI_BIAS_SILU &&
-        epi != EPI_BIAS_GELU)
-        return false;
+    if (epi != EPI_NONE && !epi_has_bias(epi)) return false;
     const bool va = g.sak == 1 && (g.K % 4) == 0 && (g.sam % 4) == 0 && ((uintptr_t)g.A % 16) == 0;
     if (!va) return false;
     if (g.K > 256) return x3k_applies(g);
@@ -802,6 +804,8 @@ int gemm_x3_launch(const GemmArgs& g, int epi, int tpw, hipStream_t s) {
             case EPI_BIAS: return launch_gemm_x3k<EPI_BIAS>(g, s);
             case EPI_BIAS_SILU: return launch_gemm_x3k<EPI_BIAS_SILU>(g, s);
             case EPI_BIAS_GELU: return launch_gemm_x3k<EPI_BIAS_GELU>(g, s);
+            case EPI_BIAS_SWOOSHL: return launch_gemm_x3k<EPI_BIAS_SWOOSHL>(g, s);
+            case EPI_BIAS_SWOOSHR: return launch_gemm_x3k<EPI_BIAS_SWOOSHR>(g, s);
             default: return launch_gemm_x3k<EPI_BIAS_RELU>(g, s);
         }
     }
@@ -810,6 +814,8 @@ int gemm_x3_launch(const GemmArgs& g, int epi, int tpw, hipStream_t s) {
         case EPI_BIAS: return launch_gemm_x3_epi<EPI_BIAS>(g, tpw, s);
         case EPI_BIAS_SILU: return launch_gemm_x3_epi<EPI_BIAS_SILU>(g, tpw, s);
         case EPI_BIAS_GELU: return launch_gemm_x3_epi<EPI_BIAS_GELU>(g, tpw, s);
+        case EPI_BIAS_SWOOSHL: return launch_gemm_x3_epi<EPI_BIAS_SWOOSHL>(g, tpw, s);
+        case EPI_BIAS_SWOOSHR: return launch_gemm_x3_epi<EPI_BIAS_SWOOSHR>(g, tpw, s);
         default: return launch_gemm_x3_epi<EPI_BIAS_RELU>(g, tpw, s);
     }
 }

@@ -55,6 +55,7 @@ static_assert(GD_ROWS * GD_CH * sizeof(float) <= 64 * 1024, "the staged tile fit
 __device__ __forceinline__ float glu_act(float v, int act) {
     if (act == ASR_GLU_ACT_RELU) return fmaxf(v, 0.f);
     if (act == ASR_GLU_ACT_SILU) return silu_f32(v);
+    if (act == ASR_GLU_ACT_SWOOSHR) return swooshr_f32(v);
     return v;
 }
 
@@ -136,7 +137,9 @@ int asr_glu_dwconv_fwd(const asr_glu_dwconv_desc* d, const float* d_u, long ldu,
     if (T <= 0 || B <= 0 || d->channels <= 0 || d->kernel <= 0) return ASR_ERR_ARG;
     if (d->pad_left < 0 || d->pad_right < 0) return ASR_ERR_ARG;
     if (ldu < 2L * d->channels || ldo < d->channels) return ASR_ERR_ARG;
-    if (d->act != ASR_GLU_ACT_NONE && d->act != ASR_GLU_ACT_RELU && d->act != ASR_GLU_ACT_SILU) return ASR_ERR_ARG;
+    if (d->act != ASR_GLU_ACT_NONE && d->act != ASR_GLU_ACT_RELU && d->act != ASR_GLU_ACT_SILU &&
+        d->act != ASR_GLU_ACT_SWOOSHR)
+        return ASR_ERR_ARG;
     if (d_out == d_u) return ASR_ERR_ARG;
     if ((long)d->pad_left + d->pad_right != (long)d->kernel - 1) return ASR_ERR_UNSUPPORTED;
     if (d->kernel > ASR_GLU_DWCONV_MAX_KERNEL) return ASR_ERR_UNSUPPORTED;

@@ -169,6 +169,8 @@ int asr_linear_fwd(const float* x, const float* W, const float* b, float* y, int
         case ASR_EPI_BIAS_LOGSOFTMAX: epi = asr::EPI_LOGSOFTMAX; break;
         case ASR_EPI_BIAS_SILU: epi = asr::EPI_BIAS_SILU; break;
         case ASR_EPI_BIAS_GELU: epi = asr::EPI_BIAS_GELU; break;
+        case ASR_EPI_BIAS_SWOOSHL: epi = asr::EPI_BIAS_SWOOSHL; break;
+        case ASR_EPI_BIAS_SWOOSHR: epi = asr::EPI_BIAS_SWOOSHR; break;
         default: return ASR_ERR_ARG;
     }
     return asr::gemm_launch(g, epi, asr_stream(s));

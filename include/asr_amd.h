@@ -91,7 +91,9 @@ typedef enum asr_epilogue {
     ASR_EPI_BIAS_RELU = 2,       /* y = max(x.W + b, 0)  — Linear.cu:3-10 ReLU      */
     ASR_EPI_BIAS_LOGSOFTMAX = 3, /* y = log_softmax(x.W + b) per row (model.py:49)  */
     ASR_EPI_BIAS_SILU = 4,       /* y = v / (1 + exp(-v)), v = x.W + b (SiLU / Swish) */
-    ASR_EPI_BIAS_GELU = 6        /* y = v/2 * erfc(-v / sqrt(2)), v = x.W + b (exact GELU); 5 is not assigned */
+    ASR_EPI_BIAS_GELU = 6,       /* y = v/2 * erfc(-v / sqrt(2)), v = x.W + b (exact GELU); 5 is not assigned */
+    ASR_EPI_BIAS_SWOOSHL = 7,    /* y = log1p(exp(v - 4)) - 0.08 v - 0.035, v = x.W + b (SwooshL)       */
+    ASR_EPI_BIAS_SWOOSHR = 8     /* y = log1p(exp(v - 1)) - 0.08 v - 0.313261687 (SwooshR)               */
 } asr_epilogue;
 
 /* Linear::forward (Linear.cu:42-49): y[M,N] = epi(x[M,K] . W[K,N] + b[N]).
@@ -104,7 +106,10 @@ typedef enum asr_epilogue {
  * (the cgMLP's activation: the exact GELU, torch.nn.GELU()'s default, not the
  * tanh approximation) is applied in the same places under the same rules, as
  * v/2 * erfc(-v / sqrt(2)): 1 + erf(x) = erfc(-x) has no cancellation in the
- * negative tail; -100 gives -0 and +100 gives 100.  Every epilogue but
+ * negative tail; -100 gives -0 and +100 gives 100.  ASR_EPI_BIAS_SWOOSHL /
+ * _SWOOSHR (the Zipformer's feed-forward activations) follow the same rules;
+ * for v - c > 20 (c = 4 / 1) the log term is v - c itself, so +100 is finite
+ * and -100 gives 0.08 * 100 - const, never NaN or inf.  Every epilogue but
  * ASR_EPI_NONE needs d_b (NULL: ASR_ERR_ARG). */
 int asr_linear_fwd(const float* d_x, const float* d_W, const float* d_b, float* d_y, int M,
                    int K, int N, int epilogue, asr_stream_t s);
@@ -578,7 +583,9 @@ int asr_conv2d_fwd(const asr_conv2d_desc* d, const float* d_x, long ldx, const i
  * Stride 1, dilation 1, pad_left + pad_right = kernel - 1, so T_out = T: "same"
  * is ((k-1)/2, k-1 - (k-1)/2), causal (k-1, 0).  One fmaf chain per element
  * from 0, taps ascending, then the bias, then the activation:
- * ASR_GLU_ACT_NONE, _RELU max(v, 0) or _SILU v / (1 + exp(-v)).  The sigmoid is
+ * ASR_GLU_ACT_NONE, _RELU max(v, 0), _SILU v / (1 + exp(-v)) or _SWOOSHR
+ * (ASR_EPI_BIAS_SWOOSHR's expression; the Zipformer's convolution module, which
+ * has no BatchNorm to fold).  The sigmoid is
  * evaluated once per input element.  fp32 always.
  * d_lengths device int32 [B], clamped to [0, T], NULL = all T.  Frames
  * t >= len[b] of u are never read (the zero is selected, not multiplied: they
@@ -599,7 +606,7 @@ int asr_conv2d_fwd(const asr_conv2d_desc* d, const float* d_x, long ldx, const i
  * Not built: stride or dilation other than 1, GroupNorm / LayerNorm in place of
  * the BatchNorm, a split-bf16 variant. */
 #define ASR_GLU_DWCONV_MAX_KERNEL 80
-enum { ASR_GLU_ACT_NONE = 0, ASR_GLU_ACT_RELU = 1, ASR_GLU_ACT_SILU = 2 };
+enum { ASR_GLU_ACT_NONE = 0, ASR_GLU_ACT_RELU = 1, ASR_GLU_ACT_SILU = 2, ASR_GLU_ACT_SWOOSHR = 4 };   /* 3 is not assigned */
 typedef struct asr_glu_dwconv_desc {
     int channels;             /* C: u rows have 2C floats, out rows C */
     int kernel;               /* k taps, 1 .. ASR_GLU_DWCONV_MAX_KERNEL */
@@ -772,6 +779,100 @@ int asr_attention_rel_fwd(const asr_attn_desc* d, const float* d_q, long ldq, co
                           const float* d_v, long ldv, const float* d_pos, long ldp, int n_pos, int pos_zero,
                           const float* d_bias_u, const float* d_bias_v, const int32_t* d_lengths, float* d_out,
                           long ldo, int Tq, int q_pos0, int Tk, int k_pos0, int B, asr_stream_t s);
+
+/* Shared-score attention, the attention of the Zipformer encoder (icefall's
+ * zipformer.py, Zipformer2):
+ *   score(p, r, h) = scale * (q(p,b,h,:) . k(r,b,h,:) + pz(p,b,h,:) . pi(h, p - r)),
+ *   out(p, b, g, :) = sum_r softmax_r(score(p, r, s(g))) v(r, b, g, :)  over the keys p sees.
+ * One set of scores serves several value tensors: the caller keeps q, k and pz
+ * and calls once per value tensor; the probabilities are never written to
+ * memory, each call recomputes them.  Everything asr_attention_fwd means stays:
+ * the time-major layout, absolute positions q_pos0 / k_pos0, d_lengths, the
+ * chunk / left / right window, exact zeros for dead queries and for queries
+ * that see nothing (selected, not multiplied: padding rows of every operand,
+ * d_sg and d_y included, may hold NaN), 64-key blocks aligned on absolute
+ * positions, and an output row's bits depend only on what that row sees and
+ * the descriptor (never on B, Tq, Tk, how a stream is cut, strides, alignment,
+ * value_dim or the other columns of the value head).
+ * Widths: d_q / d_k rows hold heads*query_dim floats (head h at columns
+ * [h*query_dim, ...)), d_pz rows (Tq frames) heads*pos_dim, d_v / d_out rows
+ * value_heads*value_dim.  value_heads == heads: value head g uses score head g
+ * (self_attn1 / self_attn2).  value_heads == 1: one value head of width
+ * value_dim <= 4096 uses score head `score_head` (the non-linear attention).
+ * gate == 1: the value used is d_v(r) * tanh(d_sg(r)) (d_sg: Tk frames, d_v's
+ * columns, stride ldsg) and the output row is multiplied by d_y(p) (Tq frames,
+ * d_out's columns, stride ldy); tanh saturates, sg = +-100 gives +-1.  gate ==
+ * 0: d_sg and d_y are not read (NULL allowed).  All operands may be column
+ * ranges of one projection buffer; d_out must not overlap any of them.
+ * d_pos [n_pos][>= heads*pos_dim] (row stride ldp) is the projected position
+ * table in asr_attention_rel_fwd's convention: row pos_zero - delta holds
+ * distance delta = query frame - key frame, the rows a call may need are that
+ * entry point's delta_max / delta_min range, and no row outside it is loaded
+ * (such rows may hold NaN).  pos_dim == 0 drops the term: d_pz and d_pos are
+ * not read (NULL allowed) and n_pos / pos_zero are ignored.
+ * scale = 0 means 1 / sqrt(query_dim); the Zipformer passes 1 (its scale is in
+ * the projection weights).  Arithmetic: fp32 always, all three products on
+ * v_mfma_f32_16x16x4_f32, online softmax; the content product keeps
+ * asr_attention_fwd's chain.  Grid (ceil(Tq / 64), value_heads * slabs, B): a
+ * value head wider than 128 columns is cut into slabs of 128 and each slab's
+ * workgroup recomputes the scores (csrc/attention_zip.hip).
+ * One launch, asynchronous on s, no allocation, no workspace, no host sync.
+ * Checks, in this order, all before any HIP call — ASR_ERR_ARG: a NULL
+ * descriptor, d_q, d_k, d_v or d_out; pos_dim < 0 or a gate other than 0 / 1;
+ * pos_dim > 0 with a NULL d_pz or d_pos; gate with a NULL d_sg or d_y;
+ * non-positive Tq, Tk, B, heads, query_dim, value_dim or chunk (n_pos when
+ * pos_dim > 0); value_heads neither heads nor 1; score_head outside [0, heads);
+ * left or right < -1; negative q_pos0 or k_pos0; ldq or ldk < heads*query_dim,
+ * ldv or ldo < value_heads*value_dim; with pos_dim > 0, ldpz or ldp <
+ * heads*pos_dim; with the gate, ldsg or ldy < value_heads*value_dim; a scale
+ * that is not finite or < 0; with pos_dim > 0, pos_zero - delta_max < 0 or
+ * pos_zero - delta_min > n_pos - 1.  ASR_ERR_UNSUPPORTED: query_dim % 4 != 0
+ * or > 128 or heads*query_dim > 4096; pos_dim % 4 != 0 or > 16; value_dim % 4
+ * != 0 or value_heads*value_dim > 4096; heads or B > 65535; q_pos0 + Tq or
+ * k_pos0 + Tk > INT_MAX - 64; Tq*B or Tk*B > INT_MAX.
+ * Not built: a form that holds P for a key block and streams value slabs past
+ * it; a split-bf16 variant; training. */
+typedef struct asr_zattn_desc {
+    int heads;             /* H score heads */
+    int query_dim;         /* dq % 4 == 0, 4 .. 128; heads*query_dim <= 4096 */
+    int pos_dim;           /* dp % 4 == 0, 0 .. 16; 0 = no position term */
+    int value_heads;       /* G: heads or 1 */
+    int value_dim;         /* dv % 4 == 0; value_heads*value_dim <= 4096 */
+    int score_head;        /* 0 .. heads - 1: the score head value_heads == 1 uses (else ignored) */
+    float scale;           /* 0 = 1/sqrt(query_dim); else finite, > 0 */
+    int chunk, left, right;   /* asr_attn_desc's window */
+    int gate;              /* 0 / 1 */
+} asr_zattn_desc;
+int asr_attention_zip_fwd(const asr_zattn_desc* d, const float* d_q, long ldq, const float* d_k, long ldk,
+                          const float* d_pz, long ldpz, const float* d_v, long ldv, const float* d_sg, long ldsg,
+                          const float* d_y, long ldy, const float* d_pos, long ldp, int n_pos, int pos_zero,
+                          const int32_t* d_lengths, float* d_out, long ldo, int Tq, int q_pos0, int Tk, int k_pos0,
+                          int B, asr_stream_t s);
+
+/* BiasNorm, the Zipformer's norm, one wave per row [T*B rows of N columns]:
+ *   out(t, b, c) = x(t, b, c) * exp(log_scale) / sqrt(mean_c((x(t, b, c) - bias[c])^2))
+ * (x itself is scaled, not x - bias; no epsilon, as in icefall).  A row equal
+ * to its bias has mean square 0: the factor is +inf, so the row is +-inf where
+ * x != 0 and NaN where x == 0, which is what the float64 formula gives.
+ * With d_x0 [rows][>= N] (stride ldx0) and d_bypass [N] both given, the layer's
+ * last bypass is fused: out = x0 + (out - x0) * bypass[c].  The sum of squares
+ * is asr_layernorm_fwd's order (a lane's columns ascending, then the butterfly).
+ * Rows t >= len[b] are zeros and are not read.  d_out may alias d_x or d_x0.
+ * Checks, in this order — ASR_ERR_ARG: a NULL d_x, d_bias or d_out; exactly one
+ * of d_x0 / d_bypass NULL; non-positive T, B or N; ldx or ldo < N (ldx0 with
+ * d_x0); a log_scale that is not finite.  ASR_ERR_UNSUPPORTED: N > 4096;
+ * T*B > INT_MAX. */
+int asr_biasnorm_fwd(const float* d_x, long ldx, const float* d_bias, float log_scale, const float* d_x0, long ldx0,
+                     const float* d_bypass, const int32_t* d_lengths, float* d_out, long ldo, int T, int B, int N,
+                     asr_stream_t s);
+
+/* The Zipformer's per-channel bypass: out = x0 + (x - x0) * scale[c], rows
+ * t >= len[b] zeros (asr_matadd takes a scalar).  d_out may alias d_x or d_x0.
+ * Checks, in this order — ASR_ERR_ARG: a NULL d_x, d_x0, d_scale or d_out;
+ * non-positive T, B or N; ldx, ldx0 or ldo < N.  ASR_ERR_UNSUPPORTED: N > 4096;
+ * T*B > INT_MAX. */
+int asr_bypass_fwd(const float* d_x, long ldx, const float* d_x0, long ldx0, const float* d_scale,
+                   const int32_t* d_lengths, float* d_out, long ldo, int T, int B, int N, asr_stream_t s);
 
 /* Grouped cross-attention, the hot path of attention-decoder rescoring (WeNet's
  * attention_rescoring, ESPnet's joint CTC / attention scoring): N = sum n_b
