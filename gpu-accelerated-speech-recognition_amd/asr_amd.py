@@ -194,6 +194,8 @@ EXPORTS = [
     "asr_ctc_prefix_begin", "asr_ctc_prefix_score", "asr_ctc_prefix_advance",
     "asr_fbank_num_frames", "asr_fbank_feature_dim", "asr_fbank_host_tables", "asr_fbank_create",
     "asr_fbank_destroy", "asr_fbank_workspace_bytes", "asr_fbank_fwd",
+    "asr_stft_num_frames", "asr_stft_host_basis", "asr_stft_create", "asr_stft_destroy",
+    "asr_stft_workspace_bytes", "asr_stft_fwd", "asr_add_pos_fwd",
     "asr_lm_create_arpa", "asr_lm_create_arpa_mem", "asr_lm_destroy", "asr_lm_get_info", "asr_lm_token_id",
     "asr_lm_token_string", "asr_lm_score_host", "asr_lm_upload", "asr_lm_score",
     "asr_edit_distance", "asr_edit_distance_host", "asr_nbest_mbr", "asr_nbest_mbr_host",
@@ -426,6 +428,12 @@ def lib() -> ctypes.CDLL:
                                 _vp]
     sig["asr_wave_conv_out_frames"] = [_vp, _i]
     sig["asr_layernorm_gelu_fwd"] = [_vp, ctypes.c_long, _vp, _vp, _f, _i, _vp, _vp, ctypes.c_long, _i, _i, _i, _vp]
+    sig["asr_stft_num_frames"] = [_vp, _i]
+    sig["asr_stft_host_basis"] = [_vp, _vp, _vp]
+    sig["asr_stft_create"] = [_vp, _vp, _vp, ctypes.POINTER(_vp)]
+    sig["asr_stft_destroy"] = [_vp]
+    sig["asr_stft_fwd"] = [_vp, _vp, ctypes.c_long, _vp, _i, _i, _i, _vp, ctypes.c_long, _vp, _vp, _i, _vp]
+    sig["asr_add_pos_fwd"] = [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, ctypes.c_long, _i, _i, _i, _i, _vp]
     for name, args in sig.items():
         fn = getattr(L, name)
         fn.argtypes = args
@@ -440,6 +448,8 @@ def lib() -> ctypes.CDLL:
     L.asr_wave_conv_workspace_bytes.restype = _sz
     L.asr_fbank_workspace_bytes.argtypes = [_vp, _i, _i]
     L.asr_fbank_workspace_bytes.restype = _sz
+    L.asr_stft_workspace_bytes.argtypes = [_vp, _i, _i]
+    L.asr_stft_workspace_bytes.restype = _sz
     L.asr_ctc_align_workspace_bytes.argtypes = [_i, _i, _i]
     L.asr_ctc_align_workspace_bytes.restype = _sz
     L.asr_rnnt_workspace_bytes.argtypes = [_vp, _i, _i]
@@ -4405,6 +4415,249 @@ class FeatureFrontend:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------- torch.stft-style front end, Whisper encoder
+STFT_LOG_NONE, STFT_LOG_LN, STFT_LOG_LOG10, STFT_LOG_DB = 0, 1, 2, 3
+STFT_LOGS = {None: STFT_LOG_NONE, "none": STFT_LOG_NONE, "ln": STFT_LOG_LN, "log10": STFT_LOG_LOG10, "db": STFT_LOG_DB}
+STFT_FLOOR_CLAMP, STFT_FLOOR_ADD = 0, 1
+STFT_FLOORS = {"clamp": STFT_FLOOR_CLAMP, "add": STFT_FLOOR_ADD}
+ADD_POS_ACTS = {None: 0, "none": 0, "gelu": 1}
+
+
+class StftConfig(ctypes.Structure):
+    """asr_stft_config (include/asr_amd.h)."""
+    _fields_ = [("n_fft", _i), ("win_length", _i), ("hop_length", _i), ("center", _i), ("power", _i), ("n_mels", _i),
+                ("log", _i), ("floor_mode", _i), ("floor", _f), ("dyn_range", _f), ("shift", _f), ("scale", _f),
+                ("drop_last", _i)]
+
+
+def stft_config(n_fft: int, win_length: Optional[int] = None, hop_length: Optional[int] = None, center: bool = True,
+                power: int = 2, n_mels: int = 80, log="ln", floor_mode="clamp", floor: float = 1e-10,
+                dyn_range: float = 0.0, shift: float = 0.0, scale: float = 1.0, drop_last: bool = False) -> StftConfig:
+    """torch.stft's defaults: win_length = n_fft, hop_length = win_length // 4."""
+    win = n_fft if win_length is None else win_length
+    return StftConfig(n_fft, win, win // 4 if hop_length is None else hop_length, int(bool(center)), power, n_mels,
+                      STFT_LOGS[log] if not isinstance(log, int) else log,
+                      STFT_FLOORS[floor_mode] if isinstance(floor_mode, str) else int(floor_mode), floor, dyn_range,
+                      shift, scale, int(bool(drop_last)))
+
+
+def mel_filter_bank(n_bins: int, n_mels: int, f_min: float, f_max: float, sample_rate: float,
+                    mel_scale: str = "htk", norm: Optional[str] = None) -> np.ndarray:
+    """Triangular mel filters [n_mels, n_bins] in float64 over the n_bins
+    frequencies 0 .. sample_rate / 2: n_mels + 2 corners equally spaced in mel
+    ("htk": 2595 log10(1 + f / 700); "slaney": linear below 1 kHz, logarithmic
+    above, as librosa), weights max(0, min(rising, falling)) on the Hz axis;
+    norm "slaney" divides each filter by half its width in Hz.  The Whisper
+    setting (201, 80 or 128, 0, 8000, 16000, "slaney", "slaney") is
+    WhisperFeatureExtractor.mel_filters, transposed."""
+    if mel_scale not in ("htk", "slaney") or norm not in (None, "slaney"):
+        raise ValueError(f"mel_filter_bank: mel_scale {mel_scale!r} / norm {norm!r}")
+    logstep = 27.0 / np.log(6.4)
+
+    def to_mel(f):
+        f = np.asarray(f, np.float64)
+        if mel_scale == "htk":
+            return 2595.0 * np.log10(1.0 + f / 700.0)
+        return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) * logstep, 3.0 * f / 200.0)
+
+    def to_hz(m):
+        if mel_scale == "htk":
+            return 700.0 * (np.power(10.0, m / 2595.0) - 1.0)
+        return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), 200.0 * m / 3.0)
+
+    corners = to_hz(np.linspace(to_mel(f_min), to_mel(f_max), n_mels + 2))
+    freqs = np.linspace(0.0, sample_rate / 2.0, n_bins)
+    width = np.diff(corners)
+    slopes = corners[None, :] - freqs[:, None]
+    w = np.maximum(0.0, np.minimum(-slopes[:, :-2] / width[:-1], slopes[:, 2:] / width[1:]))
+    if norm == "slaney":
+        w = w * (2.0 / (corners[2:n_mels + 2] - corners[:n_mels]))
+    return np.ascontiguousarray(w.T)
+
+
+def stft_window(kind: str, win_length: int, periodic: bool = True) -> np.ndarray:
+    """A float64 window of win_length samples: "hann", "hamming" or "rect";
+    periodic (torch's default, the first win_length samples of the symmetric
+    window of win_length + 1) or symmetric."""
+    n = np.arange(win_length, dtype=np.float64)
+    ang = 2.0 * np.pi * n / (win_length if periodic else max(win_length - 1, 1))
+    if kind == "hann":
+        return 0.5 - 0.5 * np.cos(ang)
+    if kind == "hamming":
+        return 0.54 - 0.46 * np.cos(ang)
+    if kind == "rect":
+        return np.ones(win_length)
+    raise ValueError(f"stft_window: kind {kind!r}")
+
+
+def stft_num_frames(cfg: StftConfig, n_samples: int) -> int:
+    return int(lib().asr_stft_num_frames(ctypes.byref(cfg), int(n_samples)))
+
+
+def stft_host_basis(cfg: StftConfig, window) -> np.ndarray:
+    """The fp32 DFT basis the device uses, [n_fft, 2 NBp] (asr_stft_host_basis)."""
+    win = np.ascontiguousarray(window, np.float32)
+    assert win.shape == (cfg.win_length,), win.shape
+    G = np.zeros((cfg.n_fft, 2 * ((cfg.n_fft // 2 + 1 + 15) // 16 * 16)), np.float32)
+    check(lib().asr_stft_host_basis(ctypes.byref(cfg), _ptr(win), _ptr(G)), "asr_stft_host_basis")
+    return G
+
+
+def add_pos_fwd(x, pos, out, T: int, B: int, N: int, act=None, lengths: Optional[DeviceBytes] = None,
+                stream: int = 0):
+    """out[t*B + b] = act(x[t*B + b]) + pos[t] over the first N columns
+    (asr_add_pos_fwd); act None or "gelu"; out may be x; rows past lengths
+    become zeros."""
+    assert pos.rows >= T, (pos.rows, T)
+    check(lib().asr_add_pos_fwd(x.ptr, x.cols, pos.ptr, pos.cols, lengths.ptr if lengths is not None else None,
+                                out.ptr, out.cols, T, B, N, ADD_POS_ACTS[act], stream), "asr_add_pos_fwd")
+    return out
+
+
+class StftFrontend:
+    """Waveform -> (log-)mel features in torch.stft's conventions on
+    asr_stft_fwd (the semantics are in include/asr_amd.h): any n_fft, centred
+    frames with reflect padding, the caller's window and mel matrix.  config: a
+    StftConfig (stft_config(...)); window [win_length]; mel [n_mels, n_fft/2+1].
+    No arithmetic here beyond rounding the two tables to fp32."""
+
+    def __init__(self, config: StftConfig, window, mel):
+        self.h = None
+        self.cfg = config
+        self.window = np.ascontiguousarray(window, np.float32)
+        self.mel = np.ascontiguousarray(mel, np.float32)
+        if self.window.shape != (config.win_length,) or self.mel.shape != (config.n_mels, config.n_fft // 2 + 1):
+            raise ValueError(f"StftFrontend: window {self.window.shape} / mel {self.mel.shape} do not fit the config")
+        h = _vp()
+        check(lib().asr_stft_create(ctypes.byref(config), _ptr(self.window), _ptr(self.mel), ctypes.byref(h)),
+              "asr_stft_create")
+        self.h = h.value
+        self._work: Optional[DeviceBytes] = None
+        self._keep = None
+
+    @classmethod
+    def whisper(cls, n_mels: int = 80) -> "StftFrontend":
+        """Whisper's features (80 mels; 128 for large-v3); pass pad_to=480000
+        to forward for the 30 s input its encoder takes."""
+        cfg = stft_config(400, 400, 160, True, 2, n_mels, "log10", "clamp", 1e-10, 8.0, 4.0, 0.25, True)
+        return cls(cfg, stft_window("hann", 400), mel_filter_bank(201, n_mels, 0.0, 8000.0, 16000.0, "slaney", "slaney"))
+
+    @classmethod
+    def from_transformers(cls, feature_extractor) -> "StftFrontend":
+        """From a transformers WhisperFeatureExtractor: its n_fft, hop_length,
+        feature_size and mel_filters; n_samples is kept as self.n_samples."""
+        fe = feature_extractor
+        if getattr(fe, "dither", 0.0):
+            raise ValueError("StftFrontend.from_transformers: dither is not supported")
+        cfg = stft_config(fe.n_fft, fe.n_fft, fe.hop_length, True, 2, fe.feature_size, "log10", "clamp", 1e-10, 8.0,
+                          4.0, 0.25, True)
+        front = cls(cfg, stft_window("hann", fe.n_fft), np.asarray(fe.mel_filters, np.float64).T)
+        front.n_samples = int(fe.n_samples)
+        return front
+
+    def num_frames(self, n_samples: int) -> int:
+        return stft_num_frames(self.cfg, n_samples)
+
+    def workspace_bytes(self, T: int, B: int) -> int:
+        return int(lib().asr_stft_workspace_bytes(self.h, T, B))
+
+    def forward(self, wave, nsamples=None, pad_to: int = 0, stream: int = 0, T: Optional[int] = None):
+        """wave: a numpy [B, S] float32 array or a DeviceMatrix [B, S]; nsamples
+        None, a sequence of B counts or a DeviceBytes of int32 [B]; pad_to > 0:
+        every utterance is followed by zeros up to pad_to samples.  Returns
+        (features DeviceMatrix [T*B, n_mels] time-major with zero rows past an
+        utterance's frames, frames DeviceBytes int32 [B]); T defaults to
+        num_frames(pad_to or S) (at least 1).  Asynchronous on stream."""
+        st = stream or 0
+        if isinstance(wave, np.ndarray):
+            wave = DeviceMatrix.from_numpy(np.ascontiguousarray(wave, np.float32))
+        B, S = wave.rows, wave.cols
+        nsamples = _device_lengths_or_none(nsamples)
+        T = max(1, self.num_frames(pad_to or S)) if T is None else int(T)
+        out, frames = DeviceMatrix(T * B, self.cfg.n_mels), DeviceBytes(4 * B)
+        need = self.workspace_bytes(T, B)
+        if need and (self._work is None or self._work.nbytes < need):
+            self._work = DeviceBytes(need)
+        check(lib().asr_stft_fwd(self.h, wave.ptr, S, nsamples.ptr if nsamples is not None else None, B, S, int(pad_to),
+                                 out.ptr, out.cols, frames.ptr, self._work.ptr if need else None, T, st),
+              "asr_stft_fwd")
+        self._keep = [wave, nsamples]
+        return out, frames
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            lib().asr_stft_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WhisperEncoder:
+    """Whisper's audio encoder for inference on the existing layers:
+    Conv1d(k 3, pad 1) -> GELU (asr_layernorm_gelu_fwd, norm off) ->
+    Conv1d(k 3, stride 2, pad 1) -> GELU + positional table in one pass
+    (asr_add_pos_fwd) -> N pre-norm TransformerEncoderLayer(activation="gelu")
+    -> LayerNorm.  pos: the [max_source_positions, d_model] table."""
+
+    def __init__(self, conv1: Conv1d, conv2: Conv1d, pos, layers: Sequence[TransformerEncoderLayer],
+                 ln_post: LayerNorm):
+        pos = np.asarray(pos, np.float32)
+        self.E = conv2.desc.c_out
+        if pos.ndim != 2 or pos.shape[1] != self.E or conv1.desc.c_out != conv2.desc.c_in or ln_post.N != self.E:
+            raise ValueError("WhisperEncoder: the convolutions, the positional table and the last norm disagree")
+        self.conv1, self.conv2, self.layers, self.ln_post = conv1, conv2, list(layers), ln_post
+        self.pos = DeviceMatrix.from_numpy(pos)
+        self.out_lengths, self._keep = None, None
+
+    @classmethod
+    def from_transformers(cls, model_or_encoder) -> "WhisperEncoder":
+        """From a transformers WhisperModel / WhisperForConditionalGeneration /
+        WhisperEncoder (or a module with the same attribute names)."""
+        enc = model_or_encoder
+        for name in ("model", "encoder"):
+            enc = getattr(enc, name, enc)
+        host = lambda p: p.detach().cpu().float().numpy()   # noqa: E731
+        norm = lambda m: LayerNorm(len(m.weight), float(m.eps), host(m.weight), host(m.bias))   # noqa: E731
+        layers = []
+        for layer in enc.layers:
+            at = layer.self_attn
+            ws, bs = zip(*(_torch_linear(lin) for lin in (at.q_proj, at.k_proj, at.v_proj)))   # k_proj: no bias, zeros
+            w_out, b_out = _torch_linear(at.out_proj)
+            w1, b1 = _torch_linear(layer.fc1)
+            w2, b2 = _torch_linear(layer.fc2)
+            mha = MultiheadAttention(w_out.shape[0], int(at.num_heads), np.ascontiguousarray(np.concatenate(ws, axis=1)),
+                                     np.concatenate(bs), w_out, b_out)
+            layers.append(TransformerEncoderLayer(mha, norm(layer.self_attn_layer_norm), norm(layer.final_layer_norm),
+                                                  w1, b1, w2, b2, norm_first=True, activation="gelu"))
+        return cls(Conv1d.from_torch(enc.conv1), Conv1d.from_torch(enc.conv2), host(enc.embed_positions.weight),
+                   layers, norm(enc.layer_norm))
+
+    def forward(self, features, T: int, B: int, lengths=None, stream: int = 0) -> DeviceMatrix:
+        """features time-major [T*B, n_mels] (StftFrontend.forward's output);
+        lengths None (Whisper: all T frames), B counts or a DeviceBytes.
+        Returns the states [T_out*B, d_model], T_out = (T - 1) // 2 + 1, in the
+        layout CrossAttention and TransformerDecoder take as memory; the
+        frame counts are kept as self.out_lengths (None without lengths)."""
+        st, E = stream or 0, self.E
+        x, T1, l1 = self.conv1.forward(features, T, B, lengths, st)
+        layernorm_gelu_fwd(x, x, T1, B, self.conv1.desc.c_out, norm=False, lengths=l1, stream=st)
+        y, T2, l2 = self.conv2.forward(x, T1, B, l1, st)
+        if T2 > self.pos.rows:
+            raise AsrError(ASR_ERR_ARG, f"WhisperEncoder.forward: {T2} frames, {self.pos.rows} positions")
+        add_pos_fwd(y, self.pos, y, T2, B, E, "gelu", l2, st)
+        keep = [features, x, y]
+        for layer in self.layers:
+            y = layer.forward(y, T2, B, l2, st)
+            keep.append(y)
+        out = self.ln_post.forward(y, T2, B, l2, stream=st)
+        self.out_lengths, self._keep = l2, keep
+        return out
 
 
 def device_int32(d: DeviceBytes, n: int, stream: int = 0) -> np.ndarray:

@@ -1601,6 +1601,109 @@ size_t asr_fbank_workspace_bytes(const asr_fbank_t* h, int T, int B);
 int asr_fbank_fwd(asr_fbank_t* h, const float* d_wave, long ldw, const int32_t* d_nsamples, int B, int S,
                   float* d_out, long ldo, int32_t* d_frames, void* d_work, int T, asr_stream_t s);
 
+/* ---- torch.stft-style front end: waveform -> (log-)mel features, any n_fft ----
+ * No reference member is replaced.  The conventions are torch.stft's (Whisper,
+ * torchaudio MelSpectrogram, librosa, NeMo), where asr_fbank_* above has
+ * Kaldi's: with center the signal of L samples is reflect-padded by n_fft / 2
+ * at both ends (position -i is sample i, position L - 1 + i is sample
+ * L - 1 - i) and frame t is padded positions [t hop, t hop + n_fft); without,
+ * frame t is samples [t hop, t hop + n_fft).  The caller's window of
+ * win_length samples sits at offset (n_fft - win_length) / 2 inside n_fft,
+ * zeros around it.  X[k] = sum_n w'[n] x[n] exp(-2 pi i n k / n_fft), k = 0 ..
+ * n_fft / 2; P = |X| (power 1) or |X|^2 (power 2), no scaling;
+ * mel[m] = sum_k h_mel[m][k] P[k]; then by log:
+ *   NONE  x = mel;          LN  x = ln(f(mel));
+ *   LOG10 x = log10(f(mel)); DB  x = 10 log10(f(mel)),
+ * f(v) = max(v, floor) (ASR_STFT_FLOOR_CLAMP) or v + floor (ASR_STFT_FLOOR_ADD);
+ * with dyn_range > 0, x = max(x, max_b - dyn_range), max_b the maximum of x over
+ * the utterance's valid frames and mel bins; last x = (x + shift) * scale.
+ * Whisper: n_fft = win = 400 (periodic Hann), hop 160, center, power 2, Slaney
+ * mel with Slaney norm, LOG10 with FLOOR_CLAMP 1e-10, dyn_range 8, shift 4,
+ * scale 0.25, drop_last, pad_to = 480000.  The window's and the mel matrix's
+ * conventions are the caller's (asr_amd.py: stft_window, mel_filter_bank). */
+enum { ASR_STFT_LOG_NONE = 0, ASR_STFT_LOG_LN = 1, ASR_STFT_LOG_LOG10 = 2, ASR_STFT_LOG_DB = 3 };
+enum { ASR_STFT_FLOOR_CLAMP = 0, ASR_STFT_FLOOR_ADD = 1 };
+
+typedef struct asr_stft_config {
+    int n_fft;          /* 16 .. 1024, any integer, not only powers of two      */
+    int win_length;     /* 2 .. n_fft; centred inside n_fft (torch.stft)         */
+    int hop_length;     /* 1 .. n_fft                                            */
+    int center;         /* 1: reflect-pad n_fft/2 at both ends; 0: no padding    */
+    int power;          /* 1 magnitude, 2 power                                  */
+    int n_mels;         /* 1 .. 128                                              */
+    int log;            /* ASR_STFT_LOG_NONE / _LN / _LOG10 / _DB (10 log10)     */
+    int floor_mode;     /* _CLAMP: log(max(m, floor)); _ADD: log(m + floor)      */
+    float floor;        /* > 0 when log != NONE                                  */
+    float dyn_range;    /* > 0: x = max(x, max over the utterance - dyn_range); 0 off */
+    float shift, scale; /* x = (x + shift) * scale, after the clamp              */
+    int drop_last;      /* 1: one frame fewer (Whisper drops the last frame)     */
+} asr_stft_config;
+
+typedef struct asr_stft asr_stft_t;
+
+/* Host only.  Frames of an n_samples signal (< 0: bad configuration): with
+ * center 1 + n / hop, or 0 when n <= n_fft / 2 (torch refuses the reflection);
+ * without, n < n_fft ? 0 : 1 + (n - n_fft) / hop; drop_last then subtracts one,
+ * never below 0. */
+int asr_stft_num_frames(const asr_stft_config* cfg, int n_samples);
+/* Host only, no HIP call: the fp32 DFT basis the device uses, h_G[n_fft][2 NBp],
+ * NBp = n_fft / 2 + 1 rounded up to 16: column k < n_fft / 2 + 1 is
+ * w'[n] cos(2 pi ((n k) mod n_fft) / n_fft), column NBp + k is minus the sine,
+ * computed in double (the integer mod keeps the argument exact) and rounded
+ * once; the other columns are zeros.  ASR_ERR_ARG: a NULL pointer;
+ * ASR_ERR_UNSUPPORTED: a configuration outside the ranges above. */
+int asr_stft_host_basis(const asr_stft_config* cfg, const float* h_window, float* h_G);
+/* h_window[win_length], h_mel[n_mels][n_fft / 2 + 1] on the host.  Validates
+ * before any HIP call — ASR_ERR_ARG: a NULL pointer; ASR_ERR_UNSUPPORTED: a
+ * configuration outside the ranges above, or one whose 64-frame tile
+ * (63 hop + n_fft samples) does not fit in LDS beside the basis slab — then
+ * builds the basis and uploads the tables (synchronous). */
+int asr_stft_create(const asr_stft_config* cfg, const float* h_window, const float* h_mel, asr_stft_t** out);
+int asr_stft_destroy(asr_stft_t* h);
+/* Bytes of d_work for asr_stft_fwd: one float per 64-frame tile and utterance
+ * when dyn_range > 0, 0 otherwise (and for a non-positive T or B).  It needs no
+ * initialisation. */
+size_t asr_stft_workspace_bytes(const asr_stft_t* h, int T, int B);
+/* d_wave batch-major [B][ldw], ldw >= S; d_nsamples device int32 [B], clamped
+ * to [0, S] (NULL: S for all).  pad_to = 0: utterance b is its n_b samples;
+ * pad_to >= S: it is its n_b samples followed by zeros up to pad_to, and the
+ * reflection and the frame count use pad_to (Whisper's pad to 30 s; the frames
+ * of the zero tail are valid frames and take part in max_b).  Nothing at or
+ * past n_b is read as a value (selection: the buffer may hold NaN there).
+ * d_out time-major [T][B][ldo], ldo >= n_mels, columns >= n_mels of a row are
+ * not touched; T >= asr_stft_num_frames(cfg, pad_to ? pad_to : S): all T rows
+ * are written, zeros past an utterance's frames; d_frames device int32 [B]
+ * (may be NULL) receives frames_b.  One workgroup per 64 frames of an
+ * utterance, tiles from frame 0; the DFT is a product with the basis on the
+ * fp32 matrix cores, bins in groups of 128 ascending, n ascending inside, then
+ * the mel product over the groups ascending: a frame's bits depend on the
+ * configuration and the utterance only, never on B, T, ldo, its position in
+ * the batch or the alignment of d_out.  dyn_range > 0 adds one launch that
+ * reduces the tiles' maxima (from d_work, tiles ascending) and applies the
+ * clamp and the affine step in place.  Asynchronous on s, no allocation, no
+ * host sync: capturable as a linear chain.  Checks, all before any HIP call —
+ * ASR_ERR_ARG: a NULL required pointer, a non-positive size, pad_to < 0 or
+ * 0 < pad_to < S, ldw < S, ldo < n_mels, T too small, d_work NULL with
+ * dyn_range > 0; ASR_ERR_UNSUPPORTED: more than 2^25 output rows T*B,
+ * B > 65535. */
+int asr_stft_fwd(asr_stft_t* h, const float* d_wave, long ldw, const int32_t* d_nsamples, int B, int S, int pad_to,
+                 float* d_out, long ldo, int32_t* d_frames, void* d_work, int T, asr_stream_t s);
+
+/* out[t B + b][n] = act(x[t B + b][n]) + pos[t][n] over the N columns of a
+ * time-major [T*B, N] buffer: the GELU after Whisper's second convolution and
+ * its positional table in one pass.  act: ASR_ADD_POS_ACT_NONE, or _GELU, the
+ * exact GELU of ASR_EPI_BIAS_GELU (the same expression, the same bits).  d_pos
+ * [T][ldp]; row strides ldx, ldp, ldo >= N; columns >= N of d_out are not
+ * touched; rows t >= len[b] are zeros whatever x holds (d_lengths device int32
+ * [B], clamped to [0, T], NULL = all rows).  d_out may be d_x.  Element-wise:
+ * an element's bits depend on its x and pos alone.  One launch, asynchronous
+ * on s.  Checks, in this order, before any HIP call — ASR_ERR_ARG: NULL d_x,
+ * d_pos or d_out; non-positive T, B or N; a stride < N; an unknown act.
+ * ASR_ERR_UNSUPPORTED: T*B > INT_MAX. */
+enum { ASR_ADD_POS_ACT_NONE = 0, ASR_ADD_POS_ACT_GELU = 1 };
+int asr_add_pos_fwd(const float* d_x, long ldx, const float* d_pos, long ldp, const int32_t* d_lengths, float* d_out,
+                    long ldo, int T, int B, int N, int act, asr_stream_t s);
+
 /* ---- back-off n-gram language model: ARPA loader, exact table, scoring -----
  * No reference member is replaced: the reference decodes without a language
  * model, while every ctcdecode caller (baseline/main.py:10) passes one.  These
